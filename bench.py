@@ -1,13 +1,19 @@
 """Benchmark: batched Y.mergeUpdates / diffUpdate / encodeStateVectorFromUpdate on MI355X
 (BASELINE.json metric "merged update MB/s + docs/sec (bit-exact vs yjs) at 1/2/4/8 MI355X").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [...]
 
-One JSON line (rank 0).  Its headline (`value`, `roofline`, `cpu_baseline`) is config C2
+A plain run sets up the headline workload, warms up, times the K steps and prints one JSON line (rank 0):
+`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall milliseconds of one timed step), the
+configuration and the headline's `roofline`.  --dump-outputs DIR then writes what the last timed step returned
+(dump_outputs below).  Everything else -- the oracle parity samples, the side blocks and the CPU baselines listed
+below -- runs only with --full, which adds them to the same line as extra keys.
+
+The headline (`value`, `roofline`; `parity` and `cpu_baseline` with --full) is config C2
 (BASELINE.json configs[1]): 10 000 documents x 200 single-character Y.Text insert
 updates per GPU, one step = one batched mergeUpdates over all of them with the inputs resident in
 HBM (ygm_merge_v1_device_async: counter reset + the lean kernel; every C2 document is finished by
-the lean kernel -- asserted -- so no step needs the host-driven tiers).  Beside it, as extra keys:
+the lean kernel -- asserted -- so no step needs the host-driven tiers).  Beside it with --full, as extra keys:
 
   c2_100k  the same merge at 100 000 documents per GPU (0.47 GB in: past the 256 MiB Infinity Cache,
            so the HBM fraction is not L3-served)
@@ -64,6 +70,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the oracle parity samples, the side blocks (c2_100k, c2_1m, c4, f1, c2_mixed, v2, c3, "
+                         "c5, c5_store, host_api) and the CPU baselines; the options below that size or skip them apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--docs", type=int, default=10000, help="C2 documents per GPU")
     ap.add_argument("--updates", type=int, default=200)
     ap.add_argument("--c2big-docs", type=int, default=100000, help="C2 documents per GPU of the c2_100k block (0: skip)")
@@ -88,7 +99,10 @@ def parse():
     ap.add_argument("--block", choices=["f1", "mixed", "v2", "store"], default=None,
                     help="run one side block alone and print its JSON (counter passes: tools/pmc_blocks.py)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: gloo + the CPU oracle stand in (tests of the rank path)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and (args.dry_run or args.big or args.block):
+        ap.error("--dump-outputs writes the headline merge's device results: not with --dry-run, --big or --block")
+    return args
 
 
 def _free_port():
@@ -268,6 +282,32 @@ def _pmc(name, key):
         return d.get(key) if key else d.get("hbm_bytes_per_launch")
     except Exception:
         return None
+
+
+DUMP_BUDGET = 64 << 20   # bytes of .npy payload --dump-outputs may write in all
+
+
+def dump_outputs(dirname, st, off, ln, data, budget=DUMP_BUDGET, seed=0):
+    """--dump-outputs: what a caller of the timed merge receives, per document in document order -- `status` (float32),
+    `len` (float64: output bytes) and `data` (float32: the merged updates' bytes, concatenated without gaps; the
+    engine's slot offsets are left out, a caller reads through them).  The corpus is seeded, so two builds given
+    the same arguments write comparable files.  An array over its share of the budget is written as a fixed
+    sample: the elements at sorted indices drawn once from default_rng(seed)."""
+    ln = np.where(st == 0, ln, 0).astype(np.int64)
+    total = int(ln.sum())
+    pos = np.cumsum(ln) - ln
+    idx = np.repeat(off.astype(np.int64) - pos, ln) + np.arange(total, dtype=np.int64)
+    arrays = {"status": st.astype(np.float32), "len": ln.astype(np.float64),
+              "data": np.frombuffer(data, np.uint8)[idx].astype(np.float32)}
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        rng = np.random.default_rng(seed)
+        share = budget // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                arrays[k] = a[np.sort(rng.choice(a.size, share // a.itemsize, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------- workloads
@@ -766,7 +806,9 @@ def run_rank(args, rank, world, dist, be, dev=None):
     dt = allmax(dt, dist, dev)
     node = gather_stats({"docs": c["n"], "updates": c["n_upd"], "bytes_in": c["bytes"], "bytes_out": out_bytes, "kernel_ms": kms}, dist, dev)
     parity = None
-    if rank == 0 and not args.dry_run:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *be.fetch(r, c["n"]))
+    if rank == 0 and args.full and not args.dry_run:
         import oracle
         from tools import synth
         st, off, ln, data = be.fetch(r, c["n"])
@@ -798,6 +840,8 @@ def run_rank(args, rank, world, dist, be, dev=None):
             "parity": parity,
         }
     del c
+    if not args.full:
+        return line
     # ---- C2 at 100 000 documents per GPU (past the Infinity Cache)
     if args.c2big_docs:
         cb = c2_corpus(be, "c2b-", args.c2big_docs, args.updates, rank, world)

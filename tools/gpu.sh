@@ -1,7 +1,7 @@
 #!/bin/bash
 # One launcher for every GPU-box job (run through gpurun from the repository root):
 #
-#   gpurun --timeout 900 -- 'bash tools/gpu.sh "tests && bench main --steps 20 && kt c4 -- python3 tools/bench_configs.py c4 1000000"'
+#   bash tools/gpu.sh "tests && bench main --full --steps 20 && kt c4 -- python3 tools/bench_configs.py c4 1000000"
 #
 # The argument is a chain of the steps below joined with && (the chain stops at the first failure, and a
 # step that times out, aborts or faults stops it too: nothing more runs on the GPU in that call).  Every
