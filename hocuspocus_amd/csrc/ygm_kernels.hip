@@ -907,14 +907,6 @@ __global__ __launch_bounds__(256) void k_route_big(const uint64_t* __restrict__ 
 // While document i is parsed, the chunk loads of document i + 1 are in flight (register
 // prefetch) and the scalar header loads of documents i + 1 / i + 2 run ahead of them.
 // Documents outside the lean shape are appended to `defer_list` for k_merge_wave.
-// the lane id, recomputed where it is used: an address derived from threadIdx.x is loop-invariant across the
-// persistent loop's documents, so the compiler hoists it out and, at the 128-VGPR cap, spills it -- and the copy
-// loops then wait on a scratch reload per document
-YDEV uint32_t lane_opaque() {
-  uint32_t li;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(li));
-  return li;
-}
 struct LeanHdr { uint32_t u0, k; uint64_t b0, nbytes; };
 
 // Document headers come through VECTOR loads (lane-dependent addresses, then readlane): a
@@ -1113,17 +1105,21 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
       uint8_t* o = out + slot;
       // compact input form: a single update whose length is not the document's bytes (include/ygm.h: an error)
       const bool badlen = upd_len != nullptr && k == 1 && (uint64_t)upd_len[h.u0] != nbytes;
-      if (badlen) { size = 0; if (l == 0) { out_off[d] = slot; out_len[d] = 0; status[d] = ST_MALFORMED; } }
-      else if (slot + (k == 0 ? 2 : nbytes) > out_cap) { size = 0; if (l == 0) { out_off[d] = slot; out_len[d] = 0; status[d] = ST_NOMEM; } }
+      // (one store of the three results for every outcome: a constant 0 length of the error outcomes is hoisted out
+      // of the persistent loop into a register pair the parse has no room for)
+      uint64_t olen = k == 0 ? 2 : nbytes;
+      int32_t ost = ST_OK;
+      if (badlen) { size = 0; olen = 0; ost = ST_MALFORMED; }
+      else if (slot + olen > out_cap) { size = 0; olen = 0; ost = ST_NOMEM; }
       else {
         if (k == 0) { if (l == 0) { o[0] = 0; o[1] = 0; } }
         else for (uint64_t c = lane_opaque(); c * 16 < nbytes; c += WAVE) {   // unaligned 16-byte loads (arena tail padding >= 16), aligned stores
           uint4 x; __builtin_memcpy(&x, arena + b0 + 16 * c, 16);
           *(uint4*)(o + 16 * c) = x;
         }
-        if (l == 0) { out_off[d] = slot; out_len[d] = k == 0 ? 2 : nbytes; status[d] = ST_OK; }
-        payload += k == 0 ? 2 : nbytes;
+        payload += olen;
       }
+      if (l == 0) { out_off[d] = slot; out_len[d] = olen; status[d] = ost; }
       // drain the copy's loads here: left pending into the join with the parse path, the waitcnt pass
       // makes the parse wait for them -- and, counters being in order, for the next header's loads
       __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
@@ -1134,7 +1130,39 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     bool bad = false;
 #pragma unroll
     for (int q = 0; q < LN_ROWS; q++) { hs[q] = false; hasd[q] = false; }
-    if (go) {
+    if (go && !WIDE && YGM_LN_FASTPARSE) {
+      // phase-major: the windows and tail bytes of YGM_LN_FASTGROUP rows are loaded (invalid lanes: the first
+      // update, 0 bytes), then those rows' fast parses run, straight-line; a row with a valid lane that is not
+      // fast is parsed again, whole, by lean_parse
+#pragma unroll
+      for (int q = 0; q < LN_ROWS; q++) {
+        const bool valid = l + WAVE * q < k;
+        us[q] = valid ? us[q] : shift; un[q] = valid ? un[q] : 0u;
+      }
+      bool slow[LN_ROWS];
+#pragma unroll
+      for (int g = 0; g < LN_ROWS; g += YGM_LN_FASTGROUP) {
+        LFastIn F[YGM_LN_FASTGROUP];
+#pragma unroll
+        for (int q = g; q < g + YGM_LN_FASTGROUP; q++) lean_fast_load(lin, us[q], un[q], F[q - g]);
+#pragma unroll
+        for (int q = g; q < g + YGM_LN_FASTGROUP; q++) {
+          const bool valid = l + WAVE * q < k;
+          bool hd;
+          slow[q] = !lean_parse_fast(F[q - g], us[q], un[q], rec[q], hd) && valid;
+          hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
+          hasd[q] = valid && hd;
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < LN_ROWS; q++) {
+        if (__ballot(slow[q]) == 0) continue;
+        const bool valid = l + WAVE * q < k;
+        if (valid) { rec[q] = lean_parse<LN_UMAX>(lin, us[q], un[q]); bad |= !rec[q].ok; }
+        hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
+        hasd[q] = valid && rec[q].ok && lin[lean_ds_pos(us[q], rec[q].span)] != 0;
+      }
+    } else if (go) {
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) {
         const bool valid = l + WAVE * q < k;
@@ -1292,13 +1320,17 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
           if (size > (uint32_t)C::OUT || ((size + 15u) & ~15u) > cap || slot + size > out_cap) defer = true;
           else {
             // ---- emit into the LDS output buffer: structs (funnel copies), block headers, document header, delete set
+            uint32_t ct[LN_ROWS], cw = 0;   // destinations; the widest run (head + bytes) of the document
 #pragma unroll
             for (int r = 0; r < LN_ROWS; r++) {
-              const uint32_t j = l + WAVE * r;
               const uint32_t b = (osp[r] >> 13) & 7u;
-              const uint32_t t = (oex[r] & 0xFFFFu) + ((b < 4u ? HC0 : HC1) >> (8u * (b & 3u)) & 0xFFu);
-              lean_copy<WIDE>(lout, lin, j < nrec, t, osp[r] >> 16, osp[r] & 0x3Fu);
+              ct[r] = (oex[r] & 0xFFFFu) + ((b < 4u ? HC0 : HC1) >> (8u * (b & 3u)) & 0xFFu);
+              cw = max(cw, l + WAVE * r < nrec ? (ct[r] & 3u) + (osp[r] & 0x3Fu) : 0u);
             }
+            const uint32_t cls = lean_copy_class<WIDE>(cw);
+#pragma unroll
+            for (int r = 0; r < LN_ROWS; r++)
+              lean_copy<WIDE>(lout, lin, cls, l + WAVE * r < nrec, ct[r], osp[r] >> 16, osp[r] & 0x3Fu);
             if (l < nC) {
               uint32_t t = lds_vu(lout, hpos, hcnt);
               t = lds_vu(lout, t, ctl);

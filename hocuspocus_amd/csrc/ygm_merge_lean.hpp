@@ -3,7 +3,7 @@
 //
 // Shape it takes (the onChange stream of row a4/a5): k >= 2 updates of
 // <= 32 bytes, each either ONE client block of Items (ContentString ASCII / ContentDeleted)
-// or no structs at all (a deletion: delete set only), at most 4 distinct struct clients,
+// or no structs at all (a deletion: delete set only), at most 8 distinct struct clients,
 // every client's updates clock-contiguous in log order, and at most 64 delete-set ranges
 // in the document.  For such a document rule R-M degenerates to:
 // blocks by client descending, each block = the clients' structs in log order, copied
@@ -16,13 +16,23 @@
 // Phases (all in registers except the two LDS byte buffers):
 //   stage   every 16-byte chunk load of the document issued before the first wait
 //   parse   lane per update (rows q = 0..3 hold updates l + 64q); the update's bytes are
-//           read as three aligned ds_read_b128 and normalised to a 32-byte register
-//           window; varuint ends come from a terminator bit mask (no byte loop)
+//           read as nine dword-aligned ds_read_b32 and funnelled (v_alignbyte) into a 32-byte
+//           register window (64 in the wide kernel); varuint ends come from a terminator bit
+//           mask (no byte loop).  Narrow kernel: phase-major -- the loads of all four rows
+//           are issued together and lean_parse_fast decides the single-Item / delete-
+//           set-only shapes from the window and the update's last three bytes, with no read
+//           that depends on the window; only a row holding another shape runs lean_parse,
+//           the generic grammar (multi-struct, parents, ContentDeleted, longer strings),
+//           whose dependent byte reads cost an LDS round trip each
 //   clients distinct clients by wave vote, ranked descending (scalar)
-//   scan    per-row DPP scans of packed 16-bit per-client byte counts; predecessor
-//           clock checks by one bpermute per row
+//   scan    log order: a record's index inside its block by per-row DPP scans of packed 8-bit
+//           per-block counts.  Sorted order: the records are scattered to LDS by (block,
+//           index) -- clock, end, packed source -- and read back a row at a time with their
+//           predecessor's (contiguity: clock == the previous record's end), then one DPP scan
+//           per row of the packed (structs, bytes) gives every record's byte offset
 //   emit    ds_or_b32 of funnel-shifted source dwords into a zeroed LDS output buffer
-//           (branch-free, order-free), then 16-byte coalesced stores
+//           (branch-free, order-free; one width class per document), then 16-byte coalesced
+//           stores
 #pragma once
 #include "ygm_common.hpp"
 #include "ygm_merge_wave.hpp"
@@ -73,6 +83,15 @@ typedef __attribute__((address_space(3))) uint32_t LB32;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) u32x4 LB128;
 
+// the lane id, recomputed where it is used: an address derived from threadIdx.x is loop-invariant across the
+// persistent loop's documents, so the compiler hoists it out and, at the 128-VGPR cap, spills it -- and the copy
+// loops then wait on a scratch reload per document (the delete-set sort's lane predicates likewise: 21 stages'
+// compares kept in the prologue cost two VGPRs of lane-written scalars for a path most documents never take)
+YDEV uint32_t lane_opaque() {
+  uint32_t li;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(li));
+  return li;
+}
 // ---- DPP wave scans (row_shr within 16-lane rows, then row_bcast:15 / row_bcast:31)
 YDEV uint32_t dpp_incl_add(uint32_t x) {
   x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);   // row_shr:1
@@ -293,6 +312,92 @@ YDEV LRec lean_parse(LB8* in, uint32_t s, uint32_t n) {
   return R;
 }
 
+// ---- phase-major fast parse (narrow kernel): the shapes a debounce log is made of, decided from the
+// window registers and two bytes read beside the window, with no read that depends on the window
+//   * ONE Item of one block: ContentString of one ASCII character, with an origin and/or a right origin
+//     (no 0x20 bit), or with a parent ykey of ASCII bytes and neither (a document's first insert), followed
+//     by a one-byte delete set that ends the update;
+//   * no structs: a delete set only.
+// Such an update's string length, character and delete-set count are its last three bytes, so their
+// address is known from (s, n) alone: the loads of every row are issued before the first is used.  A
+// lane that is not fast proves nothing: its row runs lean_parse.  A fast lane's record is lean_parse's.
+#ifndef YGM_LN_FASTPARSE
+#define YGM_LN_FASTPARSE 1    // 0 (experiment): row-major lean_parse only, as before the fast parse
+#endif
+#ifndef YGM_LN_FASTGROUP
+#define YGM_LN_FASTGROUP 4    // rows whose loads are issued together (1, 2 or 4)
+#endif
+#ifndef YGM_LN_FASTPARENT
+#define YGM_LN_FASTPARENT 1   // 0 (experiment): the parent-ykey first insert is left to lean_parse
+#endif
+struct LFastIn {
+  uint32_t d[8];     // the update's 32-byte window
+  uint32_t tl, td;   // bytes n - 3 (the string length of the fast shape) and n - 1 (its delete-set count)
+};
+YDEV void lean_fast_load(LB8* in, uint32_t s, uint32_t n, LFastIn& F) {
+  lean_window(in, s, F.d);
+  const uint32_t t = s + (n > 3u ? n : 3u);
+  F.tl = in[t - 3u]; F.td = in[t - 1u];
+}
+// true: R is the update's record (R.ok) and hasd whether its delete set is non-empty
+YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, LRec& R, bool& hasd) {
+  const uint32_t (&d)[8] = F.d;
+  const uint32_t H = lean_hmask(d);
+  uint32_t Z = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    Z |= top8((d[2 * j] - 0x01010101u) & ~d[2 * j], (d[2 * j + 1] - 0x01010101u) & ~d[2 * j + 1]) << (8 * j);
+  const uint32_t V = n >= 32u ? 0xFFFFFFFFu : ((1u << n) - 1u);
+  const uint32_t T = ~H & V, HV = H & V;
+  // lean_parse's whole-window checks (a varuint of >= 8 bytes, a zero byte after a top-bit byte)
+  const uint32_t h2 = HV & (HV >> 1), h4 = h2 & (h2 >> 2), h7 = h4 & (h4 >> 3);
+  uint32_t bad = h7 | (Z & (HV << 1) & V);
+  const uint32_t b0 = d[0] & 0xFFu, b1 = (d[0] >> 8) & 0xFFu;
+  bad |= (b0 ^ 1u) | (b1 ^ 1u);                // one block of one struct
+  // client (bytes 2..e) and clock (bytes p..e): ends from the terminator mask.  A varuint that runs out
+  // of the window ends at >= 31, which the length test below (the structs end at n - 1 <= 31) refuses
+  uint32_t e = 2u + lnctz(T >> 2);
+  const uint32_t cl_n = e - 1u;
+  const uint32_t client = pext32(__builtin_amdgcn_alignbyte(d[1], d[0], 2u), (d[1] >> 16) & 0xFFu, cl_n);
+  bad |= (cl_n > 5u ? 1u : 0u) | (cl_n == 5u ? ((d[1] >> 16) & 0x70u) : 0u);
+  const uint32_t p = e + 1u;                   // 3..7 when the client is good
+  const uint32_t pc = p < 31u ? p : 31u;
+  e = pc + lnctz(T >> pc);
+  const uint32_t ck_n = e - p + 1u;
+  const uint64_t U01 = ((uint64_t)d[1] << 32) | d[0], U23 = ((uint64_t)d[3] << 32) | d[2];
+  const uint64_t cw = (U01 >> (8u * (p & 7u))) | (p & 7u ? (U23 << (64u - 8u * (p & 7u))) : 0ull);   // bytes p..p+7
+  const uint32_t clock = pext32((uint32_t)cw, (uint32_t)(cw >> 32) & 0xFFu, ck_n);
+  bad |= (ck_n > 5u ? 1u : 0u) | (ck_n == 5u ? ((uint32_t)(cw >> 32) & 0x70u) : 0u);
+  bad |= clock == 0xFFFFFFFFu ? 1u : 0u;       // clock + 1 stays a uint32
+  const uint32_t ip = e + 1u;                  // the info byte: byte ck_n of cw (ck_n <= 5), the two bytes after it too
+  const uint32_t x3 = (uint32_t)(cw >> (8u * (ck_n & 7u)));
+  const uint32_t info = x3 & 0xFFu;
+  // origin and/or right origin: the 2nd / 4th terminator from ip + 1 (a missing one lands past the window)
+  const uint32_t pp = ip + 1u < 31u ? ip + 1u : 31u;
+  const uint32_t t0 = (T >> pp) | 0x80000000u, t1 = t0 & (t0 - 1u), t2 = t1 & (t1 - 1u), t3 = t2 & (t2 - 1u);
+  const uint32_t nsk = ((info >> 6) & 1u) + ((info >> 7) & 1u);
+  uint32_t pl = nsk == 2u ? pp + lnctz(t3) + 1u : pp + lnctz(t1) + 1u;   // the string length's position
+  bool shape = nsk != 0u && (info & 0x3Fu) == 4u;
+#if YGM_LN_FASTPARENT
+  {
+    // parent ykey: info 0x04, parentInfo 1, key length, ASCII key
+    const uint32_t lk = (x3 >> 16) & 0xFFu;
+    const uint32_t kp = ip + 3u < 31u ? ip + 3u : 31u;
+    const bool par = x3 << 16 == 0x01040000u && lk < 32u && ((HV >> kp) & ((1u << (lk & 31u)) - 1u)) == 0u;
+    pl = nsk == 0u ? ip + 3u + lk : pl;
+    shape = shape || (nsk == 0u && par);
+  }
+#endif
+  // the length byte, one ASCII character and the delete set's count end the update
+  const bool item = bad == 0u && shape && pl + 3u == n && n <= 32u && F.tl == 1u && ((HV >> ((n - 2u) & 31u)) & 1u) == 0u;
+  const bool dsonly = b0 == 0u && n >= 2u && n <= 32u;
+  R.ok = true;
+  R.client = item ? client : 0u; R.clock = item ? clock : 0u; R.clen = item ? 1u : 0u;
+  R.span = item ? ((s + ip) << 16) | (1u << 8) | ((n - 1u - ip) & 0xFFu) : 0u;
+  hasd = item ? F.td != 0u : b1 != 0u;
+  return item || dsonly;
+}
+
 // byte p (0..31) of a 32-byte register window.  Selects by bit masks (v_bfi): a ?: over array elements is
 // turned into a scratch-indexed load by the compiler
 YDEV uint32_t w2_byte(const uint32_t (&d)[8], uint32_t p) {
@@ -385,13 +490,20 @@ YDEV void lds_or_copy(LB8* out, LB8* in, uint32_t t, uint32_t s, uint32_t n) {
     __hip_atomic_fetch_or(od + j, v & m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
 }
-// one row of struct copies: 6 destination dwords when every lane's run fits (C2 structs are
-// <= 19 bytes), else 9, else (the wide kernel's runs of up to 63 bytes) 17
+// struct copies: 6 destination dwords when every run of the document fits (C2 structs are <= 19 bytes),
+// else 9, else (the wide kernel's runs of up to 63 bytes) 17 -- one decision per document (cw: the lane's
+// widest head + bytes), wave-uniform
 template <int WIDE>
-YDEV void lean_copy(LB8* out, LB8* in, bool go, uint32_t t, uint32_t s, uint32_t n) {
-  if (__ballot(go && (t & 3u) + n > 24u) == 0) { if (go) lds_or_copy<6>(out, in, t, s, n); }
-  else if (!WIDE || __ballot(go && (t & 3u) + n > 36u) == 0) { if (go) lds_or_copy<9>(out, in, t, s, n); }
-  else if (go) lds_or_copy<17>(out, in, t, s, n);
+YDEV uint32_t lean_copy_class(uint32_t cw) {
+  if (__ballot(cw > 24u) == 0) return 0u;
+  return (!WIDE || __ballot(cw > 36u) == 0) ? 1u : 2u;
+}
+template <int WIDE>
+YDEV void lean_copy(LB8* out, LB8* in, uint32_t cls, bool go, uint32_t t, uint32_t s, uint32_t n) {
+  if (!go) return;
+  if (cls == 0u) lds_or_copy<6>(out, in, t, s, n);
+  else if (!WIDE || cls == 1u) lds_or_copy<9>(out, in, t, s, n);
+  else lds_or_copy<17>(out, in, t, s, n);
 }
 YDEV uint32_t lds_vu(LB8* out, uint32_t t, uint32_t v) {
   while (v > 127u) { out[t++] = (uint8_t)(0x80u | (v & 127u)); v >>= 7; }
@@ -413,39 +525,39 @@ YDEV void dpp_max64_step(uint32_t& hi, uint32_t& lo) {
 }
 // lane l's value of x at lane l ^ J (J = 1, 2: quad permutes; 4, 8: row shifts by lane bit; 16, 32: bpermute)
 template <int J>
-YDEV uint32_t lane_xor(uint32_t x) {
+YDEV uint32_t lane_xor(uint32_t x, uint32_t l) {
   if (J == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
   if (J == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
   if (J == 4 || J == 8) {
     const uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x100 | J, 0xF, 0xF, false);   // row_shl:J (lane + J)
     const uint32_t dn = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x110 | J, 0xF, 0xF, false);   // row_shr:J (lane - J)
-    return (threadIdx.x & J) ? dn : up;
+    return (l & J) ? dn : up;
   }
   return (uint32_t)__shfl_xor((int)x, J, 64);
 }
 // one compare-exchange stage of a 64-lane bitonic sort (ascending) on the key (a, b, c)
 template <int K, int J>
-YDEV void bitonic_step(uint32_t& a, uint32_t& b, uint32_t& c) {
-  const uint32_t oa = lane_xor<J>(a), ob = lane_xor<J>(b), oc = lane_xor<J>(c);
+YDEV void bitonic_step(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t l) {
+  const uint32_t oa = lane_xor<J>(a, l), ob = lane_xor<J>(b, l), oc = lane_xor<J>(c, l);
   const bool lt = oa < a || (oa == a && (ob < b || (ob == b && oc < c)));   // other < mine
-  const uint32_t l = threadIdx.x;
   const bool lower = (l & J) == 0, asc = (l & K) == 0;
   const bool take = lower == asc ? lt : !lt;   // the lower lane of an ascending pair keeps the minimum
   a = take ? oa : a; b = take ? ob : b; c = take ? oc : c;
 }
 template <int K, int J>
-YDEV void bitonic_merge(uint32_t& a, uint32_t& b, uint32_t& c) {
-  bitonic_step<K, J>(a, b, c);
-  if constexpr (J > 1) bitonic_merge<K, J / 2>(a, b, c);
+YDEV void bitonic_merge(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t l) {
+  bitonic_step<K, J>(a, b, c, l);
+  if constexpr (J > 1) bitonic_merge<K, J / 2>(a, b, c, l);
 }
 // sorts the 64 lanes' distinct keys (a, b, c) ascending: lane l gets the l-th smallest
 YDEV void lane_bitonic3(uint32_t& a, uint32_t& b, uint32_t& c) {
-  bitonic_merge<2, 1>(a, b, c);
-  bitonic_merge<4, 2>(a, b, c);
-  bitonic_merge<8, 4>(a, b, c);
-  bitonic_merge<16, 8>(a, b, c);
-  bitonic_merge<32, 16>(a, b, c);
-  bitonic_merge<64, 32>(a, b, c);
+  const uint32_t l = lane_opaque();   // (the stages' lane predicates are computed here, not in the kernel's prologue)
+  bitonic_merge<2, 1>(a, b, c, l);
+  bitonic_merge<4, 2>(a, b, c, l);
+  bitonic_merge<8, 4>(a, b, c, l);
+  bitonic_merge<16, 8>(a, b, c, l);
+  bitonic_merge<32, 16>(a, b, c, l);
+  bitonic_merge<64, 32>(a, b, c, l);
 }
 YDEV uint64_t lean_max_scan64(uint64_t v) {   // inclusive prefix max over the wave (DPP, as dpp_incl_max)
   uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
