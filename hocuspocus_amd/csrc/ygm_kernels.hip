@@ -45,7 +45,17 @@ __device__ unsigned long long ygm_diag_ts[16384 * 8];
 #define DIAG_NOW() __builtin_amdgcn_s_memrealtime()
 #define DIAG_PUT(i, v) do { if (threadIdx.x == 0) ygm_diag_ts[(blockIdx.x & 16383u) * 8 + (i)] = (v); } while (0)
 #define DIAG_C(...) __VA_ARGS__
+// lean kernel, per wave: shader cycles spent at the vmcnt(0) a document's first staging write sits behind (the
+// prefetch chunks -- and, the counter being in order, the previous document's output stores), and in the whole
+// persistent loop: ygm_diag_sw[wave * 2 + {0, 1}]
+__device__ unsigned long long ygm_diag_sw[16384 * 2];
+#define DIAGSW_T0 unsigned long long _sw = 0; const unsigned long long _sl = __builtin_amdgcn_s_memtime();
+#define DIAGSW_WAIT do { const unsigned long long _a = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0x0F70); _sw += __builtin_amdgcn_s_memtime() - _a; } while (0)
+#define DIAGSW_END do { if (threadIdx.x == 0) { ygm_diag_sw[(blockIdx.x & 16383u) * 2] = _sw; ygm_diag_sw[(blockIdx.x & 16383u) * 2 + 1] = __builtin_amdgcn_s_memtime() - _sl; } } while (0)
 #else
+#define DIAGSW_T0
+#define DIAGSW_WAIT
+#define DIAGSW_END
 #define DIAGL_T0
 #define DIAGL(i)
 #define DIAG_NOW() 0ull
@@ -933,17 +943,22 @@ YDEV LeanHdr lean_hdr_of(uint32_t du, uint64_t bo) {
   h.b0 = b0; h.nbytes = b1 - b0;
   return h;
 }
+// blocked layout: lane l owns updates (and, in the sorted domain, record slots) 4l .. 4l+3.  Does its slot q lie
+// below n, 4l + q < n?  Against a scalar threshold, so no per-slot index registers live across the loop
+YDEV bool ln_owns(uint32_t l, int q, uint32_t n) { return l < ((n + (uint32_t)(LN_ROWS - 1 - q)) >> 2); }
 template <int WIDE>
 YDEV bool lean_stageable(const LeanHdr& h) {
   return h.k >= 2 && h.k < (uint32_t)(WAVE * LN_ROWS) && (h.b0 & 15u) + h.nbytes <= (uint64_t)LnCfg<WIDE>::IN;
 }
-// issues the loads of one document: staged chunks and the per-row update offsets.  Every
+// issues the loads of one document: staged chunks and the lane's update offsets.  Every
 // load is unconditional (clamped addresses) so the prefetch registers are dead between the
 // staging of one document and the prefetch of the next (no loop-carried live ranges).
+// Blocked layout: lane l owns updates 4l .. 4l+3 (slot q = update 4l + q).  rx[0..3] are their
+// lengths (LENS) or rx[0..4] the offsets of updates 4l .. 4l+4 (update i spans rx[q] .. rx[q+1]).
 template <int WIDE, int LENS = 0>
 YDEV void lean_prefetch(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ upd_off, const uint16_t* __restrict__ upd_len,
-                        const LeanHdr& h, bool go, u32x4 (&v)[(LnCfg<WIDE>::IN + 16 * WAVE - 1) / (16 * WAVE)], uint32_t (&rx)[LN_ROWS],
-                        uint32_t (&ry)[LN_ROWS]) {
+                        const LeanHdr& h, bool go, u32x4 (&v)[(LnCfg<WIDE>::IN + 16 * WAVE - 1) / (16 * WAVE)],
+                        uint32_t (&rx)[LN_ROWS + 1]) {
   const uint32_t l = threadIdx.x;
   const uint64_t a0 = go ? (h.b0 & ~15ull) : 0ull;
   const uint32_t last = go ? (uint32_t)(((h.b0 & 15u) + h.nbytes + 15) / 16) - 1u : 0u;
@@ -955,20 +970,22 @@ YDEV void lean_prefetch(const uint8_t* __restrict__ arena, const uint64_t* __res
   // low dwords only (offsets inside one document differ by < 2^32; whole-register loads keep
   // the allocator from reusing a dead high half while the load is in flight -- a forced wait)
   const uint32_t kk = go ? h.k : 0u;
-  if (LENS) {   // the rows' update lengths (2 bytes each); offsets by a scan at staging
+  // (the opaque lane id: as functions of threadIdx.x the four update indexes are hoisted out of the persistent loop,
+  // four VGPRs the kernel does not have)
+  const uint32_t l4 = LN_ROWS * lane_opaque();
+  if (LENS) {   // the lane's update lengths (2 bytes each); offsets by a scan at staging
 #pragma unroll
     for (int q = 0; q < LN_ROWS; q++) {
-      const uint32_t i = l + WAVE * q;
+      const uint32_t i = l4 + q;
       rx[q] = upd_len[h.u0 + (i < kk ? i : 0u)];
     }
     return;
   }
   const uint32_t* off32 = (const uint32_t*)upd_off;
 #pragma unroll
-  for (int q = 0; q < LN_ROWS; q++) {
-    const uint32_t i = l + WAVE * q;
-    const uint32_t ix = h.u0 + (i < kk ? i : 0u);
-    rx[q] = off32[2ull * ix]; ry[q] = off32[2ull * ix + 2];
+  for (int q = 0; q <= LN_ROWS; q++) {   // entry kk is the document's end
+    const uint32_t i = l4 + q;
+    rx[q] = off32[2ull * (h.u0 + (i <= kk ? i : 0u))];
   }
 }
 
@@ -1019,11 +1036,11 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
   LeanHdr hn = lean_hdr_of(du, lean_bo_load<LENS>(upd_off, doc_off, du, d, n_docs));
   du = lean_du_load(doc_upd, LN_AHEAD(1), n_docs);                  // header pipeline: doc_upd one document ahead
   u32x4 v[(C::IN + 16 * WAVE - 1) / (16 * WAVE)];
-  uint32_t rx[LN_ROWS], ry[LN_ROWS];
+  uint32_t rx[LN_ROWS + 1];
 #pragma unroll
-  for (int q = 0; q < LN_ROWS; q++) { rx[q] = 0; ry[q] = 0; }
+  for (int q = 0; q <= LN_ROWS; q++) rx[q] = 0;
   bool gn = !force_seq && lean_stageable<WIDE>(hn);
-  lean_prefetch<WIDE, LENS>(arena, upd_off, upd_len, hn, gn, v, rx, ry);
+  lean_prefetch<WIDE, LENS>(arena, upd_off, upd_len, hn, gn, v, rx);
   uint64_t payload = 0;   // this wave's output bytes: one atomic per wave, not per document
   // deferred documents: bit j of dmask = the j-th document of the current run of 64 iterations (document
   // dch + j * G), appended to defer_list with ONE atomic per run -- one atomic per document on the single
@@ -1035,9 +1052,10 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     uint32_t base = 0;
     if (l == 0) base = atomicAdd(WIDE ? &meta->wide_defer : &meta->lean_defer, (uint32_t)__popcll(dmask));
     base = __shfl(base, 0, WAVE);
-    if ((dmask >> l) & 1ull) defer_list[base + (uint32_t)__popcll(dmask & ((1ull << l) - 1ull))] = WIDE ? lst0 : dch + l * G;
+    if ((dmask >> l) & 1ull) defer_list[base + lanes_below(dmask)] = WIDE ? lst0 : dch + l * G;
     dmask = 0;
   };
+  DIAGSW_T0
   for (; WIDE ? (uint64_t)blockIdx.x + (uint64_t)it * G < n_it : d < n_docs; it++) {
     DIAGL_T0
     if (dit == 64) {
@@ -1052,6 +1070,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     const uint32_t shift = (uint32_t)(b0 & 15u);
     // ---- stage the prefetched document into LDS
     uint32_t us[LN_ROWS], un[LN_ROWS];
+    DIAGSW_WAIT;
     if (go) {
       const uint32_t nch = (uint32_t)((shift + nbytes + 15) / 16);
 #pragma unroll
@@ -1059,24 +1078,27 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         const uint32_t c = l + WAVE * j;
         if (c < nch) *(LB128*)(lin + 16 * c) = v[j];
       }
-      if (LENS) {   // offsets: an exclusive scan of the lengths over rows (update l + 64 q in lane l of row q)
-        uint32_t carry = shift;
+      if (LENS) {   // offsets: the exclusive prefix of the lane's four lengths on top of ONE wave scan of the lane totals
+        uint32_t tot = 0;
 #pragma unroll
         for (int q = 0; q < LN_ROWS; q++) {
-          un[q] = l + WAVE * q < k ? rx[q] : 0u;
-          const uint32_t inc = dpp_incl_add(un[q]);
-          us[q] = carry + inc - un[q];
-          carry += lane63(inc);
+          un[q] = ln_owns(l, q, k) ? rx[q] : 0u;
+          us[q] = tot;
+          tot += un[q];
         }
-        if (carry - shift != (uint32_t)nbytes) go = false;   // lengths that do not add up: deferred (k_build_off clamps)
+        const uint32_t inc = dpp_incl_add(tot);
+        const uint32_t base = shift + inc - tot;
+#pragma unroll
+        for (int q = 0; q < LN_ROWS; q++) us[q] += base;
+        if (lane63(inc) != (uint32_t)nbytes) go = false;   // lengths that do not add up: deferred (k_build_off clamps)
       } else {
 #pragma unroll
-        for (int q = 0; q < LN_ROWS; q++) { us[q] = shift + (rx[q] - (uint32_t)b0); un[q] = ry[q] - rx[q]; }
+        for (int q = 0; q < LN_ROWS; q++) { us[q] = shift + (rx[q] - (uint32_t)b0); un[q] = rx[q + 1] - rx[q]; }
       }
       if (!WIDE) {   // an update past the narrow window: the wide kernel's document -- defer it without parsing
         bool lng = false;
 #pragma unroll
-        for (int q = 0; q < LN_ROWS; q++) lng |= l + WAVE * q < k && un[q] > (uint32_t)LN_UMAX;
+        for (int q = 0; q < LN_ROWS; q++) lng |= ln_owns(l, q, k) && un[q] > (uint32_t)LN_UMAX;
         if (__ballot(lng)) go = false;
       }
     }
@@ -1088,7 +1110,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     DIAGL(0);
 #if defined(YGM_LEAN_STOP) && YGM_LEAN_STOP == 1   // timing experiment: stage only
     { hn = lean_hdr_of(du, lean_bo_load<LENS>(upd_off, doc_off, du, LN_AHEAD(1), n_docs)); du = lean_du_load(doc_upd, LN_AHEAD(2), n_docs);
-      gn = !force_seq && lean_stageable<WIDE>(hn); lean_prefetch<WIDE, LENS>(arena, upd_off, upd_len, hn, gn, v, rx, ry); wave_sync(); dit++; d = LN_AHEAD(1); continue; }
+      gn = !force_seq && lean_stageable<WIDE>(hn); lean_prefetch<WIDE, LENS>(arena, upd_off, upd_len, hn, gn, v, rx); wave_sync(); dit++; d = LN_AHEAD(1); continue; }
 #endif
     // ---- header of the next document (its prefetch is issued after the parse) and doc_upd of the one after
     const uint64_t bo_next = lean_bo_load<LENS>(upd_off, doc_off, du, LN_AHEAD(1), n_docs);
@@ -1136,7 +1158,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
       // fast is parsed again, whole, by lean_parse
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) {
-        const bool valid = l + WAVE * q < k;
+        const bool valid = ln_owns(l, q, k);
         us[q] = valid ? us[q] : shift; un[q] = valid ? un[q] : 0u;
       }
       bool slow[LN_ROWS];
@@ -1147,7 +1169,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         for (int q = g; q < g + YGM_LN_FASTGROUP; q++) lean_fast_load(lin, us[q], un[q], F[q - g]);
 #pragma unroll
         for (int q = g; q < g + YGM_LN_FASTGROUP; q++) {
-          const bool valid = l + WAVE * q < k;
+          const bool valid = ln_owns(l, q, k);
           bool hd;
           slow[q] = !lean_parse_fast(F[q - g], us[q], un[q], rec[q], hd) && valid;
           hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
@@ -1157,7 +1179,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) {
         if (__ballot(slow[q]) == 0) continue;
-        const bool valid = l + WAVE * q < k;
+        const bool valid = ln_owns(l, q, k);
         if (valid) { rec[q] = lean_parse<LN_UMAX>(lin, us[q], un[q]); bad |= !rec[q].ok; }
         hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
         hasd[q] = valid && rec[q].ok && lin[lean_ds_pos(us[q], rec[q].span)] != 0;
@@ -1165,7 +1187,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     } else if (go) {
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) {
-        const bool valid = l + WAVE * q < k;
+        const bool valid = ln_owns(l, q, k);
         if (valid) { rec[q] = lean_parse<WIDE ? LNW_UMAX : LN_UMAX>(lin, us[q], un[q]); bad |= !rec[q].ok; }
         else { rec[q].ok = true; rec[q].client = 0; rec[q].clock = 0; rec[q].clen = 0; rec[q].span = 0; }
         hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
@@ -1180,7 +1202,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
 #endif
     hn = lean_hdr_of(du, bo_next); du = du_next;
     gn = !force_seq && lean_stageable<WIDE>(hn);
-    lean_prefetch<WIDE, LENS>(arena, upd_off, upd_len, hn, gn, v, rx, ry);
+    lean_prefetch<WIDE, LENS>(arena, upd_off, upd_len, hn, gn, v, rx);
     defer = defer || __ballot(bad) != 0;
     if (single) { wave_sync(); dit++; d = LN_AHEAD(1); continue; }   // (dit: bit j of dmask is the run's j-th document)
 #if defined(YGM_LEAN_STOP) && YGM_LEAN_STOP == 2   // timing experiment: stage + parse
@@ -1206,24 +1228,36 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         nC++;
       }
       if (!defer) {
-        // ---- record index inside its block: per-row DPP scans of packed 8-bit per-block counts (k <= 255)
+        // ---- record index inside its block: packed 8-bit per-block counts (k <= 255) -- the exclusive prefix
+        //      over the lane's four updates on top of one DPP scan of the lane totals (blocks 0-3; one more
+        //      scan for blocks 4-7 when there are that many)
         uint32_t cA = 0, cB = 0;
         uint32_t idx[LN_ROWS];
+        {
+          uint32_t ea[LN_ROWS], ta = 0;
 #pragma unroll
-        for (int q = 0; q < LN_ROWS; q++) {
-          const uint32_t b = hs[q] ? blk[q] : 0u;
-          const uint32_t sh = 8u * (b & 3u);
-          const uint32_t pa = (hs[q] && b < 4u) ? 1u << sh : 0u;
-          const uint32_t ia = dpp_incl_add(pa);
-          uint32_t w = cA + ia - pa;
-          cA += lane63(ia);
-          if (nC > 4u) {
-            const uint32_t pb = (hs[q] && b >= 4u) ? 1u << sh : 0u;
-            const uint32_t ib = dpp_incl_add(pb);
-            w = b < 4u ? w : cB + ib - pb;
-            cB += lane63(ib);
+          for (int q = 0; q < LN_ROWS; q++) {
+            ea[q] = ta;
+            ta += (hs[q] && blk[q] < 4u) ? 1u << (8u * (blk[q] & 3u)) : 0u;
           }
-          idx[q] = (w >> sh) & 0xFFu;
+          const uint32_t ia = dpp_incl_add(ta);
+          cA = lane63(ia);
+#pragma unroll
+          for (int q = 0; q < LN_ROWS; q++) idx[q] = ia - ta + ea[q];
+          if (nC > 4u) {
+            uint32_t eb[LN_ROWS], tb = 0;
+#pragma unroll
+            for (int q = 0; q < LN_ROWS; q++) {
+              eb[q] = tb;
+              tb += (hs[q] && blk[q] >= 4u) ? 1u << (8u * (blk[q] & 3u)) : 0u;
+            }
+            const uint32_t ib = dpp_incl_add(tb);
+            cB = lane63(ib);
+#pragma unroll
+            for (int q = 0; q < LN_ROWS; q++) idx[q] = (hs[q] && blk[q] >= 4u) ? ib - tb + eb[q] : idx[q];
+          }
+#pragma unroll
+          for (int q = 0; q < LN_ROWS; q++) idx[q] = (idx[q] >> (8u * (blk[q] & 3u))) & 0xFFu;
         }
         // exclusive per-block record bases, packed 8-bit (blocks 0-3 / 4-7): the prefix sum of the
         // packed counts by byte (x * 0x01010100 adds every lower byte into the higher ones)
@@ -1250,22 +1284,34 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         wave_sync();
         // ---- sorted domain: contiguity (rule R-M without gaps / overlaps: a record's clock is the end
         //      of the previous record of its block) and the packed (structs, bytes) prefix
+        //      Lane l takes slots 4l .. 4l+3: three 16-byte reads; the predecessor of slot 4l is lane l-1's
+        //      last slot (two dword reads), the other predecessors are the lane's own registers
         uint32_t osp[LN_ROWS], oex[LN_ROWS];
         uint32_t carry = 0;
+        {
+          const u32x4 vsp = *(const LB128*)(Ssp + LN_ROWS * l), vck = *(const LB128*)(Sck + LN_ROWS * l);
+          const u32x4 ven = *(const LB128*)(Sen + LN_ROWS * l);
+          uint32_t spp = l > 0u ? Ssp[LN_ROWS * l - 1u] : 0u, ep = l > 0u ? Sen[LN_ROWS * l - 1u] : 0u;
+          uint32_t ck[LN_ROWS], tot = 0;
+          bool first[LN_ROWS];
 #pragma unroll
-        for (int r = 0; r < LN_ROWS; r++) {
-          const uint32_t j = l + WAVE * r;
-          const bool v = j < nrec;
-          const uint32_t sp = v ? Ssp[j] : 0u, ck = v ? Sck[j] : 0u;
-          const uint32_t spp = (v && j > 0u) ? Ssp[j - 1u] : 0u, ep = (v && j > 0u) ? Sen[j - 1u] : 0u;
-          const bool first = v && (j == 0u || ((spp ^ sp) & 0xE000u) != 0u);   // first record of its block
-          bad |= v && !first && ck != ep;
-          const uint32_t f = v ? (((sp >> 6) & 0x7Fu) << 16) | (sp & 0x3Fu) : 0u;
-          const uint32_t inc = carry + dpp_incl_add(f);
-          const uint32_t ex = inc - f;
+          for (int r = 0; r < LN_ROWS; r++) {
+            const bool v = ln_owns(l, r, nrec);
+            const uint32_t sp = v ? vsp[r] : 0u;
+            ck[r] = v ? vck[r] : 0u;
+            first[r] = v && ((r == 0 && l == 0u) || ((spp ^ sp) & 0xE000u) != 0u);   // first record of its block
+            bad |= v && !first[r] && ck[r] != ep;
+            spp = sp; ep = ven[r];
+            osp[r] = sp; oex[r] = tot;
+            tot += v ? (((sp >> 6) & 0x7Fu) << 16) | (sp & 0x3Fu) : 0u;
+          }
+          const uint32_t inc = dpp_incl_add(tot);
           carry = lane63(inc);
-          if (first) { Sbs[(sp >> 13) & 7u] = ex; Sfc[(sp >> 13) & 7u] = ck; }
-          osp[r] = sp; oex[r] = ex;
+#pragma unroll
+          for (int r = 0; r < LN_ROWS; r++) {
+            oex[r] += inc - tot;
+            if (first[r]) { Sbs[(osp[r] >> 13) & 7u] = oex[r]; Sfc[(osp[r] >> 13) & 7u] = ck[r]; }
+          }
         }
         wave_sync();
         // ---- block headers, lane c = block c: structs, client, first clock; header offsets by a scan
@@ -1307,7 +1353,13 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
           constexpr int NZ = (C::OUT + 80) / 16;   // 16-byte pieces of the output buffer
 #pragma unroll
           for (int j = 0; j < NZ / WAVE; j++) *(LB128*)(lout + 16 * (l + WAVE * j)) = z;
-          if (l < (uint32_t)(NZ % WAVE)) *(LB128*)(lout + 16 * (l + WAVE * (NZ / WAVE))) = z;
+          if (l < (uint32_t)(NZ % WAVE)) {
+            // (a zero of its own, made here: the shared one is kept in four VGPRs across the persistent loop for this
+            // store alone, or spilled and reloaded from scratch per document)
+            u32x4 zt = {0u, 0u, 0u, 0u};
+            asm volatile("" : "+v"(zt));
+            *(LB128*)(lout + 16 * (l + WAVE * (NZ / WAVE))) = zt;
+          }
         }
         DIAGL(2);
         defer = __ballot(bad) != 0;
@@ -1325,12 +1377,12 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
             for (int r = 0; r < LN_ROWS; r++) {
               const uint32_t b = (osp[r] >> 13) & 7u;
               ct[r] = (oex[r] & 0xFFFFu) + ((b < 4u ? HC0 : HC1) >> (8u * (b & 3u)) & 0xFFu);
-              cw = max(cw, l + WAVE * r < nrec ? (ct[r] & 3u) + (osp[r] & 0x3Fu) : 0u);
+              cw = max(cw, ln_owns(l, r, nrec) ? (ct[r] & 3u) + (osp[r] & 0x3Fu) : 0u);
             }
             const uint32_t cls = lean_copy_class<WIDE>(cw);
 #pragma unroll
             for (int r = 0; r < LN_ROWS; r++)
-              lean_copy<WIDE>(lout, lin, cls, l + WAVE * r < nrec, ct[r], osp[r] >> 16, osp[r] & 0x3Fu);
+              lean_copy<WIDE>(lout, lin, cls, ln_owns(l, r, nrec), ct[r], osp[r] >> 16, osp[r] & 0x3Fu);
             if (l < nC) {
               uint32_t t = lds_vu(lout, hpos, hcnt);
               t = lds_vu(lout, t, ctl);
@@ -1358,6 +1410,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     wave_sync();   // the next document's staging overwrites lin / lout
     d = LN_AHEAD(1);
   }
+  DIAGSW_END;
   flush_defer();
   if (l == 0 && payload) add_payload(meta, blockIdx.x, payload);
 #undef LN_AHEAD
@@ -3364,6 +3417,11 @@ using namespace ygm;
 int ygm_diag_ts_read(unsigned long long* out, int reset) {  // 16384 x 8 stamps of the lean kernel
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ygm_diag_ts), sizeof(unsigned long long) * 16384 * 8) != hipSuccess) return -1;
   (void)reset;
+  return 0;
+}
+int ygm_diag_sw_read(unsigned long long* out, int reset) {   // 16384 x 2: the lean kernel's staging-wait / loop cycles per wave
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ygm_diag_sw), sizeof(unsigned long long) * 16384 * 2) != hipSuccess) return -1;
+  if (reset) { static unsigned long long z[16384 * 2]; (void)hipMemcpyToSymbol(HIP_SYMBOL(ygm_diag_sw), z, sizeof z); }
   return 0;
 }
 int ygm_diag_ds_read(unsigned long long* out, int reset) {   // 4 delete-set union cycle sums

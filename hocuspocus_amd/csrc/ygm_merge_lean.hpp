@@ -15,7 +15,9 @@
 //
 // Phases (all in registers except the two LDS byte buffers):
 //   stage   every 16-byte chunk load of the document issued before the first wait
-//   parse   lane per update (rows q = 0..3 hold updates l + 64q); the update's bytes are
+//   parse   four updates per lane, blocked: lane l owns updates 4l .. 4l+3 (slot q = update 4l + q; row q = slot q of every lane), so a
+//           prefix sum in log order is three adds inside the lane and ONE wave scan of the lane totals;
+//           an update's bytes are
 //           read as nine dword-aligned ds_read_b32 and funnelled (v_alignbyte) into a 32-byte
 //           register window (64 in the wide kernel); varuint ends come from a terminator bit
 //           mask (no byte loop).  Narrow kernel: phase-major -- the loads of all four rows
@@ -25,11 +27,12 @@
 //           the generic grammar (multi-struct, parents, ContentDeleted, longer strings),
 //           whose dependent byte reads cost an LDS round trip each
 //   clients distinct clients by wave vote, ranked descending (scalar)
-//   scan    log order: a record's index inside its block by per-row DPP scans of packed 8-bit
-//           per-block counts.  Sorted order: the records are scattered to LDS by (block,
-//           index) -- clock, end, packed source -- and read back a row at a time with their
-//           predecessor's (contiguity: clock == the previous record's end), then one DPP scan
-//           per row of the packed (structs, bytes) gives every record's byte offset
+//   scan    log order: a record's index inside its block by one DPP scan of packed 8-bit per-block
+//           counts (a second one with more than four clients).  Sorted order: the records are
+//           scattered to LDS by (block, index) -- clock, end, packed source -- and lane l reads slots
+//           4l .. 4l+3 back as 16-byte vectors, with slot 4l - 1 for the first one's predecessor
+//           (contiguity: clock == the previous record's end), then one DPP scan of the packed
+//           (structs, bytes) gives every record's byte offset
 //   emit    ds_or_b32 of funnel-shifted source dwords into a zeroed LDS output buffer
 //           (branch-free, order-free; one width class per document), then 16-byte coalesced
 //           stores
@@ -46,7 +49,7 @@ namespace ygm {
 #define YGM_LN_OUT 4096
 #endif
 constexpr int LN_IN = YGM_LN_IN;     // staged input bytes (including the 0..15 byte alignment shift; a multiple of 16)
-constexpr int LN_ROWS = 4;      // updates per lane: k <= 256
+constexpr int LN_ROWS = 4;      // updates per lane (blocked: lane l owns 4l .. 4l+3): k <= 256
 constexpr int LN_UMAX = 32;     // bytes per update
 constexpr int LN_CMAX = 8;      // distinct struct clients per document
 
@@ -597,6 +600,8 @@ YDEV LDsUnion lean_ds_union(LB8* lin, LB32* scr, const uint32_t (&dpos)[LN_ROWS]
   U.client = 0; U.nruns = 0; U.sclock = 0; U.rend = 0;
   LB32* rc = scr; LB32* rk = scr + LN_DSMAX; LB32* re = scr + 2 * LN_DSMAX;
   LB32* rn = scr + 3 * LN_DSMAX;   // yjs 13.5 only: the record's first-seen rank (update << 8 | range index in it)
+  // (update = 4 lane + q, from lane_opaque(): as a function of threadIdx.x the three ranks are hoisted out of the
+  // persistent loop and spilled)
   uint32_t nrec = 0, bad = 0;
   LDS_T0
   // ---- records of every update's DS, in update order (the order only matters for ties, which
@@ -627,7 +632,7 @@ YDEV LDsUnion lean_ds_union(LB8* lin, LB32* scr, const uint32_t (&dpos)[LN_ROWS]
     {
       const uint64_t m = __ballot(fq);
       const uint32_t slot = nrec + lanes_below(m);
-      if (fq && slot < (uint32_t)LN_DSMAX) { rc[slot] = fcl; rk[slot] = fck; re[slot] = fck + fln; rn[slot] = (l + 64u * q) << 8; }
+      if (fq && slot < (uint32_t)LN_DSMAX) { rc[slot] = fcl; rk[slot] = fck; re[slot] = fck + fln; rn[slot] = ((uint32_t)LN_ROWS * lane_opaque() + q) << 8; }
       nrec += (uint32_t)__builtin_popcountll(m);
     }
     const bool slow = hasd[q] && !fq;
@@ -643,7 +648,7 @@ YDEV LDsUnion lean_ds_union(LB8* lin, LB32* scr, const uint32_t (&dpos)[LN_ROWS]
       has = has && c.bad == 0u;
       const uint64_t m = __ballot(has);
       const uint32_t slot = nrec + lanes_below(m);
-      if (has && slot < (uint32_t)LN_DSMAX) { rc[slot] = cl; rk[slot] = ck; re[slot] = ck + ln; rn[slot] = ((l + 64u * q) << 8) | (uint32_t)it; }
+      if (has && slot < (uint32_t)LN_DSMAX) { rc[slot] = cl; rk[slot] = ck; re[slot] = ck + ln; rn[slot] = (((uint32_t)LN_ROWS * lane_opaque() + q) << 8) | (uint32_t)it; }
       nrec += (uint32_t)__builtin_popcountll(m);
     }
     bad |= c.bad | (lean_ds_more(c) ? 1u : 0u);   // malformed, or more ranges than the loop takes

@@ -68,5 +68,16 @@ if mixed:
     L.ygm_diag_ds_read(dsb.ctypes.data, 0)
     print("delete-set union, shader cycles per document (3 reps): records", int(dsb[0]) // (3 * n_docs), "rank sort",
           int(dsb[1]) // (3 * n_docs), "runs/scans", int(dsb[2]) // (3 * n_docs))
+if not mixed:
+    # the wait in front of a document's first staging write (prefetch chunks and, vmcnt being in order, the previous
+    # document's output stores) against the wave's whole persistent loop, shader cycles of the last launch
+    L.ygm_diag_sw_read.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    sw = np.zeros(16384 * 2, np.uint64)
+    L.ygm_diag_sw_read(sw.ctypes.data, 0)
+    sw = sw.reshape(16384, 2).astype(np.int64)
+    sw = sw[sw[:, 1] > 0]
+    per_wave = -(-n_docs // max(len(sw), 1))
+    print(f"  staging wait: {sw[:, 0].mean() / per_wave:.0f} shader cycles per document, {100.0 * sw[:, 0].sum() / sw[:, 1].sum():.2f} % "
+          f"of the persistent loop ({len(sw)} waves, {sw[:, 1].mean() / per_wave:.0f} cycles per document)")
 s = e.stats()
 print("kernel_ms (3 reps)", s.kernel_ms, "lean_ms", s.lean_ms, "docs_lean", s.docs_lean)
