@@ -26,6 +26,22 @@ int ygm_k_launch_doc(int mode, const uint8_t* arena, const uint64_t* doc_off, co
                      const uint32_t* docs, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
                      uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap, hipStream_t s);
 size_t ygm_k_sv_table_bytes(uint32_t n_docs);
+int ygm_k_launch_ask_plan(const uint64_t* doc_off, uint32_t n_docs, const uint32_t* ask_doc, uint32_t n_asks, uint32_t* ask_ix,
+                          uint64_t* ask_base, uint64_t* bs, hipStream_t s);
+int ygm_k_launch_ask_status(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, int32_t* status, uint64_t* len, hipStream_t s);
+int ygm_k_launch_ask_pending(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, uint32_t* list, unsigned int* n_out,
+                             hipStream_t s);
+int ygm_k_launch_doc_lean_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
+                                 const uint32_t* ask_ix, const uint64_t* ask_base, uint32_t n_asks, uint8_t* out, uint64_t* out_off,
+                                 uint64_t* out_len, int32_t* status, void* meta, uint32_t* defer_list, uint64_t out_cap, uint8_t* tbl,
+                                 uint32_t* tbl_n, hipStream_t s);
+int ygm_k_launch_doc_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
+                            const uint32_t* docs, const uint32_t* ask_ix, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out,
+                            uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap,
+                            hipStream_t s);
+int ygm_k_launch_pend_split_g(const uint32_t* list, uint32_t P, const uint32_t* ask_ix, const uint8_t* ws, const uint64_t* out_off,
+                              const uint8_t* sv, const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc,
+                              uint8_t* dsv, int pass, hipStream_t s);
 int ygm_k_launch_snap_plan(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, void* cnt, uint64_t* ws_off,
                            uint64_t* bs, const uint8_t* claim, hipStream_t s);
 int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
@@ -38,6 +54,9 @@ int ygm_k_launch_cont(const uint8_t* st_arena, const uint64_t* st_off, const uin
 int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
                       uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
                       uint64_t base, uint32_t* pend_list, unsigned int* pend_n, hipStream_t s);
+int ygm_k_launch_snap_w(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
+                        uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
+                        uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, hipStream_t s);
 int ygm_k_launch_pend_plan(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, uint64_t* upd_off, uint32_t* doc_upd,
                            hipStream_t s);
 int ygm_k_launch_pend_copy(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const uint64_t* upd_off, uint8_t* dst,
@@ -189,6 +208,9 @@ struct ygm_ctx {
   DevBuf s_readers, s_order, s_tmp, s_ubase, s_ulen, s_cnt, s_drec;
   DevBuf big_blk, big_rec, big_list, big_scan, big_up;   // large-document tier: block tables, struct records, documents sent on, scan
   DevBuf sv_tbl, sv_tn;                // diff: sorted state-vector tables (k_sv_table) and their entry counts
+  // shared-state diff / step2: per ask the checked state id, the scanned state lengths (slot bases, n_asks + 1), scan
+  // scratch; step2: the asks of pending states and their count
+  DevBuf ask_ix, ask_base, ask_bs, ask_pl, ask_pn;
   DevBuf sn_cnt, sn_off, sn_bs, sn_ws, sn_claim, sn_pay;
   DevBuf sn_pend, pn_off, pn_du, pn_arena;   // snapshot: documents left pending, their three-update batch for the merge
   DevBuf pq_off, pq_a, pq_b, pq_c, pq_s, pq_st;   // step2 of pending documents: their parts and state vectors, statuses
@@ -286,7 +308,7 @@ void ygm_close(ygm_ctx* c) {
   if (c->stream2) (void)hipStreamSynchronize(c->stream2);
   for (DevBuf* b : {&c->arena, &c->offs, &c->docs, &c->sv_arena, &c->sv_offs, &c->out, &c->out_off, &c->out_len, &c->status,
                     &c->lb, &c->meta, &c->fb_list, &c->defer_list, &c->defer2_list, &c->defer_w_list, &c->route_list, &c->s_readers, &c->s_order, &c->s_tmp, &c->s_ubase, &c->s_ulen, &c->s_cnt,
-                    &c->s_drec, &c->big_blk, &c->big_rec, &c->big_list, &c->big_scan, &c->big_up, &c->lens_off, &c->sv_tbl, &c->sv_tn, &c->sn_cnt, &c->sn_off, &c->sn_bs, &c->sn_ws, &c->sn_claim, &c->sn_pay,
+                    &c->s_drec, &c->big_blk, &c->big_rec, &c->big_list, &c->big_scan, &c->big_up, &c->lens_off, &c->sv_tbl, &c->sv_tn, &c->ask_ix, &c->ask_base, &c->ask_bs, &c->ask_pl, &c->ask_pn, &c->sn_cnt, &c->sn_off, &c->sn_bs, &c->sn_ws, &c->sn_claim, &c->sn_pay,
                     &c->sn_pend, &c->pn_off, &c->pn_du, &c->pn_arena,
                     &c->pq_off, &c->pq_a, &c->pq_b, &c->pq_c, &c->pq_s, &c->pq_st, &c->v2_len, &c->v2_st, &c->v2_bs, &c->v2_v1, &c->v2_L, &c->v2_out, &c->v2_off, &c->v2_olen, &c->v2_ost, &c->v2_fo, &c->v2_claim, &c->v2_pay, &c->v2_scr, &c->v21_cl})
     b->release();
@@ -564,21 +586,49 @@ int ygm_merge_v1_device_lens(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_
   return ygm_merge_v1_device_finish(c, out);
 }
 
+static uint64_t read_u64(ygm_ctx* c, hipStream_t s, const uint64_t* d_p, int& e);
+// the plan of a shared-state call: c->ask_ix (checked state id per ask) and c->ask_base (exclusive scan of the asks'
+// state lengths, the total at [n_asks])
+static int ask_plan(ygm_ctx* c, hipStream_t s, const uint64_t* d_doc_off, uint32_t n_docs, const uint32_t* d_ask_doc, uint32_t n_asks) {
+  const size_t nb = ((size_t)n_asks + 1 + 255) / 256 + 2;
+  if (!c->ask_ix.ensure(4ull * n_asks + 4) || !c->ask_base.ensure(8ull * n_asks + 16) || !c->ask_bs.ensure(8 * nb)) return YGM_ENOMEM;
+  return ygm_k_launch_ask_plan(d_doc_off, n_docs, d_ask_doc, n_asks, c->ask_ix.as<uint32_t>(), c->ask_base.as<uint64_t>(),
+                               c->ask_bs.as<uint64_t>(), s) ? YGM_EDEVICE : YGM_OK;
+}
+
+// gather (mode 1 only): the batch is n_asks asks over n_docs shared documents, ask a answered from document
+// d_ask_doc[a] with state vector a; results are indexed by ask, slots placed from the asks' scanned state lengths
 static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off,
                           const uint8_t* d_sv, uint64_t sv_bytes, const uint64_t* d_sv_off, uint32_t n_docs, void* stream,
-                          ygm_device_result* out, uint32_t extra_flags = 0) {
+                          ygm_device_result* out, uint32_t extra_flags = 0, bool gather = false, const uint32_t* d_ask_doc = nullptr,
+                          uint32_t n_asks = 0) {
   const uint32_t flags = c ? c->flags | extra_flags : 0;
-  if (!c || !out) return YGM_EINVAL;
+  if (!c || !out || (gather && mode != 1)) return YGM_EINVAL;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   (void)hipSetDevice(c->device);
+  int e = YGM_OK;
+  const uint32_t n_states = n_docs;
+  uint64_t vbytes = arena_bytes;   // gather: the virtual bytes V, the sum over asks of the ask's state length
+  if (gather) {
+    if ((e = ask_plan(c, s, d_doc_off, n_states, d_ask_doc, n_asks))) return e;
+    vbytes = read_u64(c, s, c->ask_base.as<uint64_t>() + n_asks, e);   // the one read that sizes the output region
+    if (e) return e;
+    n_docs = n_asks;
+  }
   // per-document slots (lean kernel), then the packed region of the exact kernel's deferred documents
-  const uint64_t slot_total = 2 * arena_bytes + 64ull * n_docs;
-  const uint64_t out_cap = slot_total + 2 * arena_bytes + 32ull * n_docs + 64;
-  int e = prep_outputs(c, n_docs, out_cap, s, true);
+  const uint64_t slot_total = 2 * vbytes + 64ull * n_docs;
+  const uint64_t out_cap = slot_total + 2 * vbytes + 32ull * n_docs + 64;
+  e = prep_outputs(c, n_docs, out_cap, s, true);
   if (e) return e;
   void* meta = c->meta_slot(2);
   if (mode == 1 && (!c->sv_tbl.ensure(ygm_k_sv_table_bytes(n_docs)) || !c->sv_tn.ensure(4ull * n_docs + 4))) return YGM_ENOMEM;
   HIPCHK(hipEventRecord(c->e0, s));
+  if (gather) {
+    if (ygm_k_launch_doc_lean_gather(d_arena, d_doc_off, d_sv, d_sv_off, c->ask_ix.as<uint32_t>(), c->ask_base.as<uint64_t>(), n_asks,
+                                     c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
+                                     meta, c->defer_list.as<uint32_t>(), out_cap, c->sv_tbl.as<uint8_t>(), c->sv_tn.as<uint32_t>(), s))
+      return YGM_EDEVICE;
+  } else
   if (ygm_k_launch_doc_lean(mode, d_arena, arena_bytes, d_doc_off, d_sv, sv_bytes, d_sv_off, n_docs, flags, c->out.as<uint8_t>(),
                             c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), meta,
                             c->defer_list.as<uint32_t>(), out_cap, c->sv_tbl.as<uint8_t>(), c->sv_tn.as<uint32_t>(), s))
@@ -591,6 +641,12 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
   if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) { c->stats.kernel_ms += ms; c->stats.lean_ms += ms; c->stats.lean_launches++; }
   if (m.lean_defer) {   // the exact per-document kernel over the deferred list, packed after the slots
     HIPCHK(hipEventRecord(c->e0, s));
+    if (gather) {
+      if (ygm_k_launch_doc_gather(d_arena, d_doc_off, d_sv, d_sv_off, c->defer_list.as<uint32_t>(), c->ask_ix.as<uint32_t>(), slot_total,
+                                  m.lean_defer, flags, c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
+                                  c->status.as<int32_t>(), c->lb.as<unsigned long long>(), meta, out_cap, s))
+        return YGM_EDEVICE;
+    } else
     if (ygm_k_launch_doc(mode, d_arena, d_doc_off, d_sv, d_sv_off, c->defer_list.as<uint32_t>(), slot_total, m.lean_defer, flags,
                          c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
                          c->lb.as<unsigned long long>(), meta, out_cap, s))
@@ -600,6 +656,9 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
     if (m.fault) return YGM_EDEVICE;
     if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
   }
+  // gather: an ask of a refused state id carries YGM_EINVAL (whatever the kernels left there)
+  if (gather && ygm_k_launch_ask_status(c->ask_ix.as<uint32_t>(), n_asks, nullptr, c->status.as<int32_t>(), c->out_len.as<uint64_t>(), s))
+    return YGM_EDEVICE;
   const uint64_t payload = m.payload_total() + m.fast_total;
   c->stats.calls++; c->stats.docs += n_docs; c->stats.docs_fast += m.lean_defer; c->stats.docs_lean += n_docs - m.lean_defer;
   c->stats.bytes_in += arena_bytes; c->stats.bytes_out += payload;
@@ -623,7 +682,8 @@ static uint64_t read_u64(ygm_ctx* c, hipStream_t s, const uint64_t* d_p, int& e)
   return v;
 }
 static int pend_merge_place(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t total, const int32_t* pst, DevBuf& dst, uint64_t used,
-                            uint64_t& data_bytes, unsigned long long& payload) {
+                            uint64_t& data_bytes, unsigned long long& payload, const uint32_t* list = nullptr) {
+  if (!list) list = c->sn_pend.as<uint32_t>();   // (the shared-state step2: its list of asks)
   if (!c->pend_ctx) { const int e = ygm_open(c->device, c->flags, &c->pend_ctx); if (e) return e; }
   int e = ygm_merge_v1_device_async(c->pend_ctx, c->pn_arena.as<uint8_t>(), total, c->pn_off.as<uint64_t>(), c->pn_du.as<uint32_t>(), 3 * P, P, s);
   ygm_device_result r;
@@ -631,7 +691,7 @@ static int pend_merge_place(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t tota
   if (e) return e;
   if (!dst.ensure(used + r.data_bytes + 64, used, s)) return YGM_ENOMEM;
   if (r.data_bytes) HIPCHK(hipMemcpyAsync(dst.as<uint8_t>() + used, r.data, r.data_bytes, hipMemcpyDeviceToDevice, s));
-  if (ygm_k_launch_pend_fix(c->sn_pend.as<uint32_t>(), P, r.off, r.len, r.status, pst, used, c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
+  if (ygm_k_launch_pend_fix(list, P, r.off, r.len, r.status, pst, used, c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
                             c->status.as<int32_t>(), s))
     return YGM_EDEVICE;
   data_bytes = used + r.data_bytes;
@@ -658,8 +718,9 @@ static int snap_resolve_pending(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t 
 // the snapshot batch; xf: YGM_F_SNAP_STATE (contains) for states that leave pending parts
 // leave: when non-null, documents left pending are not resolved: their count goes there (list c->sn_pend, statuses
 // ST_PEND, their PendHdr layouts at out_off)
+// dpw: k_snap's documents per wave (0: its default)
 static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off, uint32_t n_docs,
-                        hipStream_t s, ygm_device_result* out, uint32_t xf, uint32_t* leave = nullptr) {
+                        hipStream_t s, ygm_device_result* out, uint32_t xf, uint32_t* leave = nullptr, uint32_t dpw = 0) {
   if (leave) *leave = 0;
   const uint32_t fl = c->flags | xf;
   const uint32_t nb = (n_docs + 1 + 255) / 256;
@@ -700,10 +761,10 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
       memcpy(&total, c->h_meta, 8);
     }
     if (!c->sn_ws.ensure(slot_total + total + 64, slot_total, s) || !c->sn_pend.ensure(4ull * n_docs + 16)) return YGM_ENOMEM;
-    if (ygm_k_launch_snap(d_arena, d_doc_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_ws.as<uint8_t>(),
-                          c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                          (unsigned long long*)((uint8_t*)meta + offsetof(Meta, payload)), claim, slot_total, c->sn_pend.as<uint32_t>(),
-                          (unsigned int*)((uint8_t*)meta + offsetof(Meta, fb_count)), s))
+    if (ygm_k_launch_snap_w(d_arena, d_doc_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_ws.as<uint8_t>(),
+                            c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
+                            (unsigned long long*)((uint8_t*)meta + offsetof(Meta, payload)), claim, slot_total, c->sn_pend.as<uint32_t>(),
+                            (unsigned int*)((uint8_t*)meta + offsetof(Meta, fb_count)), dpw, s))
       return YGM_EDEVICE;
     int e = read_meta(c, s, m, meta);
     if (e) return e;
@@ -719,6 +780,7 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
   c->stats.calls++; c->stats.docs += n_docs; c->stats.bytes_in += arena_bytes; c->stats.bytes_out += m.payload;
+  c->stats.docs_snapshot += n_docs;
   out->data = c->sn_ws.as<uint8_t>(); out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
   out->status = c->status.as<int32_t>(); out->data_bytes = total_out ? total_out : slot_total + total; out->payload_bytes = m.payload;
   return YGM_OK;
@@ -838,7 +900,8 @@ static int step2_pending_split(ygm_ctx* c, hipStream_t s, uint32_t P, const uint
   return YGM_OK;
 }
 // finish (after the main diff): the two diffs, the join, the merge, the places in `out`
-static int step2_pending_finish(ygm_ctx* c, hipStream_t s, uint32_t P, const uint64_t (&tot)[4], ygm_device_result* out) {
+static int step2_pending_finish(ygm_ctx* c, hipStream_t s, uint32_t P, const uint64_t (&tot)[4], ygm_device_result* out,
+                                const uint32_t* list = nullptr) {
   const uint64_t np = (uint64_t)P + 1;
   uint64_t* offs = c->pq_off.as<uint64_t>();
   for (ygm_ctx*& k : c->pend_dx) if (!k) { const int e = ygm_open(c->device, c->flags, &k); if (e) return e; }
@@ -860,7 +923,7 @@ static int step2_pending_finish(ygm_ctx* c, hipStream_t s, uint32_t P, const uin
     return YGM_EDEVICE;
   uint64_t db = 0;
   unsigned long long pay = out->payload_bytes;
-  if ((e = pend_merge_place(c, s, P, total, c->pq_st.as<int32_t>(), c->out, out->data_bytes, db, pay))) return e;
+  if ((e = pend_merge_place(c, s, P, total, c->pq_st.as<int32_t>(), c->out, out->data_bytes, db, pay, list))) return e;
   out->data = c->out.as<uint8_t>(); out->data_bytes = db; out->payload_bytes = pay;
   return YGM_OK;
 }
@@ -895,6 +958,87 @@ int ygm_sync_step2_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t state
   S2CHK(hipStreamSynchronize(s));
   return YGM_OK;
 #undef S2CHK
+}
+
+// ------------------------------------------------------------------ shared states (device API)
+// diffUpdate of n_asks state vectors over n_docs shared updates: the gather walker and the gather exact kernel
+int ygm_diff_shared_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off, uint32_t n_docs,
+                              const uint8_t* d_sv_arena, const uint64_t* d_sv_off, const uint32_t* d_ask_doc, uint32_t n_asks, void* stream,
+                              ygm_device_result* out) {
+  if (!c || !out || (n_asks && (!d_sv_off || !d_ask_doc))) return YGM_EINVAL;
+  uint64_t sv_end = 0;
+  if (n_asks && hipMemcpy(&sv_end, d_sv_off + n_asks, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
+  return run_doc_kernel(c, 1, d_arena, arena_bytes, d_doc_off, d_sv_arena, sv_end, d_sv_off, n_docs, stream, out, 0, true, d_ask_doc, n_asks);
+}
+
+// SyncStep2 of a reconnect storm: the snapshot batch over the n_states states (each once), packed; the gather diff
+// with F_KEEP_SUB over the n_asks asks, reading the packed snapshots in place; each state's refusal carried to its
+// asks; the asks of states the snapshot left pending split off before the diff (their state's three parts copied per
+// ask, the state not snapshotted again) and finished after it at their ask indices
+int ygm_sync_step2_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
+                                    uint32_t n_states, const uint8_t* d_sv_arena, const uint64_t* d_sv_off, const uint32_t* d_ask_state,
+                                    uint32_t n_asks, void* stream, ygm_device_result* out) {
+  if (!c || !out || (n_asks && (!d_sv_off || !d_ask_state))) return YGM_EINVAL;
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  (void)hipSetDevice(c->device);
+  ygm_device_result r1;
+  uint32_t P = 0, PA = 0;   // states the snapshot leaves pending; their asks
+  uint64_t ptot[4] = {0, 0, 0, 0};
+  // k_snap runs 16 documents per wave and its lanes diverge by document.  The per-pair call over these asks would hold
+  // n_asks / n_states copies of a state on neighbouring lanes (no divergence between them): the same number of waves
+  // here, with fewer documents each (`parity`), is never more serial than that.  While the states fit one resident
+  // round of k_snap's waves with fewer per wave still (`fill`: 256 CUs x 3 workgroups of 40 KB of LDS), they take that:
+  // the shared batch is the smaller one, lanes are what it has to spare (profiles/step2_shared/README.md)
+  uint32_t dpw = 0;
+  if (n_asks > n_states) {
+    const uint32_t parity = std::max<uint32_t>(1u, (uint32_t)(16ull * n_states / n_asks));
+    const uint32_t fill = std::max<uint32_t>(1u, (n_states + 767u) / 768u);
+    dpw = std::min(parity, fill);
+  }
+  int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_states, s, &r1, 0, &P, dpw);
+  if (e) return e;
+  if (P && n_asks) {
+    if ((e = ask_plan(c, s, d_state_off, n_states, d_ask_state, n_asks))) return e;
+    if (!c->ask_pl.ensure(4ull * n_asks + 16) || !c->ask_pn.ensure(16)) return YGM_ENOMEM;
+    HIPCHK(hipMemsetAsync(c->ask_pn.p, 0, 16, s));
+    if (ygm_k_launch_ask_pending(c->ask_ix.as<uint32_t>(), n_asks, r1.status, c->ask_pl.as<uint32_t>(), c->ask_pn.as<unsigned int>(), s))
+      return YGM_EDEVICE;
+    PA = (uint32_t)read_u64(c, s, c->ask_pn.as<uint64_t>(), e);
+    if (e) return e;
+  }
+  if (PA) {   // as step2_pending_split, over the ask list
+    const uint64_t np = (uint64_t)PA + 1;
+    if (!c->pq_off.ensure(8ull * 4 * np + 16) || !c->pq_st.ensure(4ull * PA + 16) || !c->pn_off.ensure(8ull * (3ull * PA + 1) + 16) ||
+        !c->pn_du.ensure(4ull * np + 16))
+      return YGM_ENOMEM;
+    uint64_t* offs = c->pq_off.as<uint64_t>();
+    if (ygm_k_launch_pend_split_g(c->ask_pl.as<uint32_t>(), PA, c->ask_ix.as<uint32_t>(), c->sn_ws.as<uint8_t>(), r1.off, d_sv_arena, d_sv_off,
+                                  offs, nullptr, nullptr, nullptr, nullptr, 0, s))
+      return YGM_EDEVICE;
+    c->stats.host_syncs++;
+    for (int k = 0; k < 4; k++) HIPCHK(hipMemcpyAsync((uint64_t*)c->h_meta + k, offs + (uint64_t)k * np + PA, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(ptot, c->h_meta, sizeof ptot);
+    DevBuf* part[4] = {&c->pq_a, &c->pq_b, &c->pq_c, &c->pq_s};
+    for (int k = 0; k < 4; k++) {
+      if (!part[k]->ensure(ptot[k] + 64)) return YGM_ENOMEM;
+      HIPCHK(hipMemsetAsync(part[k]->as<uint8_t>() + ptot[k], 0, 64, s));
+    }
+    if (ygm_k_launch_pend_split_g(c->ask_pl.as<uint32_t>(), PA, c->ask_ix.as<uint32_t>(), c->sn_ws.as<uint8_t>(), r1.off, d_sv_arena, d_sv_off,
+                                  offs, c->pq_a.as<uint8_t>(), c->pq_b.as<uint8_t>(), c->pq_c.as<uint8_t>(), c->pq_s.as<uint8_t>(), 1, s))
+      return YGM_EDEVICE;
+  }
+  if ((e = pack_snapshots(c, s, r1, n_states))) return e;
+  uint64_t sv_end = 0;
+  if (n_asks && hipMemcpy(&sv_end, d_sv_off + n_asks, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
+  e = run_doc_kernel(c, 1, c->s2_data.as<uint8_t>(), r1.payload_bytes, c->s2_off.as<uint64_t>(), d_sv_arena, sv_end, d_sv_off, n_states, s,
+                     out, YGM_F_KEEP_SUB, true, d_ask_state, n_asks);
+  if (e) return e;
+  // the status carry from state to ask (the gather form of k_v2_status)
+  if (n_states && ygm_k_launch_ask_status(c->ask_ix.as<uint32_t>(), n_asks, c->s2_st.as<int32_t>(), out->status, out->len, s)) return YGM_EDEVICE;
+  if (PA && (e = step2_pending_finish(c, s, PA, ptot, out, c->ask_pl.as<uint32_t>()))) return e;
+  HIPCHK(hipStreamSynchronize(s));
+  return YGM_OK;
 }
 
 // ------------------------------------------------------------------ update V2 (device API)
@@ -1092,7 +1236,8 @@ struct Chunk {   // documents [d0, d1): merge updates [u0, u1) / SV-diff documen
 };
 struct HostCall {
   int mode;   // 0 sv, 1 diff, 2 merge, 3 snapshot, 4 contains (second arena in the sv slots); update V2: 5 merge, 6 diff,
-              // 7 sv, 8 V1 -> V2, 9 V2 -> V1; 10 sync step2 (states + state vectors)
+              // 7 sv, 8 V1 -> V2, 9 V2 -> V1; 10 sync step2 (states + state vectors); 11 / 12 the shared-state diff /
+              // step2 (host_shared_call: n_docs states, n_upd asks, upd_doc = the asks' states)
   const uint8_t* arena; const uint64_t* off; const uint32_t* upd_doc; const uint8_t* sv_arena; const uint64_t* sv_off;
   uint32_t n_upd, n_docs;
 };
@@ -1233,6 +1378,19 @@ static int chunk_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint64
   return YGM_OK;
 }
 
+// device work of a stage context since `b`, into the parent context's counters
+static void add_stage_stats(ygm_ctx* c, const ygm_stats_t& a, const ygm_stats_t& b) {
+  c->stats.calls += a.calls - b.calls; c->stats.docs += a.docs - b.docs; c->stats.updates += a.updates - b.updates;
+  c->stats.bytes_in += a.bytes_in - b.bytes_in; c->stats.bytes_out += a.bytes_out - b.bytes_out;
+  c->stats.docs_fast += a.docs_fast - b.docs_fast; c->stats.docs_seq += a.docs_seq - b.docs_seq;
+  c->stats.kernel_ms += a.kernel_ms - b.kernel_ms; c->stats.docs_lean += a.docs_lean - b.docs_lean;
+  c->stats.lean_ms += a.lean_ms - b.lean_ms; c->stats.lean_launches += a.lean_launches - b.lean_launches;
+  c->stats.docs_big += a.docs_big - b.docs_big; c->stats.docs_lean_wide += a.docs_lean_wide - b.docs_lean_wide;
+  c->stats.host_syncs += a.host_syncs - b.host_syncs;
+  c->stats.docs_pending += a.docs_pending - b.docs_pending;
+  c->stats.docs_snapshot += a.docs_snapshot - b.docs_snapshot;
+}
+
 static int host_call(ygm_ctx* c, const HostCall& H, ygm_result* out) {
   (void)hipSetDevice(c->device);
   const uint32_t n = H.n_docs;
@@ -1300,17 +1458,7 @@ static int host_call(ygm_ctx* c, const HostCall& H, ygm_result* out) {
       uint64_t* off = c->h_off.as<uint64_t>() + C.d0;
       for (uint32_t d = 0; d < C.d1 - C.d0; d++) off[d] += C.pos;
     }
-    for (int j = 0; j < (ch.size() > 1 ? 2 : 1); j++) {   // device work of the stages, into this context's counters
-      const ygm_stats_t& a = k[j]->stats; const ygm_stats_t& b = s0[j];
-      c->stats.calls += a.calls - b.calls; c->stats.docs += a.docs - b.docs; c->stats.updates += a.updates - b.updates;
-      c->stats.bytes_in += a.bytes_in - b.bytes_in; c->stats.bytes_out += a.bytes_out - b.bytes_out;
-      c->stats.docs_fast += a.docs_fast - b.docs_fast; c->stats.docs_seq += a.docs_seq - b.docs_seq;
-      c->stats.kernel_ms += a.kernel_ms - b.kernel_ms; c->stats.docs_lean += a.docs_lean - b.docs_lean;
-      c->stats.lean_ms += a.lean_ms - b.lean_ms; c->stats.lean_launches += a.lean_launches - b.lean_launches;
-      c->stats.docs_big += a.docs_big - b.docs_big; c->stats.docs_lean_wide += a.docs_lean_wide - b.docs_lean_wide;
-      c->stats.host_syncs += a.host_syncs - b.host_syncs;
-      c->stats.docs_pending += a.docs_pending - b.docs_pending;
-    }
+    for (int j = 0; j < (ch.size() > 1 ? 2 : 1); j++) add_stage_stats(c, k[j]->stats, s0[j]);
     int32_t* st = c->h_status.as<int32_t>();
     uint64_t* ln = c->h_len.as<uint64_t>();
     for (uint32_t d = 0; d < n; d++) {
@@ -1322,6 +1470,163 @@ static int host_call(ygm_ctx* c, const HostCall& H, ygm_result* out) {
   }
   for (Chunk& C : ch) for (hipEvent_t ev : {C.h0, C.h1, C.o0, C.o1}) if (ev) (void)hipEventDestroy(ev);
   return e;
+}
+
+// ---- shared states: n_docs states, n_asks asks (ask_doc non-decreasing).  A chunk is a range of states [u0, u1) with
+// its contiguous asks [d0, d1) (results and offsets are indexed by ask); its budget counts virtual bytes, the states'
+// bytes plus, over its asks, the ask's state length -- what bounds the slot region.  A state whose asks alone exceed
+// the budget is split: chunks of that one state, each staging (and, step2, snapshotting) it again.
+static void shared_chunks(const uint64_t* off, uint32_t n_docs, const uint32_t* ask_doc, uint32_t n_asks, uint64_t CB, std::vector<Chunk>& ch) {
+  uint32_t a = 0;   // the first ask not yet placed
+  Chunk C{};
+  uint64_t cur = 0;
+  bool open = false;
+  auto close = [&]() { if (open) { ch.push_back(C); open = false; cur = 0; } };
+  for (uint32_t sd = 0; sd < n_docs; sd++) {
+    const uint64_t L = off[sd + 1] - off[sd];
+    uint32_t a1 = a;
+    while (a1 < n_asks && ask_doc[a1] == sd) a1++;
+    const uint64_t v = L + (uint64_t)(a1 - a) * L;
+    if (open && cur + v > CB) close();
+    if (v <= CB || a1 - a <= 1) {
+      if (!open) { C = Chunk{}; C.u0 = sd; C.d0 = a; open = true; }
+      C.u1 = sd + 1; C.d1 = a1; cur += v;
+    } else {   // one state over several chunks
+      const uint64_t per = CB > L ? (CB - L) / L : 1;
+      const uint32_t m = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per, 1), a1 - a);
+      for (uint32_t x = a; x < a1; x += m) {
+        C = Chunk{}; C.u0 = sd; C.u1 = sd + 1; C.d0 = x; C.d1 = std::min(a1, x + m);
+        ch.push_back(C);
+      }
+    }
+    a = a1;
+  }
+  close();
+  if (ch.empty()) { C = Chunk{}; ch.push_back(C); }
+}
+static int shared_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
+  const uint32_t ns = C.u1 - C.u0, na = C.d1 - C.d0;
+  const uint64_t a0 = H.off[C.u0], bytes = H.off[C.u1] - a0, ab = (bytes + 64 + 15) & ~15ull;
+  const uint64_t s0 = H.sv_off[C.d0], svb = H.sv_off[C.d1] - s0, sb = (svb + 64 + 15) & ~15ull;
+  const uint64_t n_off = (uint64_t)ns + 1, n_sv = (uint64_t)na + 1;
+  if (!k->h_in.ensure(ab + 8 * n_off + sb + 8 * n_sv + 4ull * na + 64)) return YGM_ENOMEM;
+  uint8_t* P = k->h_in.as<uint8_t>();
+  if (bytes) par_memcpy(P, H.arena + a0, bytes);
+  memset(P + bytes, 0, ab - bytes);
+  uint64_t* ro = (uint64_t*)(P + ab);
+  for (uint64_t j = 0; j < n_off; j++) ro[j] = H.off[C.u0 + j] - a0;
+  uint8_t* q = P + ab + 8 * n_off;
+  if (svb) memcpy(q, H.sv_arena + s0, svb);
+  memset(q + svb, 0, sb - svb);
+  uint64_t* rs = (uint64_t*)(q + sb);
+  for (uint64_t j = 0; j < n_sv; j++) rs[j] = H.sv_off[C.d0 + j] - s0;
+  uint32_t* ra = (uint32_t*)(q + sb + 8 * n_sv);
+  for (uint32_t j = 0; j < na; j++) ra[j] = H.upd_doc[C.d0 + j] - C.u0;
+  if (!k->arena.ensure(ab) || !k->offs.ensure(8 * n_off) || !k->sv_arena.ensure(sb) || !k->sv_offs.ensure(8 * n_sv) ||
+      !k->docs.ensure(4ull * na + 4))
+    return YGM_ENOMEM;
+  HIPCHK(hipEventRecord(C.h0, k->stream));
+  HIPCHK(hipMemcpyAsync(k->arena.p, P, ab, hipMemcpyHostToDevice, k->stream));
+  HIPCHK(hipMemcpyAsync(k->offs.p, ro, 8 * n_off, hipMemcpyHostToDevice, k->stream));
+  HIPCHK(hipMemcpyAsync(k->sv_arena.p, q, sb, hipMemcpyHostToDevice, k->stream));
+  HIPCHK(hipMemcpyAsync(k->sv_offs.p, rs, 8 * n_sv, hipMemcpyHostToDevice, k->stream));
+  if (na) HIPCHK(hipMemcpyAsync(k->docs.p, ra, 4ull * na, hipMemcpyHostToDevice, k->stream));
+  HIPCHK(hipEventRecord(C.h1, k->stream));
+  return YGM_OK;
+}
+static int shared_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint64_t& pos) {
+  const uint32_t ns = C.u1 - C.u0, na = C.d1 - C.d0;
+  const uint64_t bytes = H.off[C.u1] - H.off[C.u0];
+  ygm_device_result dr;
+  int e;
+  if (H.mode == 12) e = ygm_sync_step2_shared_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), ns, k->sv_arena.as<uint8_t>(),
+                                                        k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
+  else e = ygm_diff_shared_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), ns, k->sv_arena.as<uint8_t>(),
+                                     k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
+  if (e) return e;
+  const uint32_t nb = (na + 255) / 256;
+  if (!k->pk_data.ensure(dr.payload_bytes + 64) || !k->pk_off.ensure(8ull * na + 8) || !k->pk_bsum.ensure(8ull * nb + 16)) return YGM_ENOMEM;
+  if (na && ygm_k_launch_pack(dr.data, dr.off, dr.len, dr.status, na, k->pk_bsum.as<uint64_t>(), k->pk_data.as<uint8_t>(),
+                              k->pk_off.as<uint64_t>(), k->stream))
+    return YGM_EDEVICE;
+  C.pos = pos; C.payload = dr.payload_bytes;
+  if (pos + dr.payload_bytes + 1 > c->h_data.cap) {   // regrowth moves the bytes copied so far: let those copies land first
+    for (ygm_ctx* x : c->kid) if (x) HIPCHK(hipStreamSynchronize(x->stream));
+    if (!c->h_data.ensure(pos + dr.payload_bytes + 1, pos)) return YGM_ENOMEM;
+  }
+  HIPCHK(hipEventRecord(C.o0, k->stream));
+  if (dr.payload_bytes) HIPCHK(hipMemcpyAsync(c->h_data.as<uint8_t>() + pos, k->pk_data.p, dr.payload_bytes, hipMemcpyDeviceToHost, k->stream));
+  if (na) {
+    HIPCHK(hipMemcpyAsync(c->h_off.as<uint64_t>() + C.d0, k->pk_off.p, 8ull * na, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(hipMemcpyAsync(c->h_len.as<uint64_t>() + C.d0, dr.len, 8ull * na, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(hipMemcpyAsync(c->h_status.as<int32_t>() + C.d0, dr.status, 4ull * na, hipMemcpyDeviceToHost, k->stream));
+  }
+  HIPCHK(hipEventRecord(C.o1, k->stream));
+  pos += dr.payload_bytes;
+  return YGM_OK;
+}
+static int host_shared_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, const uint8_t* sv_arena,
+                            const uint64_t* sv_off, const uint32_t* ask_doc, uint32_t n_asks, ygm_result* out) {
+  if (!c || !out || (n_docs && !doc_off) || (n_asks && (!sv_off || !ask_doc))) return YGM_EINVAL;
+  for (uint32_t d = 0; d < n_docs; d++) if (doc_off[d + 1] < doc_off[d]) return YGM_EINVAL;
+  for (uint32_t a = 0; a < n_asks; a++)
+    if (ask_doc[a] >= n_docs || (a && ask_doc[a] < ask_doc[a - 1]) || sv_off[a + 1] < sv_off[a]) return YGM_EINVAL;
+  if ((n_docs && doc_off[n_docs] > doc_off[0] && !arena) || (n_asks && sv_off[n_asks] > sv_off[0] && !sv_arena)) return YGM_EINVAL;
+  static const uint64_t zero_off[1] = {0};
+  HostCall H{mode, arena, n_docs ? doc_off : zero_off, ask_doc, sv_arena, n_asks ? sv_off : zero_off, n_asks, n_docs};
+  (void)hipSetDevice(c->device);
+  uint64_t in_bytes = n_docs ? doc_off[n_docs] - doc_off[0] : 0, vbytes = in_bytes;
+  for (uint32_t a = 0; a < n_asks; a++) vbytes += doc_off[ask_doc[a] + 1] - doc_off[ask_doc[a]];
+  std::vector<Chunk> ch;
+  shared_chunks(H.off, n_docs, ask_doc, n_asks, chunk_bytes(vbytes), ch);
+  const uint32_t n = n_asks;
+  if (!c->h_off.ensure(8ull * n + 8) || !c->h_len.ensure(8ull * n + 8) || !c->h_status.ensure(4ull * n + 4) ||
+      !c->h_data.ensure(std::min<uint64_t>(vbytes, 1ull << 30) + 16ull * n + 4096))
+    return YGM_ENOMEM;
+  int e = YGM_OK;
+  ygm_ctx* k[2];
+  if ((e = stage_ctx(c, 0, &k[0])) || (ch.size() > 1 && (e = stage_ctx(c, 1, &k[1])))) return e;
+  for (Chunk& C : ch)
+    if (hipEventCreate(&C.h0) != hipSuccess || hipEventCreate(&C.h1) != hipSuccess || hipEventCreate(&C.o0) != hipSuccess ||
+        hipEventCreate(&C.o1) != hipSuccess) { e = YGM_EDEVICE; break; }
+  const int nk = ch.size() > 1 ? 2 : 1;
+  ygm_stats_t s0[2] = {k[0]->stats, nk > 1 ? k[1]->stats : ygm_stats_t{}};
+  uint64_t pos = 0;
+  if (!e) e = shared_stage(k[0], H, ch[0]);
+  for (size_t i = 0; i < ch.size() && !e; i++) {
+    if (i + 1 < ch.size() && (e = shared_stage(k[(i + 1) & 1], H, ch[i + 1]))) break;
+    e = shared_run(c, k[i & 1], H, ch[i], pos);
+  }
+  for (int j = 0; j < nk; j++) if (hipStreamSynchronize(k[j]->stream) != hipSuccess && !e) e = YGM_EDEVICE;
+  if (!e) {
+    float ms = 0;
+    for (Chunk& C : ch) {
+      if (hipEventElapsedTime(&ms, C.h0, C.h1) == hipSuccess) c->stats.h2d_ms += ms;
+      if (hipEventElapsedTime(&ms, C.o0, C.o1) == hipSuccess) c->stats.d2h_ms += ms;
+      uint64_t* off = c->h_off.as<uint64_t>() + C.d0;
+      for (uint32_t d = 0; d < C.d1 - C.d0; d++) off[d] += C.pos;
+    }
+    for (int j = 0; j < nk; j++) add_stage_stats(c, k[j]->stats, s0[j]);
+    int32_t* st = c->h_status.as<int32_t>();
+    uint64_t* ln = c->h_len.as<uint64_t>();
+    for (uint32_t d = 0; d < n; d++) {
+      if (st[d] >= 100 || st[d] < 0) st[d] = YGM_EDEVICE;   // never leaves internal codes
+      if (st[d] != YGM_OK) ln[d] = 0;
+    }
+    out->data = c->h_data.as<uint8_t>(); out->off = c->h_off.as<uint64_t>(); out->len = ln; out->status = st;
+    out->n_docs = n; out->data_bytes = pos;
+  }
+  for (Chunk& C : ch) for (hipEvent_t ev : {C.h0, C.h1, C.o0, C.o1}) if (ev) (void)hipEventDestroy(ev);
+  return e;
+}
+
+int ygm_diff_shared_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, const uint8_t* sv_arena,
+                       const uint64_t* sv_off, const uint32_t* ask_doc, uint32_t n_asks, ygm_result* out) {
+  return host_shared_call(c, 11, arena, doc_off, n_docs, sv_arena, sv_off, ask_doc, n_asks, out);
+}
+int ygm_sync_step2_shared_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, uint32_t n_states, const uint8_t* sv_arena,
+                             const uint64_t* sv_off, const uint32_t* ask_state, uint32_t n_asks, ygm_result* out) {
+  return host_shared_call(c, 12, states, state_off, n_states, sv_arena, sv_off, ask_state, n_asks, out);
 }
 
 int ygm_merge_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* upd_doc, uint32_t n_upd, uint32_t n_docs,

@@ -79,14 +79,16 @@ YDEV uint64_t merge_place(const uint64_t* upd_off, const uint32_t* doc_upd, uint
   return slot_total + atomicAdd(&meta->cursor, (unsigned long long)size);
 }
 
-template <int MODE>  // 0 = sv, 1 = diff
-__global__ __launch_bounds__(DOC_NT) void k_doc(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
-                                                 const uint8_t* __restrict__ sv_arena, const uint64_t* __restrict__ sv_off,
-                                                 const uint32_t* __restrict__ docs, uint64_t out_base,
-                                                 uint32_t n_docs, uint32_t flags, uint8_t* __restrict__ out,
-                                                 uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
-                                                 int32_t* __restrict__ status, unsigned long long* lb, DocMeta* meta,
-                                                 uint64_t out_cap) {
+// GATHER (k_doc_gather: the asks the gather walker defers): document d is an ask; its bytes are those of state
+// ask_ix[d] (0xFFFFFFFF: an id the plan kernel refused -- ST_INVAL, nothing read), its state vector the ask's own
+template <int MODE, bool GATHER>  // 0 = sv, 1 = diff
+__device__ __forceinline__ void doc_exact(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+                                          const uint8_t* __restrict__ sv_arena, const uint64_t* __restrict__ sv_off,
+                                          const uint32_t* __restrict__ docs, uint64_t out_base,
+                                          uint32_t n_docs, uint32_t flags, uint8_t* __restrict__ out,
+                                          uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
+                                          int32_t* __restrict__ status, unsigned long long* lb, DocMeta* meta,
+                                          uint64_t out_cap, const uint32_t* __restrict__ ask_ix) {
   __shared__ uint32_t s_tile;
   __shared__ uint64_t s_tmp[DOC_NT / WAVE + 1];
   __shared__ uint64_t s_base;
@@ -99,15 +101,20 @@ __global__ __launch_bounds__(DOC_NT) void k_doc(const uint8_t* __restrict__ aren
   const uint32_t d = live ? (docs ? docs[di] : di) : 0u;
   const uint8_t* p = nullptr; uint32_t n = 0;
   const uint8_t* sv = nullptr; uint32_t svn = 0;
+  bool inval = false;
   if (live) {
-    const uint64_t a = doc_off[d], b = doc_off[d + 1];
-    p = arena + a; n = (uint32_t)(b - a);
-    if (MODE == 1) { const uint64_t sa = sv_off[d], sb = sv_off[d + 1]; sv = sv_arena + sa; svn = (uint32_t)(sb - sa); }
+    const uint32_t sd = GATHER ? ask_ix[d] : d;
+    inval = GATHER && sd == 0xFFFFFFFFu;
+    if (!inval) {
+      const uint64_t a = doc_off[sd], b = doc_off[sd + 1];
+      p = arena + a; n = (uint32_t)(b - a);
+      if (MODE == 1) { const uint64_t sa = sv_off[d], sb = sv_off[d + 1]; sv = sv_arena + sa; svn = (uint32_t)(sb - sa); }
+    }
   }
   uint32_t* blk = &s_blk[MODE == 1 ? threadIdx.x * DIFF_BLK : 0];
-  int st = ST_OK; uint64_t aux = 0;
+  int st = inval ? ST_INVAL : ST_OK; uint64_t aux = 0;
   Out o{nullptr, 0};
-  if (live) {
+  if (live && !inval) {
     if (MODE == 0) st = sv_doc(p, n, flags, o, aux, false);
     else st = diff_doc(p, n, sv, svn, flags, o, false, aux, blk, DIFF_BLK);
   }
@@ -132,6 +139,27 @@ __global__ __launch_bounds__(DOC_NT) void k_doc(const uint8_t* __restrict__ aren
   }
   if (meta->fault) st = ST_DEVICE;
   out_off[d] = at; out_len[d] = st == ST_OK ? mysz : 0; status[d] = st;
+}
+template <int MODE>
+__global__ __launch_bounds__(DOC_NT) void k_doc(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+                                                 const uint8_t* __restrict__ sv_arena, const uint64_t* __restrict__ sv_off,
+                                                 const uint32_t* __restrict__ docs, uint64_t out_base,
+                                                 uint32_t n_docs, uint32_t flags, uint8_t* __restrict__ out,
+                                                 uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
+                                                 int32_t* __restrict__ status, unsigned long long* lb, DocMeta* meta,
+                                                 uint64_t out_cap) {
+  doc_exact<MODE, false>(arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out, out_off, out_len, status, lb, meta, out_cap,
+                         nullptr);
+}
+__global__ __launch_bounds__(DOC_NT) void k_doc_gather(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+                                                        const uint8_t* __restrict__ sv_arena, const uint64_t* __restrict__ sv_off,
+                                                        const uint32_t* __restrict__ docs, uint64_t out_base,
+                                                        uint32_t n_docs, uint32_t flags, uint8_t* __restrict__ out,
+                                                        uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
+                                                        int32_t* __restrict__ status, unsigned long long* lb, DocMeta* meta,
+                                                        uint64_t out_cap, const uint32_t* __restrict__ ask_ix) {
+  doc_exact<1, true>(arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out, out_off, out_len, status, lb, meta, out_cap,
+                     ask_ix);
 }
 
 
@@ -3536,6 +3564,17 @@ int ygm_k_launch_doc(int mode, const uint8_t* arena, const uint64_t* doc_off, co
     hipLaunchKernelGGL(k_doc<0>, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out, out_off, out_len, status, lb, (DocMeta*)meta, out_cap);
   else
     hipLaunchKernelGGL(k_doc<1>, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out, out_off, out_len, status, lb, (DocMeta*)meta, out_cap);
+  return launch_rc(__func__);
+}
+
+int ygm_k_launch_doc_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
+                            const uint32_t* docs, const uint32_t* ask_ix, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out,
+                            uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap,
+                            hipStream_t s) {
+  const uint32_t tiles = (n_docs + DOC_NT - 1) / DOC_NT;
+  if (tiles == 0) return 0;
+  hipLaunchKernelGGL(k_doc_gather, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out,
+                     out_off, out_len, status, lb, (DocMeta*)meta, out_cap, ask_ix);
   return launch_rc(__func__);
 }
 

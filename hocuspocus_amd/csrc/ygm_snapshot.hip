@@ -255,6 +255,61 @@ __global__ __launch_bounds__(256) void k_pend_split_copy(const uint32_t* __restr
   const uint64_t a = offs[3ull * (P + 1) + j], n = offs[3ull * (P + 1) + j + 1] - a, s0 = sv_off[d];
   for (uint64_t i = threadIdx.x; i < n; i += 256) dsv[a + i] = sv[s0 + i];
 }
+// ---- the same split for asks that share states (ygm_sync_step2_shared_v1): `list` holds asks; ask a's parts come from
+// the workspace record of its state ask_ix[a], its state vector from the ask.  The parts of a pending state are copied
+// once per ask (such states are rare: lost updates); the state is not snapshotted again.
+// the asks whose state the snapshot left pending (one atomic per such ask: rare; every use of the list is per entry)
+__global__ __launch_bounds__(256) void k_ask_pending(const uint32_t* __restrict__ ask_ix, uint32_t n_asks, const int32_t* __restrict__ st_state,
+                                                     uint32_t* __restrict__ list, unsigned int* __restrict__ n_out) {
+  const uint32_t a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= n_asks) return;
+  const uint32_t sd = ask_ix[a];
+  if (sd != 0xFFFFFFFFu && st_state[sd] == snap::ST_PEND) list[atomicAdd(n_out, 1u)] = a;
+}
+__global__ __launch_bounds__(1024) void k_pend_split_plan_g(const uint32_t* __restrict__ list, uint32_t P, const uint32_t* __restrict__ ask_ix,
+                                                            const uint8_t* __restrict__ ws, const uint64_t* __restrict__ out_off,
+                                                            const uint64_t* __restrict__ sv_off, uint64_t* __restrict__ offs) {
+  __shared__ uint64_t tmp[1024 / WAVE + 1];
+  __shared__ uint64_t carry[4];
+  if (threadIdx.x < 4) carry[threadIdx.x] = 0;
+  __syncthreads();
+  for (uint32_t j0 = 0; j0 < P; j0 += 1024) {
+    const uint32_t j = j0 + threadIdx.x;
+    uint64_t l[4] = {0, 0, 0, 0};
+    if (j < P) {
+      const uint32_t a = list[j];
+      const uint8_t* h = ws + out_off[ask_ix[a]];
+      l[0] = pend_len(h, 0); l[1] = pend_len(h, 1); l[2] = pend_len(h, 2); l[3] = sv_off[a + 1] > sv_off[a] ? sv_off[a + 1] - sv_off[a] : 0ull;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      uint64_t tot;
+      const uint64_t pre = block_exscan<1024>(l[k], tmp, tot);
+      if (j < P) offs[(uint64_t)k * (P + 1) + j] = carry[k] + pre;
+      __syncthreads();
+      if (threadIdx.x == 0) carry[k] += tot;
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x < 4) offs[(uint64_t)threadIdx.x * (P + 1) + P] = carry[threadIdx.x];
+}
+__global__ __launch_bounds__(256) void k_pend_split_copy_g(const uint32_t* __restrict__ list, uint32_t P, const uint32_t* __restrict__ ask_ix,
+                                                           const uint8_t* __restrict__ ws, const uint64_t* __restrict__ out_off,
+                                                           const uint8_t* __restrict__ sv, const uint64_t* __restrict__ sv_off,
+                                                           const uint64_t* __restrict__ offs, uint8_t* __restrict__ da,
+                                                           uint8_t* __restrict__ db, uint8_t* __restrict__ dc, uint8_t* __restrict__ dsv) {
+  const uint32_t j = blockIdx.x, a = list[j];
+  const uint8_t* src = ws + out_off[ask_ix[a]] + sizeof(snap::PendHdr);
+  uint8_t* const dst[3] = {da, db, dc};
+#pragma unroll
+  for (uint32_t k = 0; k < 3; k++) {
+    const uint64_t o = offs[(uint64_t)k * (P + 1) + j], n = offs[(uint64_t)k * (P + 1) + j + 1] - o;
+    for (uint64_t i = threadIdx.x; i < n; i += 256) dst[k][o + i] = src[i];
+    src += n;
+  }
+  const uint64_t o = offs[3ull * (P + 1) + j], n = offs[3ull * (P + 1) + j + 1] - o, s0 = sv_off[a];
+  for (uint64_t i = threadIdx.x; i < n; i += 256) dsv[o + i] = sv[s0 + i];
+}
 __global__ __launch_bounds__(1024) void k_pend_join_plan(uint32_t P, const uint64_t* __restrict__ a_len, const int32_t* __restrict__ a_st,
                                                          const uint64_t* __restrict__ offs, const uint64_t* __restrict__ c_len,
                                                          const int32_t* __restrict__ c_st, uint64_t* __restrict__ upd_off,
@@ -448,17 +503,23 @@ int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s) {
   return snap_rc(__func__);
 }
 // phase 2: the snapshots (ws sized from ws_off[n_docs])
-int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
-                      uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
-                      uint64_t base, uint32_t* pend_list, unsigned int* pend_n, hipStream_t s) {
+// dpw_hint: documents per wave when YGM_SNAP_DPW is not set (0: the default 16)
+int ygm_k_launch_snap_w(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
+                        uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
+                        uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, hipStream_t s) {
   if (n_docs == 0) return 0;
   const char* env = getenv("YGM_SNAP_DPW");
-  uint32_t dpw = env ? (uint32_t)atoi(env) : 16u;
+  uint32_t dpw = env ? (uint32_t)atoi(env) : (dpw_hint ? dpw_hint : 16u);
   if (dpw < 1 || dpw > (uint32_t)SN_NT) dpw = 16u;
   const uint32_t g = (n_docs + dpw - 1) / dpw;
   hipLaunchKernelGGL(k_snap, dim3(g), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, (const uint4*)cnt, ws_off, ws, out_off, out_len,
                      status, payload, dpw, claim, base, pend_list, pend_n);
   return snap_rc(__func__);
+}
+int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
+                      uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
+                      uint64_t base, uint32_t* pend_list, unsigned int* pend_n, hipStream_t s) {
+  return ygm_k_launch_snap_w(arena, doc_off, n_docs, flags, cnt, ws_off, ws, out_off, out_len, status, payload, claim, base, pend_list, pend_n, 0u, s);
 }
 int ygm_k_launch_pend_plan(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, uint64_t* upd_off, uint32_t* doc_upd,
                            hipStream_t s) {
@@ -483,6 +544,21 @@ int ygm_k_launch_pend_split(const uint32_t* list, uint32_t P, const uint8_t* ws,
   if (P == 0) return 0;
   if (pass == 0) hipLaunchKernelGGL(k_pend_split_plan, dim3(1), dim3(1024), 0, s, list, P, ws, out_off, sv_off, offs);
   else hipLaunchKernelGGL(k_pend_split_copy, dim3(P), dim3(256), 0, s, list, P, ws, out_off, sv, sv_off, (const uint64_t*)offs, da, db, dc, dsv);
+  return snap_rc(__func__);
+}
+int ygm_k_launch_ask_pending(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, uint32_t* list, unsigned int* n_out,
+                             hipStream_t s) {
+  if (n_asks == 0) return 0;
+  hipLaunchKernelGGL(k_ask_pending, dim3((n_asks + 255) / 256), dim3(256), 0, s, ask_ix, n_asks, st_state, list, n_out);
+  return snap_rc(__func__);
+}
+int ygm_k_launch_pend_split_g(const uint32_t* list, uint32_t P, const uint32_t* ask_ix, const uint8_t* ws, const uint64_t* out_off,
+                              const uint8_t* sv, const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc,
+                              uint8_t* dsv, int pass, hipStream_t s) {
+  if (P == 0) return 0;
+  if (pass == 0) hipLaunchKernelGGL(k_pend_split_plan_g, dim3(1), dim3(1024), 0, s, list, P, ask_ix, ws, out_off, sv_off, offs);
+  else hipLaunchKernelGGL(k_pend_split_copy_g, dim3(P), dim3(256), 0, s, list, P, ask_ix, ws, out_off, sv, sv_off, (const uint64_t*)offs, da,
+                          db, dc, dsv);
   return snap_rc(__func__);
 }
 int ygm_k_launch_pend_join(uint32_t P, const uint8_t* ad, const uint64_t* a_off, const uint64_t* a_len, const int32_t* a_st, const uint8_t* bd,

@@ -120,12 +120,21 @@ __global__ __launch_bounds__(WAVE) void k_sv_table(const uint8_t* __restrict__ s
 #ifndef YGM_DW_WPE1
 #define YGM_DW_WPE1 2   // ... the diff walker
 #endif
-template <int MODE>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(MODE == 0 ? YGM_DW_WPE0 : YGM_DW_WPE1))) void k_doc_walk(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
-                                                  const uint8_t* __restrict__ tbl, const uint32_t* __restrict__ tbl_n,
-                                                  uint32_t n_docs, uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
-                                                  uint64_t* __restrict__ out_len, int32_t* __restrict__ status, DocMeta* meta,
-                                                  uint32_t* __restrict__ defer_list, uint64_t out_cap) {
+// GATHER (diff over shared states, k_doc_walk_gather): a lane's work item is an ask a of n_docs asks.  It streams state
+// ask_ix[a] (doc_off / arena; DW_ASK_BAD: an id the plan kernel refused, never used as an index -- the ask is deferred
+// and the exact kernel gives it ST_INVAL), takes its state-vector table at tbl + 144 a and writes into
+// merge_slot(ask_base[a], a): ask_base is the exclusive scan, over asks, of each ask's state length (n_docs + 1
+// entries), so the slots stay disjoint by the slot arithmetic and ask_base[a + 1] - ask_base[a] is the size the batch
+// sort, the prefetch and the take step use.  The body is shared and inlined: the non-gather kernels keep their
+// signatures and their code.
+constexpr uint32_t DW_ASK_BAD = 0xFFFFFFFFu;
+template <int MODE, bool GATHER>
+__device__ __forceinline__ void dw_walk(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+                                        const uint8_t* __restrict__ tbl, const uint32_t* __restrict__ tbl_n,
+                                        uint32_t n_docs, uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
+                                        uint64_t* __restrict__ out_len, int32_t* __restrict__ status, DocMeta* meta,
+                                        uint32_t* __restrict__ defer_list, uint64_t out_cap,
+                                        const uint32_t* __restrict__ ask_ix, const uint64_t* __restrict__ ask_base) {
   __shared__ DWLds L;
   uint32_t* ordk = L.ordk;
   const uint32_t l = threadIdx.x;
@@ -136,12 +145,21 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(MODE == 0 
   // offsets of the next 64 documents of the batch (lane i: entry next + i), loaded one round ahead
   uint32_t pd = 0, ptn = 0;
   uint64_t pa = 0, pb = 0;
+  uint64_t pbase = 0;                      // GATHER: the ask's slot base (ask_base[pd])
   auto prefetch = [&]() {
     pa = 0; pb = 0; ptn = 0; pd = 0;
+    if (GATHER) pbase = 0;
     if (next + l < bn) {
       pd = bbase + (ordk[next + l] & 0xFFu);
-      pa = doc_off[pd]; pb = doc_off[pd + 1];
-      if (MODE == 1) ptn = tbl_n[pd];
+      if (GATHER) {
+        const uint32_t sd = ask_ix[pd];
+        pbase = ask_base[pd];
+        if (sd != DW_ASK_BAD) { pa = doc_off[sd]; pb = doc_off[sd + 1]; ptn = tbl_n[pd]; }
+        else ptn = DW_TBL_BAD;
+      } else {
+        pa = doc_off[pd]; pb = doc_off[pd + 1];
+        if (MODE == 1) ptn = tbl_n[pd];
+      }
     }
   };
 
@@ -352,7 +370,8 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(MODE == 0 
       bbase = bnext; bn = (rem + nbat - 1u) / nbat; bnext = bbase + bn; next = 0;
       for (uint32_t e = l; e < (uint32_t)DW_BATCH; e += WAVE) {
         // key bytes + 1 (padding entries past bn: 0, sorted behind every document)
-        const uint64_t sz = e < bn ? doc_off[bbase + e + 1] - doc_off[bbase + e] + 1ull : 0ull;
+        const uint64_t* szo = GATHER ? ask_base : doc_off;
+        const uint64_t sz = e < bn ? szo[bbase + e + 1] - szo[bbase + e] + 1ull : 0ull;
         ordk[e] = ((uint32_t)(sz < 0xFFFFFFull ? sz : 0xFFFFFFull) << 8) | e;
       }
       __syncthreads();
@@ -420,6 +439,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(MODE == 0 
     const uint64_t na = dw_shfl64(pa, rank), nb = dw_shfl64(pb, rank);
     const uint32_t nd = (uint32_t)__shfl((int)pd, (int)rank);
     const uint32_t ntn = MODE == 1 ? (uint32_t)__shfl((int)ptn, (int)rank) : 0u;
+    const uint64_t nbase = GATHER ? dw_shfl64(pbase, rank) : 0ull;
     const uint32_t avail = bn - next;
     const bool got = want && rank < avail;
     const uint32_t npop = (uint32_t)__popcll(wm);
@@ -451,7 +471,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(MODE == 0 
     if (got) {
       d = nd; bad = 0; da = na; db = nb; count = 0; emitted = false; have_prev = false; nsv = 0;
       oa0 = 0; oa1 = 0; oq = 16u; of = 0;
-      slot = merge_slot(da, d);
+      slot = merge_slot(GATHER ? nbase : da, d);
       ob = out + slot;
       const uint64_t cap = merge_slot_cap(db - da), room = out_cap > slot ? out_cap - slot : 0ull;
       const uint64_t lim = cap < room ? cap : room;
@@ -812,6 +832,51 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(MODE == 0 
 #undef WDG
 }
 
+template <int MODE>
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(MODE == 0 ? YGM_DW_WPE0 : YGM_DW_WPE1))) void k_doc_walk(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+                                                  const uint8_t* __restrict__ tbl, const uint32_t* __restrict__ tbl_n,
+                                                  uint32_t n_docs, uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
+                                                  uint64_t* __restrict__ out_len, int32_t* __restrict__ status, DocMeta* meta,
+                                                  uint32_t* __restrict__ defer_list, uint64_t out_cap) {
+  dw_walk<MODE, false>(arena, doc_off, tbl, tbl_n, n_docs, out, out_off, out_len, status, meta, defer_list, out_cap, nullptr, nullptr);
+}
+// the diff walker over asks that share states (see dw_walk): n_asks work items
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(YGM_DW_WPE1))) void k_doc_walk_gather(
+    const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, const uint8_t* __restrict__ tbl,
+    const uint32_t* __restrict__ tbl_n, uint32_t n_asks, uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
+    uint64_t* __restrict__ out_len, int32_t* __restrict__ status, DocMeta* meta, uint32_t* __restrict__ defer_list, uint64_t out_cap,
+    const uint32_t* __restrict__ ask_ix, const uint64_t* __restrict__ ask_base) {
+  dw_walk<1, true>(arena, doc_off, tbl, tbl_n, n_asks, out, out_off, out_len, status, meta, defer_list, out_cap, ask_ix, ask_base);
+}
+
+// ---- the plan of a shared-state diff: per ask the checked state id and the state's length; ygm_k_launch_ask_plan
+// scans the lengths in place into ask_base (n_asks + 1 entries, the total at [n_asks]).  An id at or past n_docs,
+// or below its predecessor (the contract is non-decreasing), is refused: DW_ASK_BAD, length 0.
+__global__ __launch_bounds__(256) void k_ask_plan(const uint64_t* __restrict__ doc_off, uint32_t n_docs, const uint32_t* __restrict__ ask_doc,
+                                                  uint32_t n_asks, uint32_t* __restrict__ ask_ix, uint64_t* __restrict__ ask_base) {
+  const uint32_t a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= n_asks) return;
+  const uint32_t sd = ask_doc[a];
+  bool ok = sd < n_docs && (a == 0 || ask_doc[a - 1] <= sd);
+  uint64_t len = 0;
+  if (ok) {
+    const uint64_t x = doc_off[sd], y = doc_off[sd + 1];
+    len = y > x ? y - x : 0ull;
+  }
+  ask_ix[a] = ok ? sd : DW_ASK_BAD;
+  ask_base[a] = len;
+}
+// after the diff kernels: an ask of a refused id carries ST_INVAL; with st_state (step2: the snapshot statuses of the
+// states) a state's refusal is the status of each of its asks
+__global__ __launch_bounds__(256) void k_ask_status(const uint32_t* __restrict__ ask_ix, uint32_t n_asks, const int32_t* __restrict__ st_state,
+                                                    int32_t* __restrict__ status, uint64_t* __restrict__ len) {
+  const uint32_t a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= n_asks) return;
+  const uint32_t sd = ask_ix[a];
+  const int32_t st = sd == DW_ASK_BAD ? (int32_t)ST_INVAL : (st_state ? st_state[sd] : (int32_t)ST_OK);
+  if (st != ST_OK) { status[a] = st; len[a] = 0; }
+}
+
 }  // namespace ygm
 
 extern "C" {
@@ -828,6 +893,34 @@ int ygm_walk_diag_read(unsigned long long* out, int reset) {
   return 0;
 }
 #endif
+
+int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s);
+// ask_ix[n_asks], ask_base[n_asks + 1] (bs: scan scratch of (n_asks + 1 + 255) / 256 + 1 entries)
+int ygm_k_launch_ask_plan(const uint64_t* doc_off, uint32_t n_docs, const uint32_t* ask_doc, uint32_t n_asks, uint32_t* ask_ix,
+                          uint64_t* ask_base, uint64_t* bs, hipStream_t s) {
+  if (n_asks == 0) return hipMemsetAsync(ask_base, 0, 8, s) != hipSuccess;
+  hipLaunchKernelGGL(k_ask_plan, dim3((n_asks + 255) / 256), dim3(256), 0, s, doc_off, n_docs, ask_doc, n_asks, ask_ix, ask_base);
+  if (launch_rc(__func__)) return 1;
+  return ygm_k_launch_scan(ask_base, n_asks, bs, s);
+}
+int ygm_k_launch_ask_status(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, int32_t* status, uint64_t* len, hipStream_t s) {
+  if (n_asks == 0) return 0;
+  hipLaunchKernelGGL(k_ask_status, dim3((n_asks + 255) / 256), dim3(256), 0, s, ask_ix, n_asks, st_state, status, len);
+  return launch_rc(__func__);
+}
+// the gather walker over n_asks asks (state-vector tables per ask: k_sv_table needs no change)
+int ygm_k_launch_doc_lean_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
+                                 const uint32_t* ask_ix, const uint64_t* ask_base, uint32_t n_asks, uint8_t* out, uint64_t* out_off,
+                                 uint64_t* out_len, int32_t* status, void* meta, uint32_t* defer_list, uint64_t out_cap, uint8_t* tbl,
+                                 uint32_t* tbl_n, hipStream_t s) {
+  if (n_asks == 0) return 0;
+  const uint32_t waves = (n_asks + WAVE - 1) / WAVE, cap = device_cus() * 4u * YGM_DW_WPE1;
+  const uint32_t grid = waves < cap ? waves : cap;
+  hipLaunchKernelGGL(k_sv_table, dim3(waves), dim3(WAVE), 0, s, sv_arena, sv_off, n_asks, tbl, tbl_n);
+  hipLaunchKernelGGL(k_doc_walk_gather, dim3(grid), dim3(WAVE), 0, s, arena, doc_off, (const uint8_t*)tbl, (const uint32_t*)tbl_n, n_asks,
+                     out, out_off, out_len, status, (DocMeta*)meta, defer_list, out_cap, ask_ix, ask_base);
+  return launch_rc(__func__);
+}
 
 size_t ygm_k_sv_table_bytes(uint32_t n_docs) { return 144ull * n_docs + 64; }
 int ygm_k_launch_doc_lean(int mode, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* doc_off, const uint8_t* sv_arena,

@@ -57,7 +57,7 @@ class Stats(ctypes.Structure):
                 ("docs_lean", ctypes.c_uint64), ("lean_ms", ctypes.c_double),
                 ("lean_launches", ctypes.c_uint64), ("docs_big", ctypes.c_uint64),
                 ("docs_lean_wide", ctypes.c_uint64), ("host_syncs", ctypes.c_uint64),
-                ("docs_pending", ctypes.c_uint64)]
+                ("docs_pending", ctypes.c_uint64), ("docs_snapshot", ctypes.c_uint64)]
 
 
 _lib = None
@@ -70,7 +70,9 @@ EXPORTS = ("ygm_open", "ygm_close", "ygm_merge_v1", "ygm_diff_v1", "ygm_sv_from_
            "ygm_merge_v2", "ygm_diff_v2", "ygm_sv_from_update_v2", "ygm_convert_v1_to_v2", "ygm_convert_v2_to_v1",
            "ygm_merge_v2_device", "ygm_diff_v2_device", "ygm_sv_from_update_v2_device", "ygm_convert_v1_to_v2_device",
            "ygm_convert_v2_to_v1_device", "ygm_sync_step2_v1", "ygm_sync_step2_v1_device",
-           "ygm_merge_v1_device_lens", "ygm_merge_v1_device_lens_async")
+           "ygm_merge_v1_device_lens", "ygm_merge_v1_device_lens_async",
+           "ygm_diff_shared_v1", "ygm_sync_step2_shared_v1", "ygm_diff_shared_v1_device",
+           "ygm_sync_step2_shared_v1_device")
 
 
 def lib():
@@ -107,6 +109,12 @@ def lib():
         L.ygm_contains_v1_device.argtypes = [vp, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
         L.ygm_sync_step2_v1.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
         L.ygm_sync_step2_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
+        for f in ("ygm_diff_shared_v1", "ygm_sync_step2_shared_v1"):
+            getattr(L, f).argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, ctypes.POINTER(_Result)]
+            getattr(L, f).restype = i32
+        for f in ("ygm_diff_shared_v1_device", "ygm_sync_step2_shared_v1_device"):
+            getattr(L, f).argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
+            getattr(L, f).restype = i32
         L.ygm_merge_v2.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
         L.ygm_diff_v2.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
         for f in ("ygm_sv_from_update_v2", "ygm_convert_v1_to_v2", "ygm_convert_v2_to_v1"):
@@ -388,6 +396,32 @@ class Engine:
         if st != OK:
             raise YjsError(st)
         return self._unpack(res)
+
+    def _shared(self, fn, states, ask_state, svs):
+        if len(ask_state) != len(svs):
+            raise ValueError("one state index per state vector")
+        sa, so = _pack([bytes(s) for s in states])
+        va, vo = _pack([bytes(v) for v in svs])
+        ask = np.ascontiguousarray(np.asarray(ask_state, dtype=np.int64).astype(np.uint32))
+        res = _Result()
+        st = getattr(lib(), fn)(self._ctx, sa or None, _ptr(so), len(states), va or None, _ptr(vo),
+                                _ptr(ask) if len(ask) else None, len(ask), ctypes.byref(res))
+        if st != OK:
+            raise YjsError(st)
+        return self._unpack(res)
+
+    def diff_update_shared_batch(self, updates, ask_doc, svs):
+        """Y.diffUpdate(updates[ask_doc[a]], svs[a]) per ask a (ygm_diff_shared_v1): many state vectors answered from
+        one update, which is uploaded once and read in place.  ask_doc is non-decreasing, each entry below
+        len(updates); anything else raises YjsError(EINVAL).  -> list of (status, bytes | None) per ask."""
+        return self._shared("ygm_diff_shared_v1", updates, ask_doc, svs)
+
+    def sync_step2_shared_batch(self, states, ask_state, svs):
+        """SyncStep2 payloads of a reconnect storm (ygm_sync_step2_shared_v1): ask a is answered from
+        states[ask_state[a]] with svs[a], byte for byte what sync_step2_batch gives for that pair, but every state
+        is uploaded and snapshotted once however many asks name it.  ask_state as ask_doc in
+        diff_update_shared_batch.  -> list of (status, bytes | None) per ask."""
+        return self._shared("ygm_sync_step2_shared_v1", states, ask_state, svs)
 
     def contains_batch(self, states, updates):
         """Read-only SyncStep2: Y.snapshotContainsUpdate(Y.snapshot(doc), update) per pair, `states` being the

@@ -97,6 +97,9 @@ typedef struct {
                                           large-document and sequential tiers */
   uint64_t docs_pending;               /* snapshots of updates that leave pending structs / a pending delete set
                                           (finished by merging [state, pendingDs, pending structs] on the GPU) */
+  uint64_t docs_snapshot;              /* documents the snapshot kernels were run on (ygm_snapshot_v1, and the snapshots
+                                          inside ygm_contains_v1 / ygm_sync_step2_v1 / the shared-state forms: there one
+                                          per state and chunk, not one per ask) */
 } ygm_stats_t;
 
 /* Opens the engine on HIP device `device` (one context per GPU; contexts are
@@ -147,6 +150,29 @@ int ygm_contains_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_o
  * carries YGM_EUNSUPPORTED (the caller names it and keeps its yjs path). */
 int ygm_sync_step2_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *sv_arena,
                       const uint64_t *sv_off, uint32_t n_docs, ygm_result *out);
+
+/* ---- shared-state forms: many state vectors answered from one state ---------
+ * A reconnect storm sends many SyncStep1 messages for one document.  These forms take n_docs states and n_asks
+ * state vectors; ask_doc[a] (ask_state[a]) names the state that ask a is answered from.  The result has one entry
+ * per ask, in ask order (out->n_docs == n_asks), each byte-identical to what ygm_diff_v1 / ygm_sync_step2_v1 return
+ * for the pair (state[ask_doc[a]], sv[a]); each state is uploaded once, snapshotted once (step2), and read by the
+ * diff kernels in place.
+ *   doc_off / state_off   n_docs + 1 offsets of one update per state
+ *   sv_off                n_asks + 1 offsets of one encoded state vector per ask
+ *   ask_doc / ask_state   n_asks state ids, non-decreasing (the convention of upd_doc in ygm_merge_v1), each
+ *                         below n_docs; a state may have no ask
+ * An unordered or out-of-range id gives YGM_EINVAL before any device work.  A state's refusal (YGM_EUNSUPPORTED,
+ * YGM_EMALFORMED, ...) is the status of each of its asks; a bad state vector fails only its own ask.
+ * Chunks are ranges of states together with their asks, cut by virtual bytes (a chunk's state bytes plus, over its
+ * asks, the ask's state length: what bounds the output slots).  One state whose asks alone exceed the chunk budget
+ * is split over several chunks, and each of those chunks stages and snapshots that state again: a split state costs
+ * one snapshot per chunk, not per ask. */
+int ygm_diff_shared_v1(ygm_ctx *ctx, const uint8_t *arena, const uint64_t *doc_off, uint32_t n_docs,
+                       const uint8_t *sv_arena, const uint64_t *sv_off, const uint32_t *ask_doc, uint32_t n_asks,
+                       ygm_result *out);
+int ygm_sync_step2_shared_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, uint32_t n_states,
+                             const uint8_t *sv_arena, const uint64_t *sv_off, const uint32_t *ask_state, uint32_t n_asks,
+                             ygm_result *out);
 
 /* ---- update format V2 ------------------------------------
  * The same operations over yjs's column-encoded update format V2 (UpdateEncoderV2 / UpdateDecoderV2,
@@ -238,6 +264,18 @@ int ygm_contains_v1_device(ygm_ctx *ctx, const uint8_t *d_states, const uint64_t
 int ygm_sync_step2_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                              const uint8_t *d_sv_arena, const uint64_t *d_sv_off, uint32_t n_docs, void *stream,
                              ygm_device_result *out);
+
+/* Shared-state forms, device-resident: d_ask_doc (u32, n_asks entries) as ask_doc above; d_sv_off has n_asks + 1
+ * entries; results are indexed by ask.  Ask a's slot is placed from the exclusive scan, over asks, of each ask's
+ * state length (2 * ask_base[a] + 64 * a).  An id that is out of range or below its predecessor is never used as an
+ * index: that ask carries YGM_EINVAL. */
+int ygm_diff_shared_v1_device(ygm_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_doc_off,
+                              uint32_t n_docs, const uint8_t *d_sv_arena, const uint64_t *d_sv_off,
+                              const uint32_t *d_ask_doc, uint32_t n_asks, void *stream, ygm_device_result *out);
+int ygm_sync_step2_shared_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes,
+                                    const uint64_t *d_state_off, uint32_t n_states, const uint8_t *d_sv_arena,
+                                    const uint64_t *d_sv_off, const uint32_t *d_ask_state, uint32_t n_asks, void *stream,
+                                    ygm_device_result *out);
 
 /* update V2, device-resident (outputs packed in document order: off[d] increasing) */
 int ygm_merge_v2_device(ygm_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_upd_off,

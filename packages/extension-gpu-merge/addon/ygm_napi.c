@@ -224,7 +224,7 @@ static napi_value js_stats(napi_env env, napi_callback_info info) {
   NAPI_CALL(env, napi_create_object(env, &o));
 #define SETN(name, val) NAPI_CALL(env, napi_create_double(env, (double)(val), &v)); NAPI_CALL(env, napi_set_named_property(env, o, name, v));
   SETN("calls", s.calls) SETN("docs", s.docs) SETN("updates", s.updates) SETN("bytesIn", s.bytes_in) SETN("bytesOut", s.bytes_out)
-  SETN("docsFast", s.docs_fast) SETN("docsSeq", s.docs_seq) SETN("kernelMs", s.kernel_ms) SETN("h2dMs", s.h2d_ms) SETN("d2hMs", s.d2h_ms) SETN("docsLean", s.docs_lean) SETN("leanMs", s.lean_ms) SETN("leanLaunches", s.lean_launches) SETN("docsBig", s.docs_big) SETN("docsLeanWide", s.docs_lean_wide) SETN("hostSyncs", s.host_syncs) SETN("docsPending", s.docs_pending)
+  SETN("docsFast", s.docs_fast) SETN("docsSeq", s.docs_seq) SETN("kernelMs", s.kernel_ms) SETN("h2dMs", s.h2d_ms) SETN("d2hMs", s.d2h_ms) SETN("docsLean", s.docs_lean) SETN("leanMs", s.lean_ms) SETN("leanLaunches", s.lean_launches) SETN("docsBig", s.docs_big) SETN("docsLeanWide", s.docs_lean_wide) SETN("hostSyncs", s.host_syncs) SETN("docsPending", s.docs_pending) SETN("docsSnapshot", s.docs_snapshot)
 #undef SETN
   return o;
 }
@@ -269,6 +269,8 @@ static void job_execute(Job *j) {
   else if (j->op == 3) j->rc = ygm_snapshot_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   else if (j->op == 4) j->rc = ygm_contains_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
   else if (j->op == 5) j->rc = ygm_sync_step2_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
+  else if (j->op == 6) j->rc = ygm_diff_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, &r);
+  else if (j->op == 7) j->rc = ygm_sync_step2_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, &r);
   else if (j->op == 10) j->rc = ygm_merge_v2(j->h->ctx, j->arena, j->off, j->docs, j->n_upd, j->n_docs, &r);
   else if (j->op == 11) j->rc = ygm_diff_v2(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
   else if (j->op == 12) j->rc = ygm_sv_from_update_v2(j->h->ctx, j->arena, j->off, j->n_docs, &r);
@@ -485,6 +487,30 @@ static napi_value js_contains(napi_env env, napi_callback_info info) {
   return submit(env, j, argv[0]);
 }
 
+/* diffShared / step2Shared(h, states, stateLens, svArena, svLens, askState:Uint32Array): one result per ask (state
+   vector), ask a answered from state askState[a] (non-decreasing); n_docs = states, n_upd = asks, docs = askState */
+static napi_value js_shared(napi_env env, napi_callback_info info) {
+  size_t argc = 6; napi_value argv[6];
+  void *opd = NULL;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
+  if (argc < 6) { napi_throw_type_error(env, NULL, "step2Shared(handle, states, stateLens, svArena, svLens, askState)"); return NULL; }
+  Handle *h = get_handle(env, argv[0]);
+  if (!h) return NULL;
+  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = (int)(intptr_t)opd; j->h = h;
+  size_t an, ln, sn, sln, kn; void *lens = NULL, *slens = NULL;
+  if (get_bytes(env, argv[1], (void **)&j->arena, &an) || get_bytes(env, argv[2], &lens, &ln) || get_bytes(env, argv[3], (void **)&j->sv, &sn) ||
+      get_bytes(env, argv[4], &slens, &sln) || get_bytes(env, argv[5], (void **)&j->docs, &kn) || kn != sln) {
+    free(lens); free(slens); job_free(j); napi_throw_type_error(env, NULL, "step2Shared: bad arguments (one askState entry per state vector)"); return NULL;
+  }
+  j->n_docs = (uint32_t)(ln / 4);
+  j->n_upd = (uint32_t)(sln / 4);
+  j->off = lens_to_off((const uint32_t *)lens, j->n_docs);
+  j->sv_off = lens_to_off((const uint32_t *)slens, j->n_upd);
+  free(lens); free(slens);
+  if (j->off[j->n_docs] != an || j->sv_off[j->n_upd] != sn) { job_free(j); napi_throw_range_error(env, NULL, "step2Shared: lengths do not match arenas"); return NULL; }
+  return submit(env, j, argv[0]);
+}
+
 /* snapshotMany(h, arena, lens): Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), u)) per update */
 static napi_value js_snapshot(napi_env env, napi_callback_info info) {
   size_t argc = 3; napi_value argv[3];
@@ -514,6 +540,9 @@ static napi_value init(napi_env env, napi_value exports) {
     { "diffMany", NULL, js_diff, NULL, NULL, NULL, napi_default, NULL },
     /* SyncStep2 of stored documents: encodeStateAsUpdate(applyUpdate(new Doc, state), sv) (MessageReceiver.ts:137-138) */
     { "step2Many", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)5 },
+    /* many state vectors answered from one state (a reconnect storm): diffUpdate / SyncStep2 per ask */
+    { "diffShared", NULL, js_shared, NULL, NULL, NULL, napi_default, (void *)(intptr_t)6 },
+    { "step2Shared", NULL, js_shared, NULL, NULL, NULL, napi_default, (void *)(intptr_t)7 },
     { "svMany", NULL, js_sv, NULL, NULL, NULL, napi_default, NULL },
     { "snapshotMany", NULL, js_snapshot, NULL, NULL, NULL, napi_default, NULL },
     { "containsMany", NULL, js_contains, NULL, NULL, NULL, napi_default, NULL },

@@ -17,6 +17,13 @@ export declare class GpuEngine {
   mergeMany (docs: Uint8Array[][]): Promise<(Uint8Array | YgmError)[]>
   diffMany (states: Uint8Array[], svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   stateVectorsMany (states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  /** SyncStep2 payloads of stored documents: Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), state), sv) per pair */
+  step2Many (states: Uint8Array[], svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  /** Many state vectors answered from shared states (a reconnect storm): ask a is answered from states[askState[a]] with
+   *  svs[a]; one result per ask, in caller order, equal to diffMany / step2Many of the pair.  Each state is uploaded
+   *  (step2Shared: and snapshotted) once.  An askState entry that names no state rejects with YgmError EINVAL. */
+  diffShared (states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  step2Shared (states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   /** update format V2: Y.mergeUpdatesV2 / Y.diffUpdateV2 / Y.encodeStateVectorFromUpdateV2 / Y.convertUpdateFormat* (yjs 13.6) */
   mergeManyV2 (docs: Uint8Array[][]): Promise<(Uint8Array | YgmError)[]>
   diffManyV2 (states: Uint8Array[], stateVectors: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
@@ -28,6 +35,8 @@ export declare class GpuEngine {
   snapshotMany (states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   /** Y.snapshotContainsUpdate(Y.snapshot(doc), update), states being normalized (snapshotMany) states */
   containsMany (states: Uint8Array[], updates: Uint8Array[]): Promise<(boolean | YgmError)[]>
+  /** the context's counters (ygm_stats_t), camel-cased: calls, docs, kernelMs, h2dMs, d2hMs, hostSyncs, docsPending,
+   *  docsSnapshot (documents the snapshot kernels ran on: one per state for step2Shared, one per pair for step2Many), ... */
   stats (): Record<string, number>
   close (): void
 }
@@ -46,6 +55,10 @@ export declare class GpuEnginePool {
   mergeMany (names: string[], docs: Uint8Array[][]): Promise<(Uint8Array | YgmError)[]>
   diffMany (names: string[], states: Uint8Array[], svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   stateVectorsMany (names: string[], states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  step2Many (names: string[], states: Uint8Array[], svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  /** the shared-state forms, names[i] naming states[i]: states go to their fnv1a64(name) shard, results in ask order */
+  diffShared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  step2Shared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   snapshot (update: Uint8Array, documentName?: string): Promise<Uint8Array>
   snapshotMany (names: string[], states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   containsMany (names: string[], states: Uint8Array[], updates: Uint8Array[]): Promise<(boolean | YgmError)[]>

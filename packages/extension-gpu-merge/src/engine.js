@@ -179,6 +179,33 @@ class GpuEngine {
    *  (MessageReceiver.ts:137-138) -- the snapshot, then a diff keeping each struct's parentSub bit; EUNSUPPORTED
    *  outside the snapshot envelope */
   async step2Many (states, svs) { const r = await this._run('step2', states.map((s, i) => [s, svs[i]])); return unpack(r) }
+  /**
+   * Many state vectors answered from shared states (a reconnect storm): ask a is answered from states[askState[a]]
+   * with svs[a].  diffShared: Y.diffUpdate per ask; step2Shared: the SyncStep2 payload per ask, byte for byte what
+   * step2Many gives for the pair -- but every state is uploaded and snapshotted once, however many asks name it.
+   * The asks are sorted by state here (the native call takes them non-decreasing); results come back in caller order.
+   */
+  diffShared (states, askState, svs) { return this._shared('diffShared', states, askState, svs) }
+  step2Shared (states, askState, svs) { return this._shared('step2Shared', states, askState, svs) }
+  async _shared (op, states, askState, svs) {
+    const n = svs.length
+    if (askState.length !== n) throw new YgmError(8, 'one state index per state vector')
+    for (let a = 0; a < n; a++) {
+      if (!Number.isInteger(askState[a]) || askState[a] < 0 || askState[a] >= states.length) throw new YgmError(8, loadAddon().strerror(8))
+    }
+    const order = Array.from({ length: n }, (_, a) => a).sort((x, y) => askState[x] - askState[y] || x - y)
+    const run = () => {
+      const u = packBlobs(states); const v = packBlobs(order.map(a => svs[a]))
+      return loadAddon()[op](this.handle, u.arena, u.lens, v.arena, v.lens, Uint32Array.from(order, a => askState[a]))
+    }
+    const p = this.chain.then(run, run)
+    this.chain = p.catch(() => {})
+    const r = unpack(await p)
+    const out = new Array(n)
+    order.forEach((a, k) => { out[a] = r[k] })
+    return out
+  }
+
   async stateVectorsMany (states) { const r = await this._run('sv', states); return unpack(r) }
   async snapshotMany (states) { const r = await this._run('snapshot', states); return unpack(r) }
   /** Y.snapshotContainsUpdate(Y.snapshot(doc), update) per pair, `states` being normalized (snapshotMany) states */
@@ -253,6 +280,32 @@ class GpuEnginePool {
   mergeMany (names, docs) { return this._many(names, [docs], (e, d) => e.mergeMany(d)) }
   diffMany (names, states, svs) { return this._many(names, [states, svs], (e, a, b) => e.diffMany(a, b)) }
   step2Many (names, states, svs) { return this._many(names, [states, svs], (e, a, b) => e.step2Many(a, b)) }
+  /**
+   * The shared-state forms with one name per state: states go to their fnv1a64(name) shard, each shard's asks are
+   * re-indexed to its own states, the shards run concurrently and the results return in caller (ask) order.
+   */
+  diffShared (names, states, askState, svs) { return this._sharedMany('diffShared', names, states, askState, svs) }
+  step2Shared (names, states, askState, svs) { return this._sharedMany('step2Shared', names, states, askState, svs) }
+  async _sharedMany (op, names, states, askState, svs) {
+    if (names.length !== states.length || askState.length !== svs.length) throw new YgmError(8, 'one name per state, one state index per state vector')
+    const shard = names.map(n => this.shardOf(n))
+    const local = new Array(states.length)   // a state's index inside its shard
+    const parts = this.engines.map(() => ({ states: [], asks: [] }))
+    states.forEach((s, i) => { local[i] = parts[shard[i]].states.length; parts[shard[i]].states.push(s) })
+    for (let a = 0; a < svs.length; a++) {
+      const i = askState[a]
+      if (!Number.isInteger(i) || i < 0 || i >= states.length) throw new YgmError(8, 'ask names no state')
+      parts[shard[i]].asks.push(a)
+    }
+    const out = new Array(svs.length)
+    await Promise.all(parts.map(async (p, e) => {
+      if (!p.asks.length) return
+      const r = await this.engines[e][op](p.states, p.asks.map(a => local[askState[a]]), p.asks.map(a => svs[a]))
+      p.asks.forEach((a, k) => { out[a] = r[k] })
+    }))
+    return out
+  }
+
   stateVectorsMany (names, states) { return this._many(names, [states], (e, a) => e.stateVectorsMany(a)) }
   snapshotMany (names, states) { return this._many(names, [states], (e, a) => e.snapshotMany(a)) }
   containsMany (names, states, updates) { return this._many(names, [states, updates], (e, a, b) => e.containsMany(a, b)) }

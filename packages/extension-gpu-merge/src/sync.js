@@ -12,8 +12,9 @@
 // Step2 payload is the reference's own bytes for a document loaded from that state:
 // encodeStateAsUpdate(applyUpdate(new Doc, state), sv) -- the GPU snapshot of the state (§8f-1), then a diff
 // in which every struct keeps its parentSub bit (step2Many, ygm_sync_step2_v1; pinned against yjs by
-// tests/test_step2.py).  A state outside the snapshot kernel's envelope (pending structs or delete set,
-// sub-documents) is answered with diffUpdate(state, sv) -- the same content, not the same bytes -- and
+// tests/test_step2.py).  The asks are grouped by document: with an engine that has step2Shared
+// (ygm_sync_step2_shared_v1) a document's state is uploaded and snapshotted once for all of its asks.  A state
+// outside the snapshot kernel's envelope (pending structs or delete set, sub-documents) is answered with diffUpdate(state, sv) -- the same content, not the same bytes -- and
 // NAMED: its reply array carries `unnormalized: true` and the document is listed in
 // responder.unnormalized.  The server's Step1 carries encodeStateVectorFromUpdate(state).
 
@@ -84,6 +85,11 @@ class SyncResponder {
   _merge (names, docs) { return this._pooled() ? this.engine.mergeMany(names, docs) : this.engine.mergeMany(docs) }
   _diff (names, states, svs) { return this._pooled() ? this.engine.diffMany(names, states, svs) : this.engine.diffMany(states, svs) }
   _step2 (names, states, svs) { return this._pooled() ? this.engine.step2Many(names, states, svs) : this.engine.step2Many(states, svs) }
+  // one state per document, many asks (engines that have the shared-state forms): asks[k] = { d: index into names, sv }
+  _shared (op, names, states, askState, svs) {
+    return this._pooled() ? this.engine[op](names, states, askState, svs) : this.engine[op](states, askState, svs)
+  }
+
   _svs (names, states) { return this._pooled() ? this.engine.stateVectorsMany(names, states) : this.engine.stateVectorsMany(states) }
 
   /**
@@ -122,11 +128,22 @@ class SyncResponder {
     }
     const live = asks.filter(a => !(state.get(a.documentName) instanceof Error))
     asks.filter(a => state.get(a.documentName) instanceof Error).forEach(a => { out[a.i] = state.get(a.documentName) })
-    const diffs = await this._step2(live.map(a => a.documentName), live.map(a => state.get(a.documentName)), live.map(a => a.payload))
+    // a storm is many asks on few documents: with an engine that has step2Shared each document's state goes up once
+    // and is snapshotted once, the asks name it; otherwise one (state, sv) pair per ask
+    const grouped = rows => {
+      const docs = Array.from(new Set(rows.map(a => a.documentName)))
+      const at = new Map(docs.map((n, k) => [n, k]))
+      return [docs, docs.map(n => state.get(n)), rows.map(a => at.get(a.documentName)), rows.map(a => a.payload)]
+    }
+    const diffs = typeof this.engine.step2Shared === 'function'
+      ? await this._shared('step2Shared', ...grouped(live))
+      : await this._step2(live.map(a => a.documentName), live.map(a => state.get(a.documentName)), live.map(a => a.payload))
     // states the snapshot kernel does not take: diffUpdate of the state itself, named as such
     const unsup = live.map((a, k) => diffs[k] instanceof Error && diffs[k].code === 'EUNSUPPORTED' ? k : -1).filter(k => k >= 0)
     if (unsup.length) {
-      const plain = await this._diff(unsup.map(k => live[k].documentName), unsup.map(k => state.get(live[k].documentName)), unsup.map(k => live[k].payload))
+      const plain = typeof this.engine.diffShared === 'function'
+        ? await this._shared('diffShared', ...grouped(unsup.map(k => live[k])))
+        : await this._diff(unsup.map(k => live[k].documentName), unsup.map(k => state.get(live[k].documentName)), unsup.map(k => live[k].payload))
       unsup.forEach((k, j) => {
         diffs[k] = plain[j]
         if (!(plain[j] instanceof Error)) { plain[j].unnormalized = true; this.unnormalized.push(live[k].documentName) }

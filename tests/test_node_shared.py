@@ -1,0 +1,33 @@
+"""The reconnect storm through the Node sync responder (packages/extension-gpu-merge/test/shared.js): with an engine
+that has step2Shared, SyncResponder.answerMany sends one state per document and one state vector per message; the
+reply frames are yjs's own, in message order."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+PKG = os.path.join(ROOT, "packages", "extension-gpu-merge")
+BUNDLE = "/opt/conda/share/jupyter/lab/static/3502.fbe0c610be82ba1360db.js"
+needs_node = pytest.mark.skipif(shutil.which("node") is None or not os.path.exists(BUNDLE),
+                                reason="node or the bundled yjs (test oracle) not present")
+
+
+def run(mode):
+    r = subprocess.run(["node", os.path.join(PKG, "test", "shared.js"), f"--{mode}"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "passed" in r.stdout
+
+
+@needs_node
+def test_storm_cpu_double():
+    run("cpu")
+
+
+@needs_node
+@pytest.mark.gpu
+def test_storm_gpu_addon():
+    assert os.path.exists(os.path.join(PKG, "build", "ygm_napi.node")), "N-API addon not built"
+    run("gpu")
