@@ -292,9 +292,13 @@ __global__ __launch_bounds__(64) void k_v12_fast(const uint8_t* __restrict__ v1,
   }
 }
 
-// persistent grids: the waves resident at once (their column scratch is reused group after group)
+// persistent grids: the waves resident at once (their column scratch is reused group after group).
+// YGM_V12F_GRID (testing knob, as YGM_WALK_GRID of the walker): a positive value replaces the resident count of
+// both tiers -- a small grid gives every wave many groups, so its LDS slots and column scratch are reused.  Read on
+// every call (never cached); the scratch size and the launch of one call both come from here.
 template <int D, int FIN>
 static uint32_t v12f_grid() {
+  if (const char* e = getenv("YGM_V12F_GRID")) { const long v = atol(e); if (v > 0 && v <= 0x7FFFFFFFl) return (uint32_t)v; }
   int dev = 0, cus = 0, per = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_v12_fast<D, FIN>, WAVE, 0) != hipSuccess || cus <= 0 || per <= 0)

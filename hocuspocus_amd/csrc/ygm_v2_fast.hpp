@@ -15,7 +15,8 @@
 // origin or with a parent (parentInfo 1: a root-type key; 0: a parent id) and an optional parentSub, content
 // ContentDeleted / ContentString (ASCII: UTF-16 length = bytes), the delete set (ranges in clock order per
 // client), values < 2^32.  Anything else returns false and the document takes v12_body; the tests compare both
-// paths byte for byte (tests/test_v2_fast_host.py on the host build, tests/test_v2.py on the GPU).
+// paths byte for byte (tests/test_v2_fast_host.py on the host build; on the GPU tests/test_v2.py and, for the kernel
+// code around this file -- tiers, persistent loop, staging --, tests/test_v2_fast_gpu.py).
 #pragma once
 #include "ygm_v2.hpp"
 
