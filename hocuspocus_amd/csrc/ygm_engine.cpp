@@ -45,7 +45,8 @@ int ygm_k_launch_pend_split_g(const uint32_t* list, uint32_t P, const uint32_t* 
 int ygm_k_launch_snap_plan(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, void* cnt, uint64_t* ws_off,
                            uint64_t* bs, const uint8_t* claim, hipStream_t s);
 int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                           uint64_t* out_len, int32_t* status, uint8_t* claim, unsigned long long* pay, int again, uint64_t slot_total, hipStream_t s);
+                           uint64_t* out_len, int32_t* status, uint8_t* claim, unsigned long long* pay, int again, uint64_t slot_total,
+                           const uint8_t* opt, hipStream_t s);
 int ygm_k_launch_cont_plan(const uint8_t* st_arena, const uint64_t* st_off, uint32_t n_docs, uint32_t flags, uint64_t* ws_off, uint64_t* bs,
                            hipStream_t s);
 int ygm_k_launch_cont(const uint8_t* st_arena, const uint64_t* st_off, const uint8_t* up_arena, const uint64_t* up_off, uint32_t n_docs,
@@ -56,7 +57,7 @@ int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_
                       uint64_t base, uint32_t* pend_list, unsigned int* pend_n, hipStream_t s);
 int ygm_k_launch_snap_w(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
                         uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
-                        uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, hipStream_t s);
+                        uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, const uint8_t* opt, hipStream_t s);
 int ygm_k_launch_pend_plan(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, uint64_t* upd_off, uint32_t* doc_upd,
                            hipStream_t s);
 int ygm_k_launch_pend_copy(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const uint64_t* upd_off, uint8_t* dst,
@@ -199,7 +200,7 @@ struct ygm_ctx {
   hipStream_t stream2 = nullptr;   // the large-document tier's 16-wave launch, beside the mid size's on `stream`
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
   // device inputs (host API staging)
-  DevBuf arena, offs, docs, sv_arena, sv_offs;
+  DevBuf arena, offs, docs, sv_arena, sv_offs, opt;   // (opt: the chunk's per-document option bytes, *_opts_v1)
   // device outputs + state
   DevBuf out, out_off, out_len, status, lb, meta, fb_list, defer_list, defer2_list, defer_w_list, route_list;
   Meta* h_meta = nullptr;  // pinned read-back of the per-launch counters
@@ -306,7 +307,7 @@ void ygm_close(ygm_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-  for (DevBuf* b : {&c->arena, &c->offs, &c->docs, &c->sv_arena, &c->sv_offs, &c->out, &c->out_off, &c->out_len, &c->status,
+  for (DevBuf* b : {&c->arena, &c->offs, &c->docs, &c->sv_arena, &c->sv_offs, &c->opt, &c->out, &c->out_off, &c->out_len, &c->status,
                     &c->lb, &c->meta, &c->fb_list, &c->defer_list, &c->defer2_list, &c->defer_w_list, &c->route_list, &c->s_readers, &c->s_order, &c->s_tmp, &c->s_ubase, &c->s_ulen, &c->s_cnt,
                     &c->s_drec, &c->big_blk, &c->big_rec, &c->big_list, &c->big_scan, &c->big_up, &c->lens_off, &c->sv_tbl, &c->sv_tn, &c->ask_ix, &c->ask_base, &c->ask_bs, &c->ask_pl, &c->ask_pn, &c->sn_cnt, &c->sn_off, &c->sn_bs, &c->sn_ws, &c->sn_claim, &c->sn_pay,
                     &c->sn_pend, &c->pn_off, &c->pn_du, &c->pn_arena,
@@ -719,8 +720,10 @@ static int snap_resolve_pending(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t 
 // leave: when non-null, documents left pending are not resolved: their count goes there (list c->sn_pend, statuses
 // ST_PEND, their PendHdr layouts at out_off)
 // dpw: k_snap's documents per wave (0: its default)
+// d_opt: the documents' option bytes (YGM_DOC_NO_GC; null: none set), read by k_snap_text and k_snap
 static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off, uint32_t n_docs,
-                        hipStream_t s, ygm_device_result* out, uint32_t xf, uint32_t* leave = nullptr, uint32_t dpw = 0) {
+                        hipStream_t s, ygm_device_result* out, uint32_t xf, uint32_t* leave = nullptr, uint32_t dpw = 0,
+                        const uint8_t* d_opt = nullptr) {
   if (leave) *leave = 0;
   const uint32_t fl = c->flags | xf;
   const uint32_t nb = (n_docs + 1 + 255) / 256;
@@ -740,7 +743,7 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
     HIPCHK(hipMemsetAsync(c->sn_pay.p, 0, 16, s));
     for (int again = 0; again < 2 && lds_pay[1] < n_docs; again++) {   // 6 KiB per document, then 24 KiB for what it left
       if (ygm_k_launch_snap_text(d_arena, d_doc_off, n_docs, fl, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
-                                 c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(), c->sn_pay.as<unsigned long long>(), again, slot_total, s))
+                                 c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(), c->sn_pay.as<unsigned long long>(), again, slot_total, d_opt, s))
         return YGM_EDEVICE;
       HIPCHK(hipMemcpyAsync(c->h_meta, c->sn_pay.p, 16, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
@@ -764,7 +767,7 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
     if (ygm_k_launch_snap_w(d_arena, d_doc_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_ws.as<uint8_t>(),
                             c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
                             (unsigned long long*)((uint8_t*)meta + offsetof(Meta, payload)), claim, slot_total, c->sn_pend.as<uint32_t>(),
-                            (unsigned int*)((uint8_t*)meta + offsetof(Meta, fb_count)), dpw, s))
+                            (unsigned int*)((uint8_t*)meta + offsetof(Meta, fb_count)), dpw, d_opt, s))
       return YGM_EDEVICE;
     int e = read_meta(c, s, m, meta);
     if (e) return e;
@@ -785,11 +788,15 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
   out->status = c->status.as<int32_t>(); out->data_bytes = total_out ? total_out : slot_total + total; out->payload_bytes = m.payload;
   return YGM_OK;
 }
-int ygm_snapshot_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off, uint32_t n_docs,
-                           void* stream, ygm_device_result* out) {
+int ygm_snapshot_opts_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off,
+                                const uint8_t* d_doc_opt, uint32_t n_docs, void* stream, ygm_device_result* out) {
   if (!c || !out) return YGM_EINVAL;
   (void)hipSetDevice(c->device);
-  return snapshot_dev(c, d_arena, arena_bytes, d_doc_off, n_docs, stream ? (hipStream_t)stream : c->stream, out, 0);
+  return snapshot_dev(c, d_arena, arena_bytes, d_doc_off, n_docs, stream ? (hipStream_t)stream : c->stream, out, 0, nullptr, 0, d_doc_opt);
+}
+int ygm_snapshot_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off, uint32_t n_docs,
+                           void* stream, ygm_device_result* out) {
+  return ygm_snapshot_opts_v1_device(c, d_arena, arena_bytes, d_doc_off, nullptr, n_docs, stream, out);
 }
 // a snapshot batch's outputs packed into one arena on the device (k_pack_*: offsets n + 1, the total at [n]) with its
 // statuses, for kernels that read documents by offsets (step2's diff, contains)
@@ -931,10 +938,12 @@ static int step2_pending_finish(ygm_ctx* c, hipStream_t s, uint32_t P, const uin
 // SyncStep2 of stored documents (MessageReceiver.ts:137-138): the snapshot batch, its outputs packed into one arena
 // on the device (k_pack_*: offsets n + 1, the total at [n]), the diff kernels over it with F_KEEP_SUB, and the
 // snapshot's per-document refusals (EUNSUPPORTED, malformed states) carried into the result; states that leave
-// pending parts by step2_pending_split / _finish
-int ygm_sync_step2_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
-                             const uint8_t* d_sv_arena, const uint64_t* d_sv_off, uint32_t n_docs, void* stream,
-                             ygm_device_result* out) {
+// pending parts by step2_pending_split / _finish.  d_state_opt: the states' option bytes (a no-GC state's snapshot
+// keeps its deleted content, so the diff sends the deleted Items as the reference's live gc: false document does; the
+// pending parts are merged, never collected, so only the state part depends on it)
+int ygm_sync_step2_opts_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
+                                  const uint8_t* d_state_opt, const uint8_t* d_sv_arena, const uint64_t* d_sv_off, uint32_t n_docs,
+                                  void* stream, ygm_device_result* out) {
   if (!c || !out) return YGM_EINVAL;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   (void)hipSetDevice(c->device);
@@ -943,7 +952,7 @@ int ygm_sync_step2_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t state
 #define S2CHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { if (dbg) fprintf(stderr, "ygm step2: %s: %s\n", #x, hipGetErrorString(_e)); return YGM_EDEVICE; } } while (0)
   uint32_t P = 0;   // documents the snapshot leaves pending (their parts split off now, answered after the diff)
   uint64_t ptot[4] = {0, 0, 0, 0};
-  int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_docs, s, &r1, 0, &P);
+  int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_docs, s, &r1, 0, &P, 0, d_state_opt);
   if (!e && P) e = step2_pending_split(c, s, P, d_sv_arena, d_sv_off, ptot);
   if (dbg) fprintf(stderr, "ygm step2: snapshot rc %d payload %llu\n", e, (unsigned long long)r1.payload_bytes);
   if (e || (e = pack_snapshots(c, s, r1, n_docs))) return e;
@@ -958,6 +967,11 @@ int ygm_sync_step2_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t state
   S2CHK(hipStreamSynchronize(s));
   return YGM_OK;
 #undef S2CHK
+}
+int ygm_sync_step2_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
+                             const uint8_t* d_sv_arena, const uint64_t* d_sv_off, uint32_t n_docs, void* stream,
+                             ygm_device_result* out) {
+  return ygm_sync_step2_opts_v1_device(c, d_states, states_bytes, d_state_off, nullptr, d_sv_arena, d_sv_off, n_docs, stream, out);
 }
 
 // ------------------------------------------------------------------ shared states (device API)
@@ -974,10 +988,13 @@ int ygm_diff_shared_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena
 // SyncStep2 of a reconnect storm: the snapshot batch over the n_states states (each once), packed; the gather diff
 // with F_KEEP_SUB over the n_asks asks, reading the packed snapshots in place; each state's refusal carried to its
 // asks; the asks of states the snapshot left pending split off before the diff (their state's three parts copied per
-// ask, the state not snapshotted again) and finished after it at their ask indices
-int ygm_sync_step2_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
-                                    uint32_t n_states, const uint8_t* d_sv_arena, const uint64_t* d_sv_off, const uint32_t* d_ask_state,
-                                    uint32_t n_asks, void* stream, ygm_device_result* out) {
+// ask, the state not snapshotted again) and finished after it at their ask indices.  d_state_opt: one option byte per
+// state -- the option acts in the snapshot alone, so a state's asks inherit it (and a bad byte's YGM_EINVAL) through
+// the packed snapshot and the status carry; the gather kernels need nothing more
+int ygm_sync_step2_shared_opts_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
+                                         const uint8_t* d_state_opt, uint32_t n_states, const uint8_t* d_sv_arena,
+                                         const uint64_t* d_sv_off, const uint32_t* d_ask_state, uint32_t n_asks, void* stream,
+                                         ygm_device_result* out) {
   if (!c || !out || (n_asks && (!d_sv_off || !d_ask_state))) return YGM_EINVAL;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   (void)hipSetDevice(c->device);
@@ -995,7 +1012,7 @@ int ygm_sync_step2_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_
     const uint32_t fill = std::max<uint32_t>(1u, (n_states + 767u) / 768u);
     dpw = std::min(parity, fill);
   }
-  int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_states, s, &r1, 0, &P, dpw);
+  int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_states, s, &r1, 0, &P, dpw, d_state_opt);
   if (e) return e;
   if (P && n_asks) {
     if ((e = ask_plan(c, s, d_state_off, n_states, d_ask_state, n_asks))) return e;
@@ -1039,6 +1056,12 @@ int ygm_sync_step2_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_
   if (PA && (e = step2_pending_finish(c, s, PA, ptot, out, c->ask_pl.as<uint32_t>()))) return e;
   HIPCHK(hipStreamSynchronize(s));
   return YGM_OK;
+}
+int ygm_sync_step2_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
+                                    uint32_t n_states, const uint8_t* d_sv_arena, const uint64_t* d_sv_off, const uint32_t* d_ask_state,
+                                    uint32_t n_asks, void* stream, ygm_device_result* out) {
+  return ygm_sync_step2_shared_opts_v1_device(c, d_states, states_bytes, d_state_off, nullptr, n_states, d_sv_arena, d_sv_off, d_ask_state,
+                                              n_asks, stream, out);
 }
 
 // ------------------------------------------------------------------ update V2 (device API)
@@ -1240,6 +1263,7 @@ struct HostCall {
               // step2 (host_shared_call: n_docs states, n_upd asks, upd_doc = the asks' states)
   const uint8_t* arena; const uint64_t* off; const uint32_t* upd_doc; const uint8_t* sv_arena; const uint64_t* sv_off;
   uint32_t n_upd, n_docs;
+  const uint8_t* opt = nullptr;   // modes 3 / 10: n_docs option bytes, mode 12: one per state (null: none); each chunk stages its slice
 };
 }  // namespace
 
@@ -1295,7 +1319,8 @@ static int chunk_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
   uint64_t s0 = 0, s1 = 0, sb = 0;
   if (two) { s0 = H.sv_off[C.d0]; s1 = H.sv_off[C.d1]; sb = ((s1 - s0) + 64 + 15) & ~15ull; }
   const uint64_t n_off = (uint64_t)nu + 1, n_doc = is_merge(H.mode) ? (uint64_t)nd + 1 : 0, n_sv = two ? (uint64_t)nd + 1 : 0;
-  const uint64_t need = ab + 8 * n_off + sb + 8 * n_sv + 4 * n_doc + 64;
+  const uint64_t n_opt = H.opt ? (uint64_t)nd : 0;
+  const uint64_t need = ab + 8 * n_off + sb + 8 * n_sv + 4 * n_doc + n_opt + 64;
   if (!k->h_in.ensure(need)) return YGM_ENOMEM;
   uint8_t* P = k->h_in.as<uint8_t>();
   par_memcpy(P, H.arena + a0, bytes); memset(P + bytes, 0, ab - bytes);
@@ -1316,8 +1341,10 @@ static int chunk_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
     uint32_t u = C.u0;
     for (uint32_t d = 0; d < nd; d++) { while (u < C.u1 && H.upd_doc[u] == C.d0 + d) u++; du[d + 1] = u - C.u0; }
   }
+  uint8_t* po = q + 4 * n_doc;   // the chunk's option bytes, after everything else
+  if (n_opt) memcpy(po, H.opt + C.d0, n_opt);
   if (!k->arena.ensure(ab) || !k->offs.ensure(8 * n_off) || (two && (!k->sv_arena.ensure(sb) || !k->sv_offs.ensure(8 * n_sv))) ||
-      (is_merge(H.mode) && !k->docs.ensure(4 * n_doc)))
+      (is_merge(H.mode) && !k->docs.ensure(4 * n_doc)) || (n_opt && !k->opt.ensure(n_opt)))
     return YGM_ENOMEM;
   HIPCHK(hipEventRecord(C.h0, k->stream));
   HIPCHK(hipMemcpyAsync(k->arena.p, P, ab, hipMemcpyHostToDevice, k->stream));
@@ -1327,6 +1354,7 @@ static int chunk_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
     HIPCHK(hipMemcpyAsync(k->sv_offs.p, P + ab + 8 * n_off + sb, 8 * n_sv, hipMemcpyHostToDevice, k->stream));
   }
   if (is_merge(H.mode)) HIPCHK(hipMemcpyAsync(k->docs.p, q, 4 * n_doc, hipMemcpyHostToDevice, k->stream));
+  if (n_opt) HIPCHK(hipMemcpyAsync(k->opt.p, po, n_opt, hipMemcpyHostToDevice, k->stream));
   HIPCHK(hipEventRecord(C.h1, k->stream));
   return YGM_OK;
 }
@@ -1349,9 +1377,11 @@ static int chunk_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint64
                                                             C.u1 - C.u0, nd, nullptr, &dr);
   else if (H.mode == 4) e = ygm_contains_v1_device(k, k->arena.as<uint8_t>(), k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
                                                    k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 3) e = ygm_snapshot_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 10) e = ygm_sync_step2_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
-                                                      k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
+  else if (H.mode == 3) e = ygm_snapshot_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
+                                                        H.opt && nd ? k->opt.as<uint8_t>() : nullptr, nd, nullptr, &dr);
+  else if (H.mode == 10) e = ygm_sync_step2_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
+                                                           H.opt && nd ? k->opt.as<uint8_t>() : nullptr, k->sv_arena.as<uint8_t>(),
+                                                           k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
   else if (H.mode == 1) e = ygm_diff_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
                                                k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
   else e = ygm_sv_from_update_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
@@ -1509,7 +1539,8 @@ static int shared_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
   const uint64_t a0 = H.off[C.u0], bytes = H.off[C.u1] - a0, ab = (bytes + 64 + 15) & ~15ull;
   const uint64_t s0 = H.sv_off[C.d0], svb = H.sv_off[C.d1] - s0, sb = (svb + 64 + 15) & ~15ull;
   const uint64_t n_off = (uint64_t)ns + 1, n_sv = (uint64_t)na + 1;
-  if (!k->h_in.ensure(ab + 8 * n_off + sb + 8 * n_sv + 4ull * na + 64)) return YGM_ENOMEM;
+  const uint64_t n_opt = H.opt ? (uint64_t)ns : 0;   // the chunk's states' option bytes (a split state's byte in each of its chunks)
+  if (!k->h_in.ensure(ab + 8 * n_off + sb + 8 * n_sv + 4ull * na + n_opt + 64)) return YGM_ENOMEM;
   uint8_t* P = k->h_in.as<uint8_t>();
   if (bytes) par_memcpy(P, H.arena + a0, bytes);
   memset(P + bytes, 0, ab - bytes);
@@ -1522,8 +1553,10 @@ static int shared_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
   for (uint64_t j = 0; j < n_sv; j++) rs[j] = H.sv_off[C.d0 + j] - s0;
   uint32_t* ra = (uint32_t*)(q + sb + 8 * n_sv);
   for (uint32_t j = 0; j < na; j++) ra[j] = H.upd_doc[C.d0 + j] - C.u0;
+  uint8_t* po = (uint8_t*)(ra + na);
+  if (n_opt) memcpy(po, H.opt + C.u0, n_opt);
   if (!k->arena.ensure(ab) || !k->offs.ensure(8 * n_off) || !k->sv_arena.ensure(sb) || !k->sv_offs.ensure(8 * n_sv) ||
-      !k->docs.ensure(4ull * na + 4))
+      !k->docs.ensure(4ull * na + 4) || (n_opt && !k->opt.ensure(n_opt)))
     return YGM_ENOMEM;
   HIPCHK(hipEventRecord(C.h0, k->stream));
   HIPCHK(hipMemcpyAsync(k->arena.p, P, ab, hipMemcpyHostToDevice, k->stream));
@@ -1531,6 +1564,7 @@ static int shared_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
   HIPCHK(hipMemcpyAsync(k->sv_arena.p, q, sb, hipMemcpyHostToDevice, k->stream));
   HIPCHK(hipMemcpyAsync(k->sv_offs.p, rs, 8 * n_sv, hipMemcpyHostToDevice, k->stream));
   if (na) HIPCHK(hipMemcpyAsync(k->docs.p, ra, 4ull * na, hipMemcpyHostToDevice, k->stream));
+  if (n_opt) HIPCHK(hipMemcpyAsync(k->opt.p, po, n_opt, hipMemcpyHostToDevice, k->stream));
   HIPCHK(hipEventRecord(C.h1, k->stream));
   return YGM_OK;
 }
@@ -1539,8 +1573,9 @@ static int shared_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint6
   const uint64_t bytes = H.off[C.u1] - H.off[C.u0];
   ygm_device_result dr;
   int e;
-  if (H.mode == 12) e = ygm_sync_step2_shared_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), ns, k->sv_arena.as<uint8_t>(),
-                                                        k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
+  if (H.mode == 12) e = ygm_sync_step2_shared_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
+                                                             H.opt && ns ? k->opt.as<uint8_t>() : nullptr, ns, k->sv_arena.as<uint8_t>(),
+                                                             k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
   else e = ygm_diff_shared_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), ns, k->sv_arena.as<uint8_t>(),
                                      k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
   if (e) return e;
@@ -1566,14 +1601,14 @@ static int shared_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint6
   return YGM_OK;
 }
 static int host_shared_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, const uint8_t* sv_arena,
-                            const uint64_t* sv_off, const uint32_t* ask_doc, uint32_t n_asks, ygm_result* out) {
+                            const uint64_t* sv_off, const uint32_t* ask_doc, uint32_t n_asks, ygm_result* out, const uint8_t* opt = nullptr) {
   if (!c || !out || (n_docs && !doc_off) || (n_asks && (!sv_off || !ask_doc))) return YGM_EINVAL;
   for (uint32_t d = 0; d < n_docs; d++) if (doc_off[d + 1] < doc_off[d]) return YGM_EINVAL;
   for (uint32_t a = 0; a < n_asks; a++)
     if (ask_doc[a] >= n_docs || (a && ask_doc[a] < ask_doc[a - 1]) || sv_off[a + 1] < sv_off[a]) return YGM_EINVAL;
   if ((n_docs && doc_off[n_docs] > doc_off[0] && !arena) || (n_asks && sv_off[n_asks] > sv_off[0] && !sv_arena)) return YGM_EINVAL;
   static const uint64_t zero_off[1] = {0};
-  HostCall H{mode, arena, n_docs ? doc_off : zero_off, ask_doc, sv_arena, n_asks ? sv_off : zero_off, n_asks, n_docs};
+  HostCall H{mode, arena, n_docs ? doc_off : zero_off, ask_doc, sv_arena, n_asks ? sv_off : zero_off, n_asks, n_docs, opt};
   (void)hipSetDevice(c->device);
   uint64_t in_bytes = n_docs ? doc_off[n_docs] - doc_off[0] : 0, vbytes = in_bytes;
   for (uint32_t a = 0; a < n_asks; a++) vbytes += doc_off[ask_doc[a] + 1] - doc_off[ask_doc[a]];
@@ -1628,6 +1663,11 @@ int ygm_sync_step2_shared_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* 
                              const uint64_t* sv_off, const uint32_t* ask_state, uint32_t n_asks, ygm_result* out) {
   return host_shared_call(c, 12, states, state_off, n_states, sv_arena, sv_off, ask_state, n_asks, out);
 }
+int ygm_sync_step2_shared_opts_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* state_opt, uint32_t n_states,
+                                  const uint8_t* sv_arena, const uint64_t* sv_off, const uint32_t* ask_state, uint32_t n_asks,
+                                  ygm_result* out) {
+  return host_shared_call(c, 12, states, state_off, n_states, sv_arena, sv_off, ask_state, n_asks, out, state_opt);
+}
 
 int ygm_merge_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* upd_doc, uint32_t n_upd, uint32_t n_docs,
                  ygm_result* out) {
@@ -1655,7 +1695,7 @@ int ygm_merge_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, cons
 }
 
 static int host_doc_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena,
-                         const uint64_t* sv_off, uint32_t n_docs, ygm_result* out) {
+                         const uint64_t* sv_off, uint32_t n_docs, ygm_result* out, const uint8_t* opt = nullptr) {
   if (!c || !out || (n_docs && (!arena || !doc_off))) return YGM_EINVAL;
   const bool two = mode == 1 || mode == 4 || mode == 6 || mode == 10;
   if (two && n_docs && (!sv_arena || !sv_off)) return YGM_EINVAL;
@@ -1664,7 +1704,7 @@ static int host_doc_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint6
     if (two && sv_off[d + 1] < sv_off[d]) return YGM_EINVAL;
   }
   static const uint64_t zero_off[1] = {0};
-  HostCall H{mode, arena, n_docs ? doc_off : zero_off, nullptr, sv_arena, n_docs ? sv_off : zero_off, 0, n_docs};
+  HostCall H{mode, arena, n_docs ? doc_off : zero_off, nullptr, sv_arena, n_docs ? sv_off : zero_off, 0, n_docs, opt};
   return host_call(c, H, out);
 }
 
@@ -1676,10 +1716,17 @@ int ygm_contains_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off
 int ygm_snapshot_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
   return host_doc_call(c, 3, arena, doc_off, nullptr, nullptr, n_docs, out);
 }
+int ygm_snapshot_opts_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* doc_opt, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, 3, arena, doc_off, nullptr, nullptr, n_docs, out, doc_opt);
+}
 
 int ygm_sync_step2_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* sv_arena, const uint64_t* sv_off,
                       uint32_t n_docs, ygm_result* out) {
   return host_doc_call(c, 10, states, state_off, sv_arena, sv_off, n_docs, out);
+}
+int ygm_sync_step2_opts_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* state_opt, const uint8_t* sv_arena,
+                           const uint64_t* sv_off, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, 10, states, state_off, sv_arena, sv_off, n_docs, out, state_opt);
 }
 
 int ygm_diff_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,

@@ -19,6 +19,9 @@
 //   * ASCII content: a part's bytes are its input slice [coff, coff + len); a split cuts the slice at the clock
 //     offset, and a merged part's bytes are its own slice followed by those of the parts it absorbed (they follow
 //     it in the client's clock order), so no piece lists.
+// A no-GC document (snap::F_SNAP_NOGC, a Y.Doc({gc: false})) skips the GC step: a deleted part keeps T_STR and its
+// slice, merges with deleted T_STR neighbours only (the merge test compares T_DEL | T_STR), and is written as a
+// ContentString; the encoder's slice copy is the one live merged runs use.  The envelope is the same.
 #pragma once
 #include "ygm_snapshot.hpp"
 
@@ -350,7 +353,8 @@ struct TDoc {
     return m;
   }
   YDEV void gc_merge() {
-    for (uint32_t i = 0; i < np; i++) if (p[i].fl & T_DEL) p[i].fl = (uint8_t)(p[i].fl & ~T_STR);   // tryGcDeleteSet
+    if (!(flags & snap::F_SNAP_NOGC))   // tryGcDeleteSet (doc.gc)
+      for (uint32_t i = 0; i < np; i++) if (p[i].fl & T_DEL) p[i].fl = (uint8_t)(p[i].fl & ~T_STR);
     for (uint32_t k = 0; k < nc; k++) {   // one right-to-left tryToMergeWithLeft pass per client
       const uint32_t m = client_seq(k, false);
       for (uint32_t e = m; e-- > 1;) {

@@ -8,6 +8,9 @@
 //                  documents for the merge kernels (plan, copy), then the merged bytes' places written back (fix)
 // A thread per document keeps the reference's sequential algorithm (YATA integration order matters)
 // while 64 documents share a wave; the workspace is per document, so nothing is shared.
+// k_snap_text and k_snap take a nullable per-document option array (one byte each; bit 0, YGM_DOC_NO_GC: the document
+// is a Y.Doc({gc: false}), snap::F_SNAP_NOGC for that document alone; any other bit: ST_INVAL for that document, the
+// byte not used otherwise).  The count pass does not depend on it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -51,14 +54,16 @@ template <uint32_t LB>
 __global__ __launch_bounds__(SN_NT) void k_snap_text(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, uint32_t n_docs,
                                                     uint32_t flags, uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
                                                     uint64_t* __restrict__ out_len, int32_t* __restrict__ status, uint8_t* __restrict__ claim,
-                                                    unsigned long long* __restrict__ pay, uint32_t again, uint64_t slot_total) {
+                                                    unsigned long long* __restrict__ pay, uint32_t again, uint64_t slot_total,
+                                                    const uint8_t* __restrict__ opt) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[LB];
   const uint32_t d = blockIdx.x;
   if (threadIdx.x != 0 || (again && claim[d])) return;   // (again: the first launch took it)
   const uint64_t a = doc_off[d], b = doc_off[d + 1];
   bool ok = false;
-  // (a slot past the caller's region, slot_total = 2 * arena_bytes + 64 * n_docs: left to the general path)
-  if (b > a && b - a < 0xFFFFu && snap::al16(2 * a + 64ull * d) + 2 * (b - a) + 48 <= slot_total) {
+  // (a slot past the caller's region, slot_total = 2 * arena_bytes + 64 * n_docs: left to the general path, as is a
+  // document with a bad option byte: k_snap gives it its status)
+  if (snap::doc_flags(flags, opt, d, flags) && b > a && b - a < 0xFFFFu && snap::al16(2 * a + 64ull * d) + 2 * (b - a) + 48 <= slot_total) {
     const uint32_t n = (uint32_t)(b - a);
     const uint64_t slot = snap::al16(2 * a + 64ull * d);
     snap::OutCap o{out + slot, 0, 2u * n + 48u};
@@ -127,7 +132,7 @@ __global__ __launch_bounds__(SN_NT) void k_snap(const uint8_t* __restrict__ aren
                                                uint8_t* __restrict__ ws, uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
                                                int32_t* __restrict__ status, unsigned long long* __restrict__ payload, uint32_t dpw,
                                                const uint8_t* __restrict__ claim, uint64_t base, uint32_t* __restrict__ pend_list,
-                                               unsigned int* __restrict__ pend_n) {
+                                               unsigned int* __restrict__ pend_n, const uint8_t* __restrict__ opt) {
   // dpw documents per wave (lanes >= dpw idle): the per-document code diverges from lane to lane, so
   // fewer documents per wave trade SIMD lanes for less serialised divergence and more waves in flight
   __shared__ __attribute__((aligned(16))) uint8_t stg[SN_STAGE + 16];
@@ -140,11 +145,12 @@ __global__ __launch_bounds__(SN_NT) void k_snap(const uint8_t* __restrict__ aren
     const uint64_t a = doc_off[d], b = doc_off[d + 1];
     int st = ST_OK;
     uint32_t oo = 0, ol = 0;
-    if (b < a || b - a >= (1ull << 30)) st = ST_INVAL;
+    uint32_t fl;
+    if (!snap::doc_flags(flags, opt, d, fl) || b < a || b - a >= (1ull << 30)) st = ST_INVAL;
     else if (c.w == 0) st = ST_MALFORMED;   // (an empty update: yjs throws reading it)
     else {
       const snap::Caps k = snap::caps_of(c.x, c.y, c.z, c.w);
-      st = snap::snapshot_doc(in, c.w, flags, ws + base + ws_off[d], k, oo, ol);
+      st = snap::snapshot_doc(in, c.w, fl, ws + base + ws_off[d], k, oo, ol);
     }
     out_off[d] = base + ws_off[d] + oo;
     out_len[d] = (st == ST_OK || st == snap::ST_PEND) ? ol : 0u;
@@ -462,25 +468,26 @@ static int snap_rc(const char* fn) {
 // phase 1: counts and the scanned workspace offsets (ws_off: n_docs + 1 entries, total at [n_docs];
 // bs: ceil(n / 256) + 1 scratch entries)
 int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                           uint64_t* out_len, int32_t* status, uint8_t* claim, unsigned long long* pay, int again, uint64_t slot_total, hipStream_t s) {
+                           uint64_t* out_len, int32_t* status, uint8_t* claim, unsigned long long* pay, int again, uint64_t slot_total,
+                           const uint8_t* opt, hipStream_t s) {
   if (n_docs == 0) return 0;
   // again == 0: 6 KiB of LDS per document (209 parts); again == 1: 24 KiB for the documents the first launch left.
   // YGM_SNAP_TEXT="KiB" picks another measured size for the first launch.
   if (again) {
     hipLaunchKernelGGL((k_snap_text<24576>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
-                       claim, pay, 1u, slot_total);
+                       claim, pay, 1u, slot_total, opt);
     return snap_rc(__func__);
   }
   const char* env = getenv("YGM_SNAP_TEXT");
   const int lb = env ? atoi(env) : 6;
 #define SNT(L) if (lb == L) { hipLaunchKernelGGL((k_snap_text<L * 1024>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, \
-                                                   out_off, out_len, status, claim, pay, 0u, slot_total); return snap_rc(__func__); }
+                                                   out_off, out_len, status, claim, pay, 0u, slot_total, opt); return snap_rc(__func__); }
   SNT(4) SNT(5) SNT(8)
 #undef SNT
   if (lb == 53) { hipLaunchKernelGGL((k_snap_text<5376>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
-                                     claim, pay, 0u, slot_total); return snap_rc(__func__); }
+                                     claim, pay, 0u, slot_total, opt); return snap_rc(__func__); }
   hipLaunchKernelGGL((k_snap_text<6144>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status, claim,
-                     pay, 0u, slot_total);
+                     pay, 0u, slot_total, opt);
   return snap_rc(__func__);
 }
 int ygm_k_launch_snap_plan(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, void* cnt, uint64_t* ws_off,
@@ -506,20 +513,20 @@ int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s) {
 // dpw_hint: documents per wave when YGM_SNAP_DPW is not set (0: the default 16)
 int ygm_k_launch_snap_w(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
                         uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
-                        uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, hipStream_t s) {
+                        uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, const uint8_t* opt, hipStream_t s) {
   if (n_docs == 0) return 0;
   const char* env = getenv("YGM_SNAP_DPW");
   uint32_t dpw = env ? (uint32_t)atoi(env) : (dpw_hint ? dpw_hint : 16u);
   if (dpw < 1 || dpw > (uint32_t)SN_NT) dpw = 16u;
   const uint32_t g = (n_docs + dpw - 1) / dpw;
   hipLaunchKernelGGL(k_snap, dim3(g), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, (const uint4*)cnt, ws_off, ws, out_off, out_len,
-                     status, payload, dpw, claim, base, pend_list, pend_n);
+                     status, payload, dpw, claim, base, pend_list, pend_n, opt);
   return snap_rc(__func__);
 }
 int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
                       uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
                       uint64_t base, uint32_t* pend_list, unsigned int* pend_n, hipStream_t s) {
-  return ygm_k_launch_snap_w(arena, doc_off, n_docs, flags, cnt, ws_off, ws, out_off, out_len, status, payload, claim, base, pend_list, pend_n, 0u, s);
+  return ygm_k_launch_snap_w(arena, doc_off, n_docs, flags, cnt, ws_off, ws, out_off, out_len, status, payload, claim, base, pend_list, pend_n, 0u, nullptr, s);
 }
 int ygm_k_launch_pend_plan(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, uint64_t* upd_off, uint32_t* doc_upd,
                            hipStream_t s) {

@@ -31,6 +31,18 @@
 // After one transaction on a fresh document every struct is a merge candidate, so the reference's
 // three merge passes (delete-set ranges, afterState, _mergeStructs) reduce to one right-to-left
 // pass per client: mergeability is preserved along a merged run, so maximal runs are unique.
+//
+// Documents created with gc: false (yDocOptions, packages/server/src/types.ts:152-154; per document through
+// onCreateDocument, Hocuspocus.ts:331-344; the Y.Doc constructor, Document.ts:48-49): F_SNAP_NOGC, set per document
+// from its option byte, makes the snapshot encodeStateAsUpdate(applyUpdate(new Y.Doc({gc: false}), u)).  The
+// transaction's cleanup skips tryGcDeleteSet (cleanupTransactions: `if (doc.gc)`), nothing else: a deleted Item keeps its content
+// (a deleted type its ContentType and its children, deleted Items under it), GC structs of the input stay, an Item
+// whose parent is a GC struct still integrates as GC.  Item.mergeWith's `deleted === deleted` then matters for
+// content: two adjacent deleted String / Any / JSON Items merge (pieces, U+FFFD at a cut surrogate pair as for live
+// ones), never with a live neighbour.  The workspace capacities hold: the encoder writes per part its header (<= 21
+// bytes), a length (<= 5), up to two U+FFFD (6) and its delete-set run (<= 10), 42 of the 48 bytes caps_of counts per
+// part, and content bytes that are disjoint slices of the input (<= n) -- the all-live document's bound, which a
+// document with kept deleted content cannot exceed (a deleted Item is written exactly as the live one would be).
 #pragma once
 #include "ygm_v1.hpp"
 
@@ -40,6 +52,14 @@ namespace snap {
 constexpr int ST_UNSUP = 9;   // YGM_EUNSUPPORTED
 constexpr int ST_PEND = 64;   // internal: the output is [state, pendingDs, pending structs] for the merge kernels
 constexpr uint32_t F_SNAP_STATE = 16u;   // YGM_F_SNAP_STATE: a pending document's output is its integrated state
+constexpr uint32_t F_SNAP_NOGC = 32u;    // internal, per document (option bit YGM_DOC_NO_GC): a Y.Doc({gc: false}), no tryGcDeleteSet
+constexpr uint32_t OPT_NO_GC = 1u;       // YGM_DOC_NO_GC: the only bit of a document's option byte (any other: YGM_EINVAL)
+// a document's flags from the batch's and its option byte (opt null: every byte 0); false: a bit outside the options
+YDEV bool doc_flags(uint32_t flags, const uint8_t* opt, uint32_t d, uint32_t& out) {
+  const uint32_t ob = opt ? opt[d] : 0u;
+  out = flags | ((ob & OPT_NO_GC) ? F_SNAP_NOGC : 0u);
+  return (ob & ~OPT_NO_GC) == 0u;
+}
 // a pending document's output: this header, then the three V1 updates back to back (an absent one as the empty update)
 struct PendHdr { uint32_t len[3]; uint32_t magic; };
 constexpr uint32_t PEND_MAGIC = 0x444E4550u;
@@ -604,7 +624,7 @@ struct Doc {
   }
 
   // cleanupTransactions, gc branch (Y@30900 tryGcDeleteSet): deleted items -> ContentDeleted, their
-  // children (ContentType.gc, Y@73900) -> GC structs
+  // children (ContentType.gc, Y@73900) -> GC structs.  Not run for a no-GC document (F_SNAP_NOGC).
   YDEV void gc_item(int32_t x0, bool parent_gcd) {
     uint32_t sp = 0;
     st[sp++] = x0 * 2 + (parent_gcd ? 1 : 0);
@@ -825,7 +845,7 @@ struct Doc {
     parse();
     if (!err) integrate_all();
     if (!err) apply_ds();
-    if (!err) gc_pass();
+    if (!err && !(flags & F_SNAP_NOGC)) gc_pass();   // (doc.gc false: deleted content stays)
     if (!err) merge_pass();
     return err ? 0u : encode();
   }

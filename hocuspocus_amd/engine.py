@@ -28,6 +28,7 @@ STATUS_NAMES = {0: "OK", 1: "EMALFORMED", 2: "ERANGE", 3: "ENONCANON", 4: "ESURR
                 6: "ENOMEM", 7: "EDEVICE", 8: "EINVAL", 9: "EUNSUPPORTED"}
 F_COMPAT_135 = 1
 F_FORCE_SEQ = 2
+DOC_NO_GC = 1   # YGM_DOC_NO_GC: a document's option byte, the document is a Y.Doc({gc: false})
 
 
 class YjsError(Exception):
@@ -72,7 +73,9 @@ EXPORTS = ("ygm_open", "ygm_close", "ygm_merge_v1", "ygm_diff_v1", "ygm_sv_from_
            "ygm_convert_v2_to_v1_device", "ygm_sync_step2_v1", "ygm_sync_step2_v1_device",
            "ygm_merge_v1_device_lens", "ygm_merge_v1_device_lens_async",
            "ygm_diff_shared_v1", "ygm_sync_step2_shared_v1", "ygm_diff_shared_v1_device",
-           "ygm_sync_step2_shared_v1_device")
+           "ygm_sync_step2_shared_v1_device",
+           "ygm_snapshot_opts_v1", "ygm_sync_step2_opts_v1", "ygm_sync_step2_shared_opts_v1",
+           "ygm_snapshot_opts_v1_device", "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device")
 
 
 def lib():
@@ -115,6 +118,15 @@ def lib():
         for f in ("ygm_diff_shared_v1_device", "ygm_sync_step2_shared_v1_device"):
             getattr(L, f).argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
             getattr(L, f).restype = i32
+        L.ygm_snapshot_opts_v1.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
+        L.ygm_sync_step2_opts_v1.argtypes = [vp, vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
+        L.ygm_sync_step2_shared_opts_v1.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u32, ctypes.POINTER(_Result)]
+        L.ygm_snapshot_opts_v1_device.argtypes = [vp, vp, u64, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
+        L.ygm_sync_step2_opts_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
+        L.ygm_sync_step2_shared_opts_v1_device.argtypes = [vp, vp, u64, vp, vp, u32, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
+        for f in ("ygm_snapshot_opts_v1", "ygm_sync_step2_opts_v1", "ygm_sync_step2_shared_opts_v1", "ygm_snapshot_opts_v1_device",
+                  "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device"):
+            getattr(L, f).restype = i32
         L.ygm_merge_v2.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
         L.ygm_diff_v2.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
         for f in ("ygm_sv_from_update_v2", "ygm_convert_v1_to_v2", "ygm_convert_v2_to_v1"):
@@ -155,6 +167,19 @@ def _ptr(a):
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(ctypes.c_void_p)
     return ctypes.c_char_p(a) if a else None
+
+
+def _opts(opts, n):
+    """Per-document option bytes (YGM_DOC_NO_GC) from a bytes-like or a sequence of bools / ints; None: no options."""
+    if opts is None:
+        return None
+    if isinstance(opts, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(bytes(opts), dtype=np.uint8).copy()
+    else:
+        a = np.ascontiguousarray(np.asarray([int(x) for x in opts], dtype=np.int64).astype(np.uint8))
+    if len(a) != n:
+        raise ValueError(f"{len(a)} option bytes for {n} documents")
+    return a
 
 
 TAIL_PAD = 64   # readable bytes the kernels need after a device arena (include/ygm.h, "Tail padding")
@@ -375,37 +400,53 @@ class Engine:
         return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
 
     # ------------------------------------------------------------ yjs-shaped single calls
-    def snapshot_batch(self, updates):
+    def snapshot_batch(self, updates, opts=None):
         """Doc-normalized snapshots: Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), u)) per update
-        (ygm_snapshot_v1) -> list of (status, bytes | None); UNSUPPORTED marks documents outside the envelope."""
+        (ygm_snapshot_v1) -> list of (status, bytes | None); UNSUPPORTED marks documents outside the envelope.
+        opts: one option per update (bytes-like, or bools / ints): DOC_NO_GC / True marks a document created with
+        gc: false, whose snapshot is that of new Y.Doc({gc: false}) -- deleted content kept (ygm_snapshot_opts_v1)."""
         arena, off = _pack([bytes(u) for u in updates])
         res = _Result()
-        st = lib().ygm_snapshot_v1(self._ctx, arena or None, _ptr(off), len(updates), ctypes.byref(res))
+        o = _opts(opts, len(updates))
+        if o is None:
+            st = lib().ygm_snapshot_v1(self._ctx, arena or None, _ptr(off), len(updates), ctypes.byref(res))
+        else:
+            st = lib().ygm_snapshot_opts_v1(self._ctx, arena or None, _ptr(off), _ptr(o) if len(o) else None, len(updates), ctypes.byref(res))
         if st != OK:
             raise YjsError(st)
         return self._unpack(res)
 
-    def sync_step2_batch(self, states, svs):
+    def sync_step2_batch(self, states, svs, opts=None):
         """SyncStep2 payloads of stored documents: Y.encodeStateAsUpdate(doc, sv) for doc = Y.applyUpdate(new Y.Doc(),
         state) (MessageReceiver.ts:137-138; ygm_sync_step2_v1) -> list of (status, bytes | None); UNSUPPORTED marks
-        documents outside the snapshot envelope."""
+        documents outside the snapshot envelope.  opts as snapshot_batch, one per state (ygm_sync_step2_opts_v1)."""
         sa, so = _pack([bytes(s) for s in states])
         va, vo = _pack([bytes(v) for v in svs])
         res = _Result()
-        st = lib().ygm_sync_step2_v1(self._ctx, sa or None, _ptr(so), va or None, _ptr(vo), len(states), ctypes.byref(res))
+        o = _opts(opts, len(states))
+        if o is None:
+            st = lib().ygm_sync_step2_v1(self._ctx, sa or None, _ptr(so), va or None, _ptr(vo), len(states), ctypes.byref(res))
+        else:
+            st = lib().ygm_sync_step2_opts_v1(self._ctx, sa or None, _ptr(so), _ptr(o) if len(o) else None, va or None, _ptr(vo),
+                                              len(states), ctypes.byref(res))
         if st != OK:
             raise YjsError(st)
         return self._unpack(res)
 
-    def _shared(self, fn, states, ask_state, svs):
+    def _shared(self, fn, states, ask_state, svs, opts=None):
         if len(ask_state) != len(svs):
             raise ValueError("one state index per state vector")
         sa, so = _pack([bytes(s) for s in states])
         va, vo = _pack([bytes(v) for v in svs])
         ask = np.ascontiguousarray(np.asarray(ask_state, dtype=np.int64).astype(np.uint32))
         res = _Result()
-        st = getattr(lib(), fn)(self._ctx, sa or None, _ptr(so), len(states), va or None, _ptr(vo),
-                                _ptr(ask) if len(ask) else None, len(ask), ctypes.byref(res))
+        o = _opts(opts, len(states))
+        if o is None:
+            st = getattr(lib(), fn)(self._ctx, sa or None, _ptr(so), len(states), va or None, _ptr(vo),
+                                    _ptr(ask) if len(ask) else None, len(ask), ctypes.byref(res))
+        else:
+            st = getattr(lib(), fn)(self._ctx, sa or None, _ptr(so), _ptr(o) if len(o) else None, len(states), va or None, _ptr(vo),
+                                    _ptr(ask) if len(ask) else None, len(ask), ctypes.byref(res))
         if st != OK:
             raise YjsError(st)
         return self._unpack(res)
@@ -416,12 +457,15 @@ class Engine:
         len(updates); anything else raises YjsError(EINVAL).  -> list of (status, bytes | None) per ask."""
         return self._shared("ygm_diff_shared_v1", updates, ask_doc, svs)
 
-    def sync_step2_shared_batch(self, states, ask_state, svs):
+    def sync_step2_shared_batch(self, states, ask_state, svs, opts=None):
         """SyncStep2 payloads of a reconnect storm (ygm_sync_step2_shared_v1): ask a is answered from
         states[ask_state[a]] with svs[a], byte for byte what sync_step2_batch gives for that pair, but every state
         is uploaded and snapshotted once however many asks name it.  ask_state as ask_doc in
-        diff_update_shared_batch.  -> list of (status, bytes | None) per ask."""
-        return self._shared("ygm_sync_step2_shared_v1", states, ask_state, svs)
+        diff_update_shared_batch.  opts as snapshot_batch, one per state: a state's asks are all answered from its
+        snapshot, so from its option (ygm_sync_step2_shared_opts_v1).  -> list of (status, bytes | None) per ask."""
+        if opts is None:
+            return self._shared("ygm_sync_step2_shared_v1", states, ask_state, svs)
+        return self._shared("ygm_sync_step2_shared_opts_v1", states, ask_state, svs, opts)
 
     def contains_batch(self, states, updates):
         """Read-only SyncStep2: Y.snapshotContainsUpdate(Y.snapshot(doc), update) per pair, `states` being the
@@ -434,10 +478,15 @@ class Engine:
             raise YjsError(st)
         return [(s, None if s != OK else b == b"\x01") for s, b in self._unpack(res)]
 
-    def snapshot_device(self, d_arena, arena_bytes, d_doc_off, n_docs, stream=0) -> "DeviceResult":
+    def snapshot_device(self, d_arena, arena_bytes, d_doc_off, n_docs, stream=0, d_doc_opt=0) -> "DeviceResult":
+        """Device-resident snapshot batch; d_doc_opt: a device pointer / tensor of n_docs option bytes (0: none)."""
         r = _DevResult()
-        st = lib().ygm_snapshot_v1_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off), n_docs,
-                                          stream or None, ctypes.byref(r))
+        if d_doc_opt is None or (not hasattr(d_doc_opt, "data_ptr") and not d_doc_opt):
+            st = lib().ygm_snapshot_v1_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off), n_docs,
+                                              stream or None, ctypes.byref(r))
+        else:
+            st = lib().ygm_snapshot_opts_v1_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off),
+                                                   _dptr(d_doc_opt, n_docs), n_docs, stream or None, ctypes.byref(r))
         if st != OK:
             raise YjsError(st)
         return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)

@@ -70,6 +70,20 @@ class ShardedEngine:
     def encode_state_vector_from_update_batch(self, names, updates):
         return self._run(names, [updates], lambda e, u: e.encode_state_vector_from_update_batch(u))
 
+    def snapshot_batch(self, names, updates, opts=None):
+        """Engine.snapshot_batch by shard; opts (one per document, DOC_NO_GC / True: a gc: false document) travel with
+        their documents."""
+        if opts is None:
+            return self._run(names, [updates], lambda e, u: e.snapshot_batch(u))
+        return self._run(names, [updates, list(bytes(opts) if isinstance(opts, (bytes, bytearray, memoryview)) else opts)],
+                         lambda e, u, o: e.snapshot_batch(u, o))
+
+    def sync_step2_batch(self, names, states, svs, opts=None):
+        if opts is None:
+            return self._run(names, [states, svs], lambda e, s, v: e.sync_step2_batch(s, v))
+        return self._run(names, [states, svs, list(bytes(opts) if isinstance(opts, (bytes, bytearray, memoryview)) else opts)],
+                         lambda e, s, v, o: e.sync_step2_batch(s, v, o))
+
     def close(self):
         self._pool.shutdown()
         for e in self.engines:

@@ -131,6 +131,23 @@ int ygm_sv_from_update_v1(ygm_ctx *ctx, const uint8_t *arena, const uint64_t *do
  * (ContentDoc) are integrated like any one-clock content.  Documents outside the envelope (repeated client
  * blocks, overlapping structs) carry YGM_EUNSUPPORTED. */
 int ygm_snapshot_v1(ygm_ctx *ctx, const uint8_t *arena, const uint64_t *doc_off, uint32_t n_docs, ygm_result *out);
+
+/* ---- per-document options: documents created with gc: false -----------------
+ * The reference lets a deployment switch Yjs garbage collection off, globally (yDocOptions { gc, gcFilter },
+ * packages/server/src/types.ts:152-154) or per document (onCreateDocument's yDocOptions spread over the global
+ * ones, packages/server/src/Hocuspocus.ts:331-344); extension-database then stores Y.encodeStateAsUpdate of that
+ * live document with its deleted Items and their content (packages/extension-database/src/Database.ts:55-60).
+ * The *_opts_v1 forms take one option byte per document (doc_opt / state_opt, n_docs bytes; NULL: every byte 0,
+ * the forms above, byte for byte).  Bit 0 is YGM_DOC_NO_GC; a byte with any other bit set gives that document
+ * YGM_EINVAL and nothing else (its neighbours are unaffected).  A gcFilter predicate cannot be expressed. */
+#define YGM_DOC_NO_GC 1u   /* per-document option byte: the document is a Y.Doc({gc:false}) */
+/* ygm_snapshot_v1 with options: a YGM_DOC_NO_GC document's snapshot is
+ * Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc({gc: false}), update)) -- tryGcDeleteSet does not run: deleted Items
+ * keep their content (a deleted type its children), adjacent deleted String / Any / JSON Items merge with each
+ * other; integration, the delete set, pending structs and the merge pass are as in ygm_snapshot_v1
+ * (Hocuspocus.ts:331-344, types.ts:152-154, Database.ts:55-60). */
+int ygm_snapshot_opts_v1(ygm_ctx *ctx, const uint8_t *arena, const uint64_t *doc_off, const uint8_t *doc_opt,
+                         uint32_t n_docs, ygm_result *out);
 /* Read-only SyncStep2: Y.snapshotContainsUpdate(Y.snapshot(doc), update) per document
  * (packages/server/src/MessageReceiver.ts:156-179; yjs 13.6 snapshotContainsUpdate).  states: each
  * document's state (any update: its Y.snapshot view -- the store's integrated part, without pending structs or
@@ -139,6 +156,8 @@ int ygm_snapshot_v1(ygm_ctx *ctx, const uint8_t *arena, const uint64_t *doc_off,
  * server acks with SyncStatus true), 0 = new content (SyncStatus false). */
 int ygm_contains_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *updates,
                     const uint64_t *update_off, uint32_t n_docs, ygm_result *out);
+/* (ygm_contains_v1 has no options form: Y.snapshot(doc) is a state vector and a delete set, and both are the same
+ * with or without garbage collection, so the answer for a gc: false document is the one above.) */
 /* SyncStep2 payload of a stored document: Y.encodeStateAsUpdate(doc, sv) for doc = Y.applyUpdate(new Y.Doc(), state)
  * -- what the reference sends in reply to a SyncStep1 (packages/server/src/MessageReceiver.ts:137-138) for a
  * document loaded from stored bytes (extension-database Database.ts:44-50).  Computed as the doc-normalized
@@ -150,6 +169,13 @@ int ygm_contains_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_o
  * carries YGM_EUNSUPPORTED (the caller names it and keeps its yjs path). */
 int ygm_sync_step2_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *sv_arena,
                       const uint64_t *sv_off, uint32_t n_docs, ygm_result *out);
+/* ygm_sync_step2_v1 with options: for a YGM_DOC_NO_GC state the reply is Y.encodeStateAsUpdate(doc, sv) of the
+ * uncollected document, doc = Y.applyUpdate(new Y.Doc({gc: false}), state) -- the deleted Items are sent with their
+ * content, as the reference's live gc: false document sends them (Hocuspocus.ts:331-344, types.ts:152-154; the stored
+ * bytes of Database.ts:55-60).  Computed as diffUpdate of the no-GC snapshot with the kept parentSub bit; a state
+ * that leaves pending parts takes the three-way merge, of which only the state part depends on the option. */
+int ygm_sync_step2_opts_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *state_opt,
+                           const uint8_t *sv_arena, const uint64_t *sv_off, uint32_t n_docs, ygm_result *out);
 
 /* ---- shared-state forms: many state vectors answered from one state ---------
  * A reconnect storm sends many SyncStep1 messages for one document.  These forms take n_docs states and n_asks
@@ -173,6 +199,13 @@ int ygm_diff_shared_v1(ygm_ctx *ctx, const uint8_t *arena, const uint64_t *doc_o
 int ygm_sync_step2_shared_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, uint32_t n_states,
                              const uint8_t *sv_arena, const uint64_t *sv_off, const uint32_t *ask_state, uint32_t n_asks,
                              ygm_result *out);
+/* ygm_sync_step2_shared_v1 with options: state_opt holds one byte per state (n_states), and every ask of a state is
+ * answered from that state's snapshot, so from its option (Hocuspocus.ts:331-344, types.ts:152-154,
+ * Database.ts:55-60); a bad byte's YGM_EINVAL is the status of each of the state's asks.  A state split over several
+ * chunks carries its byte into each of them. */
+int ygm_sync_step2_shared_opts_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *state_opt,
+                                  uint32_t n_states, const uint8_t *sv_arena, const uint64_t *sv_off,
+                                  const uint32_t *ask_state, uint32_t n_asks, ygm_result *out);
 
 /* ---- update format V2 ------------------------------------
  * The same operations over yjs's column-encoded update format V2 (UpdateEncoderV2 / UpdateDecoderV2,
@@ -258,12 +291,20 @@ int ygm_sv_from_update_v1_device(ygm_ctx *ctx, const uint8_t *d_arena, uint64_t 
 
 int ygm_snapshot_v1_device(ygm_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_doc_off,
                            uint32_t n_docs, void *stream, ygm_device_result *out);
+/* Device-resident options forms: d_doc_opt / d_state_opt are device pointers to the option bytes (one per document
+ * or state; NULL: none set), as doc_opt / state_opt of the host forms (Hocuspocus.ts:331-344, types.ts:152-154,
+ * Database.ts:55-60). */
+int ygm_snapshot_opts_v1_device(ygm_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_doc_off,
+                                const uint8_t *d_doc_opt, uint32_t n_docs, void *stream, ygm_device_result *out);
 
 int ygm_contains_v1_device(ygm_ctx *ctx, const uint8_t *d_states, const uint64_t *d_state_off, const uint8_t *d_updates,
                            const uint64_t *d_update_off, uint32_t n_docs, void *stream, ygm_device_result *out);
 int ygm_sync_step2_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                              const uint8_t *d_sv_arena, const uint64_t *d_sv_off, uint32_t n_docs, void *stream,
                              ygm_device_result *out);
+int ygm_sync_step2_opts_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
+                                  const uint8_t *d_state_opt, const uint8_t *d_sv_arena, const uint64_t *d_sv_off,
+                                  uint32_t n_docs, void *stream, ygm_device_result *out);
 
 /* Shared-state forms, device-resident: d_ask_doc (u32, n_asks entries) as ask_doc above; d_sv_off has n_asks + 1
  * entries; results are indexed by ask.  Ask a's slot is placed from the exclusive scan, over asks, of each ask's
@@ -276,6 +317,10 @@ int ygm_sync_step2_shared_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint6
                                     const uint64_t *d_state_off, uint32_t n_states, const uint8_t *d_sv_arena,
                                     const uint64_t *d_sv_off, const uint32_t *d_ask_state, uint32_t n_asks, void *stream,
                                     ygm_device_result *out);
+int ygm_sync_step2_shared_opts_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes,
+                                         const uint64_t *d_state_off, const uint8_t *d_state_opt, uint32_t n_states,
+                                         const uint8_t *d_sv_arena, const uint64_t *d_sv_off, const uint32_t *d_ask_state,
+                                         uint32_t n_asks, void *stream, ygm_device_result *out);
 
 /* update V2, device-resident (outputs packed in document order: off[d] increasing) */
 int ygm_merge_v2_device(ygm_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_upd_off,

@@ -49,6 +49,7 @@ struct Job {
   uint32_t sleep_ms; double t_start, t_end;   /* op 99 */
   uint8_t *arena; uint64_t *off; uint32_t *docs; uint32_t n_upd, n_docs;
   uint8_t *sv; uint64_t *sv_off;
+  uint8_t *opt;   /* per-document (per-state) option bytes, YGM_DOC_NO_GC; NULL: the plain entry points */
   int rc;
   /* copied results */
   uint8_t *data; uint64_t *roff, *rlen; int32_t *status; uint32_t rn;
@@ -248,6 +249,18 @@ static int get_bytes(napi_env env, napi_value v, void **out, size_t *len) {
   return 0;
 }
 
+/* the optional trailing option-bytes argument (Uint8Array / Buffer, one byte per document or state: YGM_DOC_NO_GC for
+   documents created with gc: false, Hocuspocus.ts:331-344): absent / undefined / null leaves j->opt NULL; -1: not n bytes */
+static int get_opts(napi_env env, size_t argc, napi_value *argv, size_t at, uint32_t n, uint8_t **out) {
+  napi_valuetype t = napi_undefined;
+  *out = NULL;
+  if (argc <= at || napi_typeof(env, argv[at], &t) != napi_ok || t == napi_undefined || t == napi_null) return 0;
+  size_t on = 0;
+  if (get_bytes(env, argv[at], (void **)out, &on)) { *out = NULL; return -1; }
+  if (on != n) { free(*out); *out = NULL; return -1; }
+  return 0;
+}
+
 static uint64_t *lens_to_off(const uint32_t *lens, uint32_t n) {
   uint64_t *off = (uint64_t *)malloc(sizeof(uint64_t) * (n + 1));
   off[0] = 0;
@@ -266,10 +279,13 @@ static void job_execute(Job *j) {
   }
   if (j->op == 0) j->rc = ygm_merge_v1(j->h->ctx, j->arena, j->off, j->docs, j->n_upd, j->n_docs, &r);
   else if (j->op == 1) j->rc = ygm_diff_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
+  else if (j->op == 3 && j->opt) j->rc = ygm_snapshot_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->n_docs, &r);
   else if (j->op == 3) j->rc = ygm_snapshot_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   else if (j->op == 4) j->rc = ygm_contains_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
+  else if (j->op == 5 && j->opt) j->rc = ygm_sync_step2_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->sv, j->sv_off, j->n_docs, &r);
   else if (j->op == 5) j->rc = ygm_sync_step2_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
   else if (j->op == 6) j->rc = ygm_diff_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, &r);
+  else if (j->op == 7 && j->opt) j->rc = ygm_sync_step2_shared_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, &r);
   else if (j->op == 7) j->rc = ygm_sync_step2_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, &r);
   else if (j->op == 10) j->rc = ygm_merge_v2(j->h->ctx, j->arena, j->off, j->docs, j->n_upd, j->n_docs, &r);
   else if (j->op == 11) j->rc = ygm_diff_v2(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
@@ -295,7 +311,7 @@ static void job_execute(Job *j) {
 
 static void job_free(Job *j) {
   if (!j->arena_borrowed) free(j->arena);
-  free(j->off); free(j->docs); free(j->sv); free(j->sv_off);
+  free(j->off); free(j->docs); free(j->sv); free(j->sv_off); free(j->opt);
   free(j->data); free(j->roff); free(j->rlen); free(j->status);
   free(j);
 }
@@ -426,7 +442,7 @@ static napi_value js_merge(napi_env env, napi_callback_info info) {
 
 /* diffMany(h, arena, lens, svArena, svLens) */
 static napi_value js_diff(napi_env env, napi_callback_info info) {
-  size_t argc = 5; napi_value argv[5];
+  size_t argc = 6; napi_value argv[6];   /* (step2Many: an optional sixth argument, the states' option bytes) */
   void *opd = NULL;
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
   if (argc < 5) { napi_throw_type_error(env, NULL, "diffMany(handle, arena, lens, svArena, svLens)"); return NULL; }
@@ -443,6 +459,7 @@ static napi_value js_diff(napi_env env, napi_callback_info info) {
   j->sv_off = lens_to_off((const uint32_t *)slens, j->n_docs);
   free(lens); free(slens);
   if (j->off[j->n_docs] != an || j->sv_off[j->n_docs] != sn) { job_free(j); napi_throw_range_error(env, NULL, "diffMany: lengths do not match arenas"); return NULL; }
+  if (j->op == 5 && get_opts(env, argc, argv, 5, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "step2Many: one option byte per state"); return NULL; }
   return submit(env, j, argv[0]);
 }
 
@@ -490,7 +507,7 @@ static napi_value js_contains(napi_env env, napi_callback_info info) {
 /* diffShared / step2Shared(h, states, stateLens, svArena, svLens, askState:Uint32Array): one result per ask (state
    vector), ask a answered from state askState[a] (non-decreasing); n_docs = states, n_upd = asks, docs = askState */
 static napi_value js_shared(napi_env env, napi_callback_info info) {
-  size_t argc = 6; napi_value argv[6];
+  size_t argc = 7; napi_value argv[7];   /* (step2Shared: an optional seventh argument, one option byte per state) */
   void *opd = NULL;
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
   if (argc < 6) { napi_throw_type_error(env, NULL, "step2Shared(handle, states, stateLens, svArena, svLens, askState)"); return NULL; }
@@ -508,12 +525,14 @@ static napi_value js_shared(napi_env env, napi_callback_info info) {
   j->sv_off = lens_to_off((const uint32_t *)slens, j->n_upd);
   free(lens); free(slens);
   if (j->off[j->n_docs] != an || j->sv_off[j->n_upd] != sn) { job_free(j); napi_throw_range_error(env, NULL, "step2Shared: lengths do not match arenas"); return NULL; }
+  if (j->op == 7 && get_opts(env, argc, argv, 6, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "step2Shared: one option byte per state"); return NULL; }
   return submit(env, j, argv[0]);
 }
 
-/* snapshotMany(h, arena, lens): Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), u)) per update */
+/* snapshotMany(h, arena, lens[, opts]): Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), u)) per update; opts: one byte
+   per update, YGM_DOC_NO_GC: new Y.Doc({gc: false}) for that one (ygm_snapshot_opts_v1) */
 static napi_value js_snapshot(napi_env env, napi_callback_info info) {
-  size_t argc = 3; napi_value argv[3];
+  size_t argc = 4; napi_value argv[4];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 3) { napi_throw_type_error(env, NULL, "snapshotMany(handle, arena, lens)"); return NULL; }
   Handle *h = get_handle(env, argv[0]);
@@ -527,6 +546,7 @@ static napi_value js_snapshot(napi_env env, napi_callback_info info) {
   j->off = lens_to_off((const uint32_t *)lens, j->n_docs);
   free(lens);
   if (j->off[j->n_docs] != an) { job_free(j); napi_throw_range_error(env, NULL, "snapshotMany: sum(lens) != arena length"); return NULL; }
+  if (get_opts(env, argc, argv, 3, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "snapshotMany: one option byte per update"); return NULL; }
   return submit(env, j, argv[0]);
 }
 

@@ -7,6 +7,12 @@ export declare class YgmError extends Error {
   status: number
 }
 
+/** A document's yDocOptions where the engine needs them: gc false marks a document created with { gc: false }
+ *  (packages/server/src/types.ts:152-154, Hocuspocus.ts:331-344), whose snapshots and SyncStep2 replies keep deleted content. */
+export interface DocOptions { gc?: boolean }
+/** one option per document or state: an option byte (1 = no-GC), true (no-GC), or DocOptions; or the bytes themselves */
+export type DocOptionList = ArrayLike<number | boolean | DocOptions> | Uint8Array
+
 export interface GpuEngineOptions { device?: number; compat135?: boolean; batchWindowMs?: number; maxBatchDocs?: number }
 
 export declare class GpuEngine {
@@ -18,12 +24,13 @@ export declare class GpuEngine {
   diffMany (states: Uint8Array[], svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   stateVectorsMany (states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   /** SyncStep2 payloads of stored documents: Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), state), sv) per pair */
-  step2Many (states: Uint8Array[], svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  step2Many (states: Uint8Array[], svs: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** Many state vectors answered from shared states (a reconnect storm): ask a is answered from states[askState[a]] with
    *  svs[a]; one result per ask, in caller order, equal to diffMany / step2Many of the pair.  Each state is uploaded
    *  (step2Shared: and snapshotted) once.  An askState entry that names no state rejects with YgmError EINVAL. */
   diffShared (states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
-  step2Shared (states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  /** opts: one option per state; all of a state's asks are answered with it */
+  step2Shared (states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** update format V2: Y.mergeUpdatesV2 / Y.diffUpdateV2 / Y.encodeStateVectorFromUpdateV2 / Y.convertUpdateFormat* (yjs 13.6) */
   mergeManyV2 (docs: Uint8Array[][]): Promise<(Uint8Array | YgmError)[]>
   diffManyV2 (states: Uint8Array[], stateVectors: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
@@ -31,8 +38,9 @@ export declare class GpuEngine {
   convertManyV1ToV2 (updates: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   convertManyV2ToV1 (updates: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   /** Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), update)) (doc-normalized snapshot, SURVEY.md §8f-1) */
-  snapshot (update: Uint8Array): Promise<Uint8Array>
-  snapshotMany (states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  /** { gc: false }: Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc({ gc: false }), update)); both kinds share a batch window */
+  snapshot (update: Uint8Array, opts?: DocOptions): Promise<Uint8Array>
+  snapshotMany (states: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** Y.snapshotContainsUpdate(Y.snapshot(doc), update), states being normalized (snapshotMany) states */
   containsMany (states: Uint8Array[], updates: Uint8Array[]): Promise<(boolean | YgmError)[]>
   /** the context's counters (ygm_stats_t), camel-cased: calls, docs, kernelMs, h2dMs, d2hMs, hostSyncs, docsPending,
@@ -55,12 +63,12 @@ export declare class GpuEnginePool {
   mergeMany (names: string[], docs: Uint8Array[][]): Promise<(Uint8Array | YgmError)[]>
   diffMany (names: string[], states: Uint8Array[], svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   stateVectorsMany (names: string[], states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
-  step2Many (names: string[], states: Uint8Array[], svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  step2Many (names: string[], states: Uint8Array[], svs: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** the shared-state forms, names[i] naming states[i]: states go to their fnv1a64(name) shard, results in ask order */
   diffShared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
-  step2Shared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
-  snapshot (update: Uint8Array, documentName?: string): Promise<Uint8Array>
-  snapshotMany (names: string[], states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  step2Shared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, svs: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
+  snapshot (update: Uint8Array, documentName?: string, opts?: DocOptions): Promise<Uint8Array>
+  snapshotMany (names: string[], states: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   containsMany (names: string[], states: Uint8Array[], updates: Uint8Array[]): Promise<(boolean | YgmError)[]>
   stats (): Record<string, number>[]
   /** node-wide totals: every per-device counter summed over the pool, plus `devices` */
@@ -70,7 +78,9 @@ export declare class GpuEnginePool {
 
 /** Batched SyncStep1 -> SyncStep2 responder (SURVEY.md §8f-2; src/sync.js). */
 export declare class SyncResponder {
-  constructor (opts: { engine: GpuEngine | GpuEnginePool, getState: (documentName: string) => Promise<Uint8Array | Uint8Array[] | null> })
+  /** getDocOptions: a document's yDocOptions ({ gc: false }: its replies carry the deleted Items with their content); without it every document is garbage-collected */
+  constructor (opts: { engine: GpuEngine | GpuEnginePool, getState: (documentName: string) => Promise<Uint8Array | Uint8Array[] | null>,
+    getDocOptions?: (documentName: string) => DocOptions | null | undefined })
   /** per message: [Step2 reply, server Step1] for SyncStep1, null for other messages, an Error if malformed */
   answerMany (messages: Uint8Array[], opts?: { path?: 'connection' | 'reply' | 'none' }): Promise<(Uint8Array[] | Error | null)[]>
   /** read-only connections' SyncStep2 (MessageReceiver.ts:156-179): the SyncStatus(contained) frame per message */
@@ -81,6 +91,7 @@ export declare class SyncResponder {
  * remote SyncStep1 replies as GPU batches, with the reference's channel names and message framing. */
 export declare class RedisFanout {
   constructor (opts: { engine: GpuEngine | GpuEnginePool, getState: (documentName: string) => Promise<Uint8Array | Uint8Array[] | null>,
+    getDocOptions?: (documentName: string) => DocOptions | null | undefined,
     publish: (channel: string, message: Buffer) => any, identifier?: string, prefix?: string, windowMs?: number })
   identifier: string
   redisTransactionOrigin: string
@@ -110,6 +121,10 @@ export interface GpuMergeConfiguration extends GpuEngineOptions {
   normalize?: boolean
   /** merged states over this many bytes are stored as the bare merge (the snapshot kernel runs one thread per document); default 32768 */
   normalizeMaxBytes?: number
+  /** garbage collection of the normalized snapshot and of the responder's / fan-out's replies: 'document' (default) follows
+   *  each live document's own `gc` option (yDocOptions), true / false force it.  A custom gcFilter cannot be reproduced:
+   *  use normalize: false with one. */
+  gc?: 'document' | boolean
 }
 
 export declare class GpuMerge implements Extension {

@@ -114,6 +114,17 @@ function packBlobs (blobs) {
   return { arena, lens }
 }
 
+/** YGM_DOC_NO_GC: the option byte of a document created with gc: false (yDocOptions, Hocuspocus.ts:331-344) */
+const DOC_NO_GC = 1
+// per-document options -> option bytes, or undefined when none is set (the plain native entry points): an entry is an
+// option byte, `true` (no-GC), or { gc: boolean } as in yDocOptions; a Uint8Array is taken as it is
+function optBytes (opts, n) {
+  if (opts === undefined || opts === null) return undefined
+  if (opts.length !== n) throw new YgmError(8, 'one option per document')
+  const out = opts instanceof Uint8Array ? opts : Uint8Array.from(opts, o => typeof o === 'number' ? o : o === true ? DOC_NO_GC : o && o.gc === false ? DOC_NO_GC : 0)
+  return out.some(b => b !== 0) ? out : undefined
+}
+
 class GpuEngine {
   /**
    * @param {{device?: number, compat135?: boolean, batchWindowMs?: number, maxBatchDocs?: number}} [opts]
@@ -150,7 +161,12 @@ class GpuEngine {
       }
       if (op === 'diff' || op === 'contains' || op === 'diffV2' || op === 'step2') {
         const u = packBlobs(jobs.map(j => j[0])); const s = packBlobs(jobs.map(j => j[1]))
-        return ({ diff: a.diffMany, contains: a.containsMany, diffV2: a.diffManyV2, step2: a.step2Many })[op](this.handle, u.arena, u.lens, s.arena, s.lens)
+        if (op === 'step2') return a.step2Many(this.handle, u.arena, u.lens, s.arena, s.lens, optBytes(jobs.map(j => j[2] || 0), jobs.length))
+        return ({ diff: a.diffMany, contains: a.containsMany, diffV2: a.diffManyV2 })[op](this.handle, u.arena, u.lens, s.arena, s.lens)
+      }
+      if (op === 'snapshot') {   // a job is an update, or { update, opt } for one with an option byte: both kinds share a window
+        const u = packBlobs(jobs.map(j => j instanceof Uint8Array ? j : j.update))
+        return a.snapshotMany(this.handle, u.arena, u.lens, optBytes(jobs.map(j => j instanceof Uint8Array ? 0 : j.opt), jobs.length))
       }
       const u = packBlobs(jobs)
       const unary = { snapshot: a.snapshotMany, sv: a.svMany, svV2: a.svManyV2, v1ToV2: a.convertManyV1ToV2, v2ToV1: a.convertManyV2ToV1 }
@@ -169,8 +185,12 @@ class GpuEngine {
   diffUpdate (update, sv) { return this.batchers.diff.push([update, sv]) }
   /** Y.encodeStateVectorFromUpdate(update) */
   encodeStateVectorFromUpdate (update) { return this.batchers.sv.push(update) }
-  /** Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), update)): the doc-normalized snapshot (GC'd, merged) */
-  snapshot (update) { return this.batchers.snapshot.push(update) }
+  /** Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), update)): the doc-normalized snapshot (GC'd, merged);
+   *  { gc: false }: of new Y.Doc({ gc: false }) -- deleted content kept, as a document created with that option stores it */
+  snapshot (update, { gc } = {}) {
+    const u = update instanceof Uint8Array ? update : Uint8Array.from(update)
+    return this.batchers.snapshot.push(gc === false ? { update: u, opt: DOC_NO_GC } : u)
+  }
 
   /** explicit batches (sync responders, bulk snapshot jobs) */
   async mergeMany (docs) { const r = await this._run('merge', docs); return unpack(r) }
@@ -178,16 +198,21 @@ class GpuEngine {
   /** SyncStep2 payloads of stored documents: Y.encodeStateAsUpdate(doc, sv) of doc = Y.applyUpdate(new Y.Doc(), state)
    *  (MessageReceiver.ts:137-138) -- the snapshot, then a diff keeping each struct's parentSub bit; EUNSUPPORTED
    *  outside the snapshot envelope */
-  async step2Many (states, svs) { const r = await this._run('step2', states.map((s, i) => [s, svs[i]])); return unpack(r) }
+  async step2Many (states, svs, opts) {
+    const o = optBytes(opts, states.length)
+    const r = await this._run('step2', states.map((s, i) => [s, svs[i], o ? o[i] : 0]))
+    return unpack(r)
+  }
   /**
    * Many state vectors answered from shared states (a reconnect storm): ask a is answered from states[askState[a]]
    * with svs[a].  diffShared: Y.diffUpdate per ask; step2Shared: the SyncStep2 payload per ask, byte for byte what
    * step2Many gives for the pair -- but every state is uploaded and snapshotted once, however many asks name it.
    * The asks are sorted by state here (the native call takes them non-decreasing); results come back in caller order.
+   * step2Shared's opts: one option per state (as snapshotMany's), which all of the state's asks are answered with.
    */
   diffShared (states, askState, svs) { return this._shared('diffShared', states, askState, svs) }
-  step2Shared (states, askState, svs) { return this._shared('step2Shared', states, askState, svs) }
-  async _shared (op, states, askState, svs) {
+  step2Shared (states, askState, svs, opts) { return this._shared('step2Shared', states, askState, svs, optBytes(opts, states.length)) }
+  async _shared (op, states, askState, svs, opt) {
     const n = svs.length
     if (askState.length !== n) throw new YgmError(8, 'one state index per state vector')
     for (let a = 0; a < n; a++) {
@@ -196,7 +221,7 @@ class GpuEngine {
     const order = Array.from({ length: n }, (_, a) => a).sort((x, y) => askState[x] - askState[y] || x - y)
     const run = () => {
       const u = packBlobs(states); const v = packBlobs(order.map(a => svs[a]))
-      return loadAddon()[op](this.handle, u.arena, u.lens, v.arena, v.lens, Uint32Array.from(order, a => askState[a]))
+      return loadAddon()[op](this.handle, u.arena, u.lens, v.arena, v.lens, Uint32Array.from(order, a => askState[a]), opt)
     }
     const p = this.chain.then(run, run)
     this.chain = p.catch(() => {})
@@ -207,7 +232,13 @@ class GpuEngine {
   }
 
   async stateVectorsMany (states) { const r = await this._run('sv', states); return unpack(r) }
-  async snapshotMany (states) { const r = await this._run('snapshot', states); return unpack(r) }
+  /** snapshots as an explicit batch; opts: one option per state -- an option byte, true, or { gc: false } for a
+   *  document created with gc: false (both kinds in one batch) */
+  async snapshotMany (states, opts) {
+    const o = optBytes(opts, states.length)
+    const r = await this._run('snapshot', o ? states.map((s, i) => ({ update: s, opt: o[i] })) : states)
+    return unpack(r)
+  }
   /** Y.snapshotContainsUpdate(Y.snapshot(doc), update) per pair, `states` being normalized (snapshotMany) states */
   async containsMany (states, updates) {
     const r = await this._run('contains', states.map((s, i) => [s, updates[i]]))
@@ -263,7 +294,7 @@ class GpuEnginePool {
   }
   diffUpdate (update, sv, documentName = '') { return this.engineFor(documentName).diffUpdate(update, sv) }
   encodeStateVectorFromUpdate (update, documentName = '') { return this.engineFor(documentName).encodeStateVectorFromUpdate(update) }
-  snapshot (update, documentName = '') { return this.engineFor(documentName).snapshot(update) }
+  snapshot (update, documentName = '', opts) { return this.engineFor(documentName).snapshot(update, opts) }
 
   async _many (names, cols, run) {
     const parts = this.engines.map(() => [])
@@ -279,19 +310,23 @@ class GpuEnginePool {
 
   mergeMany (names, docs) { return this._many(names, [docs], (e, d) => e.mergeMany(d)) }
   diffMany (names, states, svs) { return this._many(names, [states, svs], (e, a, b) => e.diffMany(a, b)) }
-  step2Many (names, states, svs) { return this._many(names, [states, svs], (e, a, b) => e.step2Many(a, b)) }
+  step2Many (names, states, svs, opts) {
+    if (!opts) return this._many(names, [states, svs], (e, a, b) => e.step2Many(a, b))
+    return this._many(names, [states, svs, Array.from(opts)], (e, a, b, o) => e.step2Many(a, b, o))
+  }
   /**
    * The shared-state forms with one name per state: states go to their fnv1a64(name) shard, each shard's asks are
    * re-indexed to its own states, the shards run concurrently and the results return in caller (ask) order.
    */
   diffShared (names, states, askState, svs) { return this._sharedMany('diffShared', names, states, askState, svs) }
-  step2Shared (names, states, askState, svs) { return this._sharedMany('step2Shared', names, states, askState, svs) }
-  async _sharedMany (op, names, states, askState, svs) {
+  step2Shared (names, states, askState, svs, opts) { return this._sharedMany('step2Shared', names, states, askState, svs, opts) }
+  async _sharedMany (op, names, states, askState, svs, opts) {
+    if (opts && opts.length !== states.length) throw new YgmError(8, 'one option per state')
     if (names.length !== states.length || askState.length !== svs.length) throw new YgmError(8, 'one name per state, one state index per state vector')
     const shard = names.map(n => this.shardOf(n))
     const local = new Array(states.length)   // a state's index inside its shard
-    const parts = this.engines.map(() => ({ states: [], asks: [] }))
-    states.forEach((s, i) => { local[i] = parts[shard[i]].states.length; parts[shard[i]].states.push(s) })
+    const parts = this.engines.map(() => ({ states: [], asks: [], opts: [] }))
+    states.forEach((s, i) => { local[i] = parts[shard[i]].states.length; parts[shard[i]].states.push(s); if (opts) parts[shard[i]].opts.push(opts[i]) })
     for (let a = 0; a < svs.length; a++) {
       const i = askState[a]
       if (!Number.isInteger(i) || i < 0 || i >= states.length) throw new YgmError(8, 'ask names no state')
@@ -300,14 +335,19 @@ class GpuEnginePool {
     const out = new Array(svs.length)
     await Promise.all(parts.map(async (p, e) => {
       if (!p.asks.length) return
-      const r = await this.engines[e][op](p.states, p.asks.map(a => local[askState[a]]), p.asks.map(a => svs[a]))
+      const r = opts
+        ? await this.engines[e][op](p.states, p.asks.map(a => local[askState[a]]), p.asks.map(a => svs[a]), p.opts)
+        : await this.engines[e][op](p.states, p.asks.map(a => local[askState[a]]), p.asks.map(a => svs[a]))
       p.asks.forEach((a, k) => { out[a] = r[k] })
     }))
     return out
   }
 
   stateVectorsMany (names, states) { return this._many(names, [states], (e, a) => e.stateVectorsMany(a)) }
-  snapshotMany (names, states) { return this._many(names, [states], (e, a) => e.snapshotMany(a)) }
+  snapshotMany (names, states, opts) {
+    if (!opts) return this._many(names, [states], (e, a) => e.snapshotMany(a))
+    return this._many(names, [states, Array.from(opts)], (e, a, o) => e.snapshotMany(a, o))
+  }
   containsMany (names, states, updates) { return this._many(names, [states, updates], (e, a, b) => e.containsMany(a, b)) }
   stats () { return this.engines.map(e => e.stats()) }
   /**
@@ -323,4 +363,4 @@ class GpuEnginePool {
   close () { this.engines.forEach(e => e.close()) }
 }
 
-module.exports = { packJobs, GpuEngine, GpuEnginePool, fnv1a64, YgmError, STATUS, loadAddon }
+module.exports = { packJobs, GpuEngine, GpuEnginePool, fnv1a64, YgmError, STATUS, loadAddon, DOC_NO_GC, optBytes }

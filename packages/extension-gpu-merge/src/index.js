@@ -9,11 +9,15 @@
  *   storePayload.state: Buffer     packages/server/src/types.ts:329-331
  *
  * What changes versus extension-database: instead of Y.encodeStateAsUpdate(doc)
- * on every debounced store (Database.ts:55-60), the stored state is
- * Y.mergeUpdates([base, ...updates since base]) computed in a GPU batch with
- * every other document whose store fires in the same window.  The stored bytes
- * are a valid V1 update of the same document state (mergeUpdates semantics,
- * byte-identical to yjs); loading applies it exactly as Database.ts:44-50 does.
+ * on every debounced store (Database.ts:55-60), the state is computed in a GPU
+ * batch with every other document whose store fires in the same window:
+ * Y.mergeUpdates([base, ...updates since base]), then (normalize, the default)
+ * the doc-normalized snapshot of that merge -- Y.encodeStateAsUpdate(
+ * Y.applyUpdate(new Y.Doc(yDocOptions), merged)), the bytes extension-database
+ * stores for a fresh load of the same updates, with the document's own gc
+ * option.  With normalize: false the stored bytes are the bare merge.  Either
+ * is a valid V1 update of the same document state, byte-identical to yjs;
+ * loading applies it exactly as Database.ts:44-50 does.
  */
 const { GpuEngine, GpuEnginePool, fnv1a64, YgmError } = require('./engine')
 const { SyncResponder } = require('./sync')
@@ -42,7 +46,14 @@ class GpuMerge {
   /**
    * @param {{store?: DocumentStore|Function, fetch?: Function, device?: number, Y?: any,
    *          engine?: GpuEngine, batchWindowMs?: number, maxBatchDocs?: number, compat135?: boolean,
-   *          onRefused?: 'reference'|'throw', normalize?: boolean, normalizeMaxBytes?: number}} configuration
+   *          onRefused?: 'reference'|'throw', normalize?: boolean, normalizeMaxBytes?: number,
+   *          gc?: 'document'|boolean}} configuration
+   *   gc ('document' by default): whether the normalized snapshot and the responder's / fan-out's replies are
+   *   garbage-collected.  The reference passes yDocOptions { gc, gcFilter } (types.ts:152-154; per document from
+   *   onCreateDocument, Hocuspocus.ts:331-344) to the Y.Doc constructor, and a gc: false document stores and sends its
+   *   deleted Items with their content (Database.ts:55-60).  'document' reads `document.gc` of the live document this
+   *   extension captures (afterLoadDocument, onStoreDocument); true / false force one behaviour for every document.
+   *   A custom gcFilter (a JavaScript predicate per Item) cannot be reproduced: such deployments use normalize: false.
    *   onRefused: what a store does when the engine refuses ONE document (a per-document status: content
    *   yjs would re-encode, ENONCANON; a corrupt stored base, EMALFORMED / ERANGE / ESURROGATE / EDEPTH) --
    *   'reference' (default): store Y.encodeStateAsUpdate(document) like extension-database and record it in
@@ -66,6 +77,8 @@ class GpuMerge {
     this.priority = configuration.priority || 900
     this.configuration = configuration
     this.normalize = configuration.normalize !== false
+    this.gc = configuration.gc === undefined ? 'document' : configuration.gc
+    if (this.gc !== 'document' && this.gc !== true && this.gc !== false) throw new TypeError("GpuMerge: gc is 'document', true or false")
     this.normalizeMaxBytes = configuration.normalizeMaxBytes === undefined ? 32768 : configuration.normalizeMaxBytes
     /** stores whose merged state was over normalizeMaxBytes (kept as the bare merge) */
     this.sizeSkipped = 0
@@ -76,7 +89,8 @@ class GpuMerge {
       : DocumentStore.fromDatabase({ fetch: configuration.fetch, store: typeof st === 'function' ? st : undefined })
     this.Y = configuration.Y || null
     this.engine = configuration.engine || null
-    /** documentName -> { base: Uint8Array|null, log: UpdateLog (packed captured updates), doc?: Y.Doc, onUpdate?: Function } */
+    /** documentName -> { base: Uint8Array|null, log: UpdateLog (packed captured updates), doc?: Y.Doc, onUpdate?: Function,
+     *  gc?: boolean (the live document's gc option, as last seen) } */
     this.docs = new Map()
     /** stores that fell back to Y.encodeStateAsUpdate(document) because the engine refused the merge */
     this.refused = []
@@ -102,13 +116,24 @@ class GpuMerge {
   syncResponder () {
     return new SyncResponder({
       engine: this._engine(),
-      getState: async name => { const e = this.docs.get(name); return e ? (e.base ? [e.base] : []).concat(e.log.toArray()) : null }
+      getState: async name => { const e = this.docs.get(name); return e ? (e.base ? [e.base] : []).concat(e.log.toArray()) : null },
+      getDocOptions: name => ({ gc: this._gcOf(name) })
     })
+  }
+
+  // is the named document garbage-collected?  The configured value, or ('document') the live document's own option
+  // as captured at load / store; a document never seen is collected, the Y.Doc default
+  _gcOf (documentName, document) {
+    if (this.gc !== 'document') return this.gc
+    const e = this.docs.get(documentName)
+    if (document && typeof document.gc === 'boolean') { if (e) e.gc = document.gc; return document.gc }
+    return e && typeof e.gc === 'boolean' ? e.gc : true
   }
 
   /** Batched extension-redis fan-out over the same captured state (SURVEY.md §8f-3, src/redis.js) */
   redisFanout ({ publish, identifier, prefix, windowMs }) {
-    return new RedisFanout({ engine: this._engine(), getState: this.syncResponder().getState, publish, identifier, prefix, windowMs })
+    const r = this.syncResponder()
+    return new RedisFanout({ engine: this._engine(), getState: r.getState, getDocOptions: r.getDocOptions, publish, identifier, prefix, windowMs })
   }
 
   async onConfigure () { this._engine() }
@@ -144,6 +169,7 @@ class GpuMerge {
     if (await addsToBase(this._engine(), missing, entry.base, data.documentName)) entry.log.push(missing)
     if (entry.doc && entry.onUpdate) entry.doc.off('update', entry.onUpdate)
     entry.doc = data.document
+    this._gcOf(data.documentName, data.document)
     entry.onUpdate = update => entry.log.push(update)
     data.document.on('update', entry.onUpdate)
   }
@@ -176,7 +202,7 @@ class GpuMerge {
         const job = { head: entry.base ? [entry.base] : [], ...entry.log.packed(taken) }
         const eng = this._engine()
         state = await (eng.mergePacked ? eng.mergePacked(job, data.documentName) : eng.mergeUpdates(job.head.concat(entry.log.toArray(taken)), data.documentName))
-        if (this.normalize && state.byteLength <= this.normalizeMaxBytes) state = await this._normalize(state, data.documentName)
+        if (this.normalize && state.byteLength <= this.normalizeMaxBytes) state = await this._normalize(state, data.documentName, this._gcOf(data.documentName, data.document))
         else if (this.normalize) this.sizeSkipped++
       } catch (e) {
         // a document the engine refuses (content yjs would re-encode, YGM_ENONCANON; a corrupt stored
@@ -198,10 +224,13 @@ class GpuMerge {
     entry.log.drop(cut)
   }
 
-  // the doc-normalized snapshot of a merged state; outside the kernel's envelope the merge is kept
-  async _normalize (state, documentName) {
+  // the doc-normalized snapshot of a merged state (gc false: of a Y.Doc({ gc: false }), deleted content kept); outside
+  // the kernel's envelope the merge is kept
+  async _normalize (state, documentName, gc = true) {
     try {
-      return await this._engine().snapshot(state, documentName)
+      const eng = this._engine()
+      if (gc !== false) return await eng.snapshot(state, documentName)
+      return await (typeof eng.shardOf === 'function' ? eng.snapshot(state, documentName, { gc: false }) : eng.snapshot(state, { gc: false }))
     } catch (e) {
       if (e && e.code === 'EUNSUPPORTED') { this.unnormalized.push({ documentName, code: e.code }); return state }
       throw e

@@ -22,11 +22,12 @@ class RedisFanout {
   /**
    * @param {{engine: any, getState: (name: string) => Promise<Uint8Array|Uint8Array[]|null>,
    *          publish: (channel: string, message: Buffer) => any, identifier?: string, prefix?: string,
-   *          windowMs?: number}} opts
+   *          windowMs?: number, getDocOptions?: (name: string) => ({gc?: boolean}|null|undefined)}} opts
    *   getState: the document's stored update or [snapshot, ...log] (GpuMerge: syncResponder()'s source)
+   *   getDocOptions: as SyncResponder's -- { gc: false } documents are answered with their deleted content
    *   publish: the Redis client's publish (ioredis pub.publish)
    */
-  constructor ({ engine, getState, publish, identifier, prefix = 'hocuspocus', windowMs = 2, onError }) {
+  constructor ({ engine, getState, getDocOptions = null, publish, identifier, prefix = 'hocuspocus', windowMs = 2, onError }) {
     this.engine = engine
     this.getState = getState
     this.publish = publish
@@ -36,7 +37,7 @@ class RedisFanout {
     this.redisTransactionOrigin = '__hocuspocus__redis__origin__'
     const id = Buffer.from(this.identifier, 'utf8')
     this.messagePrefix = Buffer.concat([Buffer.from([id.length]), id])
-    this.responder = new SyncResponder({ engine, getState })
+    this.responder = new SyncResponder({ engine, getState, getDocOptions })
     this.pendingStep1 = new Map()   // documentName -> [resolve]
     this.pendingAsks = []           // { message, resolve, reject }
     this.t1 = null

@@ -17,6 +17,9 @@
 // outside the snapshot kernel's envelope (pending structs or delete set, sub-documents) is answered with diffUpdate(state, sv) -- the same content, not the same bytes -- and
 // NAMED: its reply array carries `unnormalized: true` and the document is listed in
 // responder.unnormalized.  The server's Step1 carries encodeStateVectorFromUpdate(state).
+// A document created with gc: false (yDocOptions, Hocuspocus.ts:331-344) answers with its deleted Items and their
+// content: the optional getDocOptions(name) -> { gc: boolean } names such documents, and their states are snapshotted
+// as new Y.Doc({ gc: false }) (the engine's option forms).  Without it nothing changes.
 
 const MessageType = { Sync: 0, SyncReply: 4 }
 const SyncStep = { Step1: 0, Step2: 1, Update: 2 }
@@ -70,11 +73,13 @@ function decodeSyncMessage (message) {
 
 class SyncResponder {
   /**
-   * @param {{ engine: any, getState: (documentName: string) => Promise<Uint8Array | Uint8Array[] | null> }} opts
-   *   engine: GpuEngine or GpuEnginePool; getState: the document's stored update, or [snapshot, ...log]
+   * @param {{ engine: any, getState: (documentName: string) => Promise<Uint8Array | Uint8Array[] | null>,
+   *           getDocOptions?: (documentName: string) => ({ gc?: boolean } | null | undefined) }} opts
+   *   engine: GpuEngine or GpuEnginePool; getState: the document's stored update, or [snapshot, ...log];
+   *   getDocOptions: the document's yDocOptions where they matter ({ gc: false }: replies keep deleted content)
    */
-  constructor ({ engine, getState, Y = null }) {
-    this.engine = engine; this.getState = getState
+  constructor ({ engine, getState, getDocOptions = null, Y = null }) {
+    this.engine = engine; this.getState = getState; this.getDocOptions = getDocOptions
     this.Y = Y   // yjs, for the read-only answer of a document outside the snapshot envelope (loaded lazily)
     /** Step1 replies sent as diffUpdate(state, sv) because the state is outside the snapshot envelope */
     this.unnormalized = []
@@ -84,10 +89,21 @@ class SyncResponder {
   _Y () { if (!this.Y) this.Y = require('yjs'); return this.Y }
   _merge (names, docs) { return this._pooled() ? this.engine.mergeMany(names, docs) : this.engine.mergeMany(docs) }
   _diff (names, states, svs) { return this._pooled() ? this.engine.diffMany(names, states, svs) : this.engine.diffMany(states, svs) }
-  _step2 (names, states, svs) { return this._pooled() ? this.engine.step2Many(names, states, svs) : this.engine.step2Many(states, svs) }
+  // (the options argument is passed only when a document has one: engines without the option forms keep working)
+  _step2 (names, states, svs, opts) {
+    const o = opts ? [opts] : []
+    return this._pooled() ? this.engine.step2Many(names, states, svs, ...o) : this.engine.step2Many(states, svs, ...o)
+  }
   // one state per document, many asks (engines that have the shared-state forms): asks[k] = { d: index into names, sv }
-  _shared (op, names, states, askState, svs) {
-    return this._pooled() ? this.engine[op](names, states, askState, svs) : this.engine[op](states, askState, svs)
+  _shared (op, names, states, askState, svs, opts) {
+    const o = opts ? [opts] : []
+    return this._pooled() ? this.engine[op](names, states, askState, svs, ...o) : this.engine[op](states, askState, svs, ...o)
+  }
+  // option bytes of the named documents (1: created with gc: false), or undefined when none has one
+  _opts (names) {
+    if (!this.getDocOptions) return undefined
+    const o = names.map(n => { const d = this.getDocOptions(n); return d && d.gc === false ? 1 : 0 })
+    return o.some(Boolean) ? o : undefined
   }
 
   _svs (names, states) { return this._pooled() ? this.engine.stateVectorsMany(names, states) : this.engine.stateVectorsMany(states) }
@@ -135,9 +151,11 @@ class SyncResponder {
       const at = new Map(docs.map((n, k) => [n, k]))
       return [docs, docs.map(n => state.get(n)), rows.map(a => at.get(a.documentName)), rows.map(a => a.payload)]
     }
+    const sharedArgs = rows => { const g = grouped(rows); return [...g, this._opts(g[0])] }
     const diffs = typeof this.engine.step2Shared === 'function'
-      ? await this._shared('step2Shared', ...grouped(live))
-      : await this._step2(live.map(a => a.documentName), live.map(a => state.get(a.documentName)), live.map(a => a.payload))
+      ? await this._shared('step2Shared', ...sharedArgs(live))
+      : await this._step2(live.map(a => a.documentName), live.map(a => state.get(a.documentName)), live.map(a => a.payload),
+        this._opts(live.map(a => a.documentName)))
     // states the snapshot kernel does not take: diffUpdate of the state itself, named as such
     const unsup = live.map((a, k) => diffs[k] instanceof Error && diffs[k].code === 'EUNSUPPORTED' ? k : -1).filter(k => k >= 0)
     if (unsup.length) {

@@ -9,6 +9,10 @@
 // Writes `out.bin` (u32 n, then (u32 len, u) per session) and `exp.bin` (i32 status 0, u32 len, bytes),
 // the formats tools/snapdev and tests read.
 //   node tools/snap_corpus.js <n> <seed> <out.bin> <exp.bin> [maxOps] [text|pending|textpending|subdoc|subpending]
+// nogc, textnogc, subnogc, pendingnogc: the sessions of '', text, subdoc and pending, with
+//   expected = Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc({ gc: false }), u))
+// -- what a deployment with yDocOptions { gc: false } stores (deleted content kept).  These modes print one JSON line
+// of counters: how many expectations differ from the garbage-collected one of the same session.
 // subdoc: the general sessions with sub-documents (Y.Doc values in a map and an array, some of them deleted)
 // pending: the same sessions with 1-3 of the log's updates lost (out-of-order delivery: later updates depend on the
 // missing ones) -- u merges what is left, so Y.applyUpdate leaves pending structs and / or a pending delete set
@@ -36,7 +40,14 @@ function dropSome (log, seed) {
   return out
 }
 
-function textSession (seed, maxOps, drop) {
+// the snapshot a Y.Doc({ gc: false }) holds after integrating u
+function snapshotNoGc (u) {
+  const fresh = new Y.Doc({ gc: false })
+  Y.applyUpdate(fresh, u)
+  return Y.encodeStateAsUpdate(fresh)
+}
+
+function textSession (seed, maxOps, drop, subdoc, nogc) {
   const R = rng(seed * 2654435761 + 777)
   const ri = n => Math.floor(R() * n)
   const nPeers = 1 + ri(4)
@@ -67,10 +78,11 @@ function textSession (seed, maxOps, drop) {
   const u = kept.length ? Y.mergeUpdates(kept) : Y.encodeStateAsUpdate(new Y.Doc())
   const fresh = new Y.Doc()
   Y.applyUpdate(fresh, u)
+  if (nogc) return [u, snapshotNoGc(u), Y.encodeStateAsUpdate(fresh)]
   return [u, Y.encodeStateAsUpdate(fresh)]
 }
 
-function session (seed, maxOps, drop, subdoc) {
+function session (seed, maxOps, drop, subdoc, nogc) {
   const R = rng(seed * 2654435761 + 12345)
   const ri = n => Math.floor(R() * n)
   const nPeers = 1 + ri(3)
@@ -154,6 +166,7 @@ function session (seed, maxOps, drop, subdoc) {
   const u = kept.length ? Y.mergeUpdates(kept) : Y.encodeStateAsUpdate(new Y.Doc())
   const fresh = new Y.Doc()
   Y.applyUpdate(fresh, u)
+  if (nogc) return [u, snapshotNoGc(u), Y.encodeStateAsUpdate(fresh)]
   return [u, Y.encodeStateAsUpdate(fresh)]
 }
 
@@ -171,11 +184,19 @@ if (require.main === module) {
   const seed = parseInt(process.argv[3] || '1', 10)
   const maxOps = parseInt(process.argv[6] || '60', 10)
   const mode = process.argv[7] || ''
-  const gen = mode === 'text' || mode === 'textpending' ? textSession : session
-  const drop = mode === 'pending' || mode === 'textpending' || mode === 'subpending'
-  const subdoc = mode === 'subdoc' || mode === 'subpending'
+  const nogc = mode.endsWith('nogc')
+  const base = nogc ? mode.slice(0, -4) : mode
+  const gen = base === 'text' || base === 'textpending' ? textSession : session
+  const drop = base === 'pending' || base === 'textpending' || base === 'subpending'
+  const subdoc = base === 'sub' || base === 'subdoc' || base === 'subpending'
   const us = []; const ex = []
-  for (let i = 0; i < n; i++) { const [u, e] = gen(seed * 100003 + i, maxOps, drop, subdoc); us.push(u); ex.push(e) }
+  let differ = 0
+  for (let i = 0; i < n; i++) {
+    const [u, e, gcd] = gen(seed * 100003 + i, maxOps, drop, subdoc, nogc)
+    us.push(u); ex.push(e)
+    if (nogc && Buffer.compare(Buffer.from(e), Buffer.from(gcd)) !== 0) differ++
+  }
+  if (nogc) console.log(JSON.stringify({ mode, rows: n, differ_from_gc: differ }))
   write(process.argv[4], us, false)
   const eb = [Buffer.from(new Uint32Array([ex.length]).buffer)]
   for (const b of ex) eb.push(Buffer.from(new Int32Array([0]).buffer), Buffer.from(new Uint32Array([b.length]).buffer), Buffer.from(b))

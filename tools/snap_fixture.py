@@ -5,7 +5,12 @@ once per (n, seed, maxOps, mode) part and writes {"source": ..., "rows": [[updat
     python tools/snap_fixture.py --contains OUT.json.gz N SEED [pending]    (tools/contains_corpus.js: states, rows)
 
 tests/golden/snapshot_pending_v135.json.gz: 200:31:120:pending 120:32:200:textpending
-tests/golden/contains_pending_v135.json.gz: --contains 120 51 pending"""
+tests/golden/contains_pending_v135.json.gz: --contains 120 51 pending
+tests/golden/snapshot_nogc_v135.json.gz: 160:61:60:nogc 120:62:80:textnogc 40:63:60:subnogc 80:64:120:pendingnogc
+                                         24:11:80:nogc 24:21:150:textnogc
+    (documents created with gc: false; the last two parts replay the first sessions of snapshot_v135 / snapshot_text_v135;
+    the generator prints how many expectations differ from the garbage-collected ones: 410 of 448)
+tests/golden/step2_nogc_v135.json.gz: node tools/step2_corpus.js OUT nogc (over snapshot_nogc_v135)"""
 import gzip
 import json
 import os

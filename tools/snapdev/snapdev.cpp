@@ -2,6 +2,7 @@
 // host over a file of updates, so the kernel's logic can be iterated against the yjs bundle in the
 // build container.  Input: u32 count, then (u32 len, bytes) per update.  Output: (i32 status, u32 len,
 // bytes) per update; a document left pending (status 64) writes its PendHdr and three updates.
+// flags: 1 = yjs 13.5 compat, + 32 (snap::F_SNAP_NOGC) = the documents are Y.Doc({gc: false}): deleted content kept.
 #define YGM_HOST_BUILD 1
 #include <cstdio>
 #include <cstdlib>

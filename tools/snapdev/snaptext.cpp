@@ -3,7 +3,8 @@
 // document the text path takes, its bytes must equal the general path's.  Output: one line per document,
 // "<taken 0/1> <general status> <equal 0/1>"; with out.bin, the text path's results in snapdev's format (status -1:
 // not taken).
-//     snaptext in.bin [flags] [budget] [out.bin]   (budget: LDS bytes of the workspace; default 6144)
+//     snaptext in.bin [flags] [budget] [out.bin]   (budget: LDS bytes of the workspace; default 6144;
+//                                                  flags: 1 = 13.5 compat, + 32 = no-GC documents, as snapdev)
 #define YGM_HOST_BUILD 1
 #include <cstdio>
 #include <cstdlib>
