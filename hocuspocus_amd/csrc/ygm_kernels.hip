@@ -1178,9 +1178,11 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     LRec rec[LN_ROWS];
     bool hs[LN_ROWS], hasd[LN_ROWS];   // row holds an update with structs / with a non-empty delete set
     bool bad = false;
+    bool allfast = false;   // (wave-uniform) every row was decided by the fast parse: the log-order placement's documents
 #pragma unroll
     for (int q = 0; q < LN_ROWS; q++) { hs[q] = false; hasd[q] = false; }
     if (go && !WIDE && YGM_LN_FASTPARSE) {
+      allfast = true;
       // phase-major: the windows and tail bytes of YGM_LN_FASTGROUP rows are loaded (invalid lanes: the first
       // update, 0 bytes), then those rows' fast parses run, straight-line; a row with a valid lane that is not
       // fast is parsed again, whole, by lean_parse
@@ -1207,6 +1209,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) {
         if (__ballot(slow[q]) == 0) continue;
+        allfast = false;
         const bool valid = ln_owns(l, q, k);
         if (valid) { rec[q] = lean_parse<LN_UMAX>(lin, us[q], un[q]); bad |= !rec[q].ok; }
         hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
@@ -1243,6 +1246,12 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) blk[q] = hs[q] ? 0xFFu : 0xFEu;
       uint32_t ctl = 0, nC = 0;
+      // log-order placement (all-fast documents): a block's first clock is the clock of its first record in log
+      // order -- the lowest lane holding one, its lowest slot.  fcb[q]: the first clock of the record's block;
+      // lane c of `fcl`: block c's
+      uint32_t fcl = 0, fcb[LN_ROWS];
+#pragma unroll
+      for (int q = 0; q < LN_ROWS; q++) fcb[q] = 0;
       for (int it = 0; it <= LN_CMAX; it++) {
         uint32_t mx = 0; bool any = false;
 #pragma unroll
@@ -1250,6 +1259,19 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         if (__ballot(any) == 0) break;
         if (nC == (uint32_t)LN_CMAX) { defer = true; break; }
         const uint32_t cand = lane63(dpp_incl_max(mx));
+        if (!WIDE && allfast) {
+          bool hit = false;
+          uint32_t lc = 0;
+#pragma unroll
+          for (int q = LN_ROWS - 1; q >= 0; q--) {
+            const bool m = blk[q] == 0xFFu && rec[q].client == cand;
+            hit |= m; lc = m ? rec[q].clock : lc;
+          }
+          const uint32_t fc = lean_first_of(lc, __ballot(hit));   // (some record holds cand: the ballot is not empty)
+#pragma unroll
+          for (int q = 0; q < LN_ROWS; q++) fcb[q] = (blk[q] == 0xFFu && rec[q].client == cand) ? fc : fcb[q];
+          fcl = l == nC ? fc : fcl;
+        }
 #pragma unroll
         for (int q = 0; q < LN_ROWS; q++) if (blk[q] == 0xFFu && rec[q].client == cand) blk[q] = nC;
         ctl = l == nC ? cand : ctl;
@@ -1287,79 +1309,114 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
 #pragma unroll
           for (int q = 0; q < LN_ROWS; q++) idx[q] = (idx[q] >> (8u * (blk[q] & 3u))) & 0xFFu;
         }
-        // exclusive per-block record bases, packed 8-bit (blocks 0-3 / 4-7): the prefix sum of the
-        // packed counts by byte (x * 0x01010100 adds every lower byte into the higher ones)
-        const uint32_t RB0 = cA * 0x01010100u;
-        const uint32_t tot0 = (RB0 >> 24) + (cA >> 24);
-        const uint32_t RB1 = cB * 0x01010100u + tot0 * 0x01010101u;
-        const uint32_t nrec = (RB1 >> 24) + (cB >> 24);
-        // ---- records scattered to their sorted slot (block, log order): clock, end, packed source
-        //      (staged position << 16 | block << 13 | structs << 5 | struct bytes)
-        LB32* Sck = (LB32*)lout;
-        LB32* Sen = Sck + WAVE * LN_ROWS;
-        LB32* Ssp = Sen + WAVE * LN_ROWS;
-        LB32* Sbs = Ssp + WAVE * LN_ROWS;   // per block: packed (structs, bytes) before its first record; first clock
-        LB32* Sfc = Sbs + LN_CMAX;
-#pragma unroll
-        for (int q = 0; q < LN_ROWS; q++) {
-          if (hs[q]) {
-            const uint32_t b = blk[q];
-            const uint32_t j = idx[q] + ((b < 4u ? RB0 : RB1) >> (8u * (b & 3u)) & 0xFFu);
-            Sck[j] = rec[q].clock; Sen[j] = rec[q].clock + rec[q].clen;
-            Ssp[j] = (rec[q].span & 0xFFFF0000u) | (b << 13) | (((rec[q].span >> 8) & 0x7Fu) << 6) | (rec[q].span & 0x3Fu);
-          }
-        }
-        wave_sync();
-        // ---- sorted domain: contiguity (rule R-M without gaps / overlaps: a record's clock is the end
-        //      of the previous record of its block) and the packed (structs, bytes) prefix
-        //      Lane l takes slots 4l .. 4l+3: three 16-byte reads; the predecessor of slot 4l is lane l-1's
-        //      last slot (two dword reads), the other predecessors are the lane's own registers
+        // what the emit takes from either placement: osp / oex per record (sorted domain: packed source and the
+        // (structs, bytes) prefix of slot 4l + r; log order: osp = the destination of update 4l + q), carry (struct
+        // bytes in the low half), lane c's block header (hcnt, ctl, hfc at hpos) and the header bytes
         uint32_t osp[LN_ROWS], oex[LN_ROWS];
-        uint32_t carry = 0;
-        {
-          const u32x4 vsp = *(const LB128*)(Ssp + LN_ROWS * l), vck = *(const LB128*)(Sck + LN_ROWS * l);
-          const u32x4 ven = *(const LB128*)(Sen + LN_ROWS * l);
-          uint32_t spp = l > 0u ? Ssp[LN_ROWS * l - 1u] : 0u, ep = l > 0u ? Sen[LN_ROWS * l - 1u] : 0u;
-          uint32_t ck[LN_ROWS], tot = 0;
-          bool first[LN_ROWS];
+        uint32_t carry = 0, hcnt = 0, hfc = 0, hpos = 0, hdr_all = 0, HC0 = 0, HC1 = 0, nrec = 0;
+        // ---- log-order placement (narrow kernel): every update is one Item of one character or a deletion, at
+        //      most four clients.  A record's place in its block is idx, known where the record is: no sorted
+        //      domain, no LDS
+        const bool logp = !WIDE && allfast && nC <= 4u;
+        if (logp) {
+          // contiguity: a gap-free, overlap-free block is clock == first clock + idx for every record (what
+          // "clock == the previous record's end" says by induction; the fast parse refuses clock 0xFFFFFFFF)
 #pragma unroll
-          for (int r = 0; r < LN_ROWS; r++) {
-            const bool v = ln_owns(l, r, nrec);
-            const uint32_t sp = v ? vsp[r] : 0u;
-            ck[r] = v ? vck[r] : 0u;
-            first[r] = v && ((r == 0 && l == 0u) || ((spp ^ sp) & 0xE000u) != 0u);   // first record of its block
-            bad |= v && !first[r] && ck[r] != ep;
-            spp = sp; ep = ven[r];
-            osp[r] = sp; oex[r] = tot;
-            tot += v ? (((sp >> 6) & 0x7Fu) << 16) | (sp & 0x3Fu) : 0u;
+          for (int q = 0; q < LN_ROWS; q++) bad |= hs[q] && rec[q].clock != fcb[q] + idx[q];
+          // byte offset inside the block: a fast record has <= 29 struct bytes and a block <= 255 records (< 2^13
+          // bytes), so two blocks share one scan as 16-bit fields -- blocks 0-1, then 2-3 when they exist
+          const uint32_t T01 = lean_byte_prefix<0>(hs, blk, rec, osp);
+          uint32_t T23 = 0;
+          if (nC > 2u) T23 = lean_byte_prefix<1>(hs, blk, rec, osp);
+          const uint32_t B0 = T01 & 0xFFFFu, B1 = T01 >> 16, B2 = T23 & 0xFFFFu, B3 = T23 >> 16;
+          // block headers, lane c = block c; their lengths to scalars (four blocks: no scan)
+          uint32_t hlen = 0;
+          if (l < nC) {
+            hcnt = (cA >> (8u * (l & 3u))) & 0xFFu; hfc = fcl;
+            hlen = vlen32(hcnt) + vlen32(ctl) + vlen32(hfc);
           }
-          const uint32_t inc = dpp_incl_add(tot);
-          carry = lane63(inc);
+          const uint32_t h0 = rdlane(hlen, 0), h1 = rdlane(hlen, 1), h2 = rdlane(hlen, 2), h3 = rdlane(hlen, 3);
+          // O[b]: where block b's structs start (the headers through b and the bytes of the blocks before it)
+          const uint32_t O0 = vlen32(nC) + h0, O1 = O0 + h1 + B0, O2 = O1 + h2 + B1, O3 = O2 + h3 + B2;
+          const uint32_t O01 = O0 | (O1 << 16), O23 = O2 | (O3 << 16);   // (< 2^16: at most 4 x 255 x 29 bytes and the headers)
+          hdr_all = h0 + h1 + h2 + h3;
+          carry = B0 + B1 + B2 + B3;
+          hpos = lean_field16((l & 2u) ? O23 : O01, l) - hlen;
 #pragma unroll
-          for (int r = 0; r < LN_ROWS; r++) {
-            oex[r] += inc - tot;
-            if (first[r]) { Sbs[(osp[r] >> 13) & 7u] = oex[r]; Sfc[(osp[r] >> 13) & 7u] = ck[r]; }
+          for (int q = 0; q < LN_ROWS; q++) { osp[q] = lean_field16(osp[q] + (blk[q] < 2u ? O01 : O23), blk[q]); oex[q] = 0; }
+        } else {
+          // exclusive per-block record bases, packed 8-bit (blocks 0-3 / 4-7): the prefix sum of the
+          // packed counts by byte (x * 0x01010100 adds every lower byte into the higher ones)
+          const uint32_t RB0 = cA * 0x01010100u;
+          const uint32_t tot0 = (RB0 >> 24) + (cA >> 24);
+          const uint32_t RB1 = cB * 0x01010100u + tot0 * 0x01010101u;
+          nrec = (RB1 >> 24) + (cB >> 24);
+          // ---- records scattered to their sorted slot (block, log order): clock, end, packed source
+          //      (staged position << 16 | block << 13 | structs << 5 | struct bytes)
+          LB32* Sck = (LB32*)lout;
+          LB32* Sen = Sck + WAVE * LN_ROWS;
+          LB32* Ssp = Sen + WAVE * LN_ROWS;
+          LB32* Sbs = Ssp + WAVE * LN_ROWS;   // per block: packed (structs, bytes) before its first record; first clock
+          LB32* Sfc = Sbs + LN_CMAX;
+#pragma unroll
+          for (int q = 0; q < LN_ROWS; q++) {
+            if (hs[q]) {
+              const uint32_t b = blk[q];
+              const uint32_t j = idx[q] + ((b < 4u ? RB0 : RB1) >> (8u * (b & 3u)) & 0xFFu);
+              Sck[j] = rec[q].clock; Sen[j] = rec[q].clock + rec[q].clen;
+              Ssp[j] = (rec[q].span & 0xFFFF0000u) | (b << 13) | (((rec[q].span >> 8) & 0x7Fu) << 6) | (rec[q].span & 0x3Fu);
+            }
           }
-        }
-        wave_sync();
-        // ---- block headers, lane c = block c: structs, client, first clock; header offsets by a scan
-        uint32_t hcnt = 0, hfc = 0, hbs = 0, hlen = 0;
-        if (l < nC) {
-          hbs = Sbs[l]; hfc = Sfc[l];
-          const uint32_t nxt = l + 1u < nC ? Sbs[l + 1u] : carry;
-          hcnt = (nxt >> 16) - (hbs >> 16);
-          hlen = vu_len(hcnt) + vu_len(ctl) + vu_len(hfc);
-        }
-        const uint32_t hinc = dpp_incl_add(hlen);          // header bytes of blocks <= c (< 128 with <= 8 blocks)
-        const uint32_t hdr_all = lane63(hinc);
-        uint32_t HC0 = 0, HC1 = 0;                         // vu_len(nC) + hinc of each block, packed 8-bit
+          wave_sync();
+          // ---- sorted domain: contiguity (rule R-M without gaps / overlaps: a record's clock is the end
+          //      of the previous record of its block) and the packed (structs, bytes) prefix
+          //      Lane l takes slots 4l .. 4l+3: three 16-byte reads; the predecessor of slot 4l is lane l-1's
+          //      last slot (two dword reads), the other predecessors are the lane's own registers
+          {
+            const u32x4 vsp = *(const LB128*)(Ssp + LN_ROWS * l), vck = *(const LB128*)(Sck + LN_ROWS * l);
+            const u32x4 ven = *(const LB128*)(Sen + LN_ROWS * l);
+            uint32_t spp = l > 0u ? Ssp[LN_ROWS * l - 1u] : 0u, ep = l > 0u ? Sen[LN_ROWS * l - 1u] : 0u;
+            uint32_t ck[LN_ROWS], tot = 0;
+            bool first[LN_ROWS];
 #pragma unroll
-        for (int c = 0; c < LN_CMAX; c++) {
-          const uint32_t hc = rdlane(hinc, (uint32_t)c) + vu_len(nC);
-          if (c < 4) HC0 |= (hc & 0xFFu) << (8 * c); else HC1 |= (hc & 0xFFu) << (8 * (c - 4));
+            for (int r = 0; r < LN_ROWS; r++) {
+              const bool v = ln_owns(l, r, nrec);
+              const uint32_t sp = v ? vsp[r] : 0u;
+              ck[r] = v ? vck[r] : 0u;
+              first[r] = v && ((r == 0 && l == 0u) || ((spp ^ sp) & 0xE000u) != 0u);   // first record of its block
+              bad |= v && !first[r] && ck[r] != ep;
+              spp = sp; ep = ven[r];
+              osp[r] = sp; oex[r] = tot;
+              tot += v ? (((sp >> 6) & 0x7Fu) << 16) | (sp & 0x3Fu) : 0u;
+            }
+            const uint32_t inc = dpp_incl_add(tot);
+            carry = lane63(inc);
+#pragma unroll
+            for (int r = 0; r < LN_ROWS; r++) {
+              oex[r] += inc - tot;
+              if (first[r]) { Sbs[(osp[r] >> 13) & 7u] = oex[r]; Sfc[(osp[r] >> 13) & 7u] = ck[r]; }
+            }
+          }
+          wave_sync();
+          // ---- block headers, lane c = block c: structs, client, first clock; header offsets by a scan
+          uint32_t hbs = 0, hlen = 0;
+          if (l < nC) {
+            hbs = Sbs[l]; hfc = Sfc[l];
+            const uint32_t nxt = l + 1u < nC ? Sbs[l + 1u] : carry;
+            hcnt = (nxt >> 16) - (hbs >> 16);
+            hlen = vu_len(hcnt) + vu_len(ctl) + vu_len(hfc);
+          }
+          const uint32_t hinc = dpp_incl_add(hlen);          // header bytes of blocks <= c (< 128 with <= 8 blocks)
+          hdr_all = lane63(hinc);
+          // HC0 / HC1: vu_len(nC) + hinc of each block, packed 8-bit
+#pragma unroll
+          for (int c = 0; c < LN_CMAX; c++) {
+            const uint32_t hc = rdlane(hinc, (uint32_t)c) + vu_len(nC);
+            if (c < 4) HC0 |= (hc & 0xFFu) << (8 * c); else HC1 |= (hc & 0xFFu) << (8 * (c - 4));
+          }
+          hpos = vu_len(nC) + hinc - hlen + (hbs & 0xFFFFu);   // lane c: block c's header position
+          wave_sync();
         }
-        const uint32_t hpos = vu_len(nC) + hinc - hlen + (hbs & 0xFFFFu);   // lane c: block c's header position
-        wave_sync();
         // ---- delete sets: union of every update's ranges (scratch: the sorted records are consumed)
         LDsUnion dsu; dsu.bytes = 1u; dsu.bad = false; dsu.nsegs = 0;
         bool anyds = false;
@@ -1392,7 +1449,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         DIAGL(2);
         defer = __ballot(bad) != 0;
 #if defined(YGM_LEAN_STOP) && YGM_LEAN_STOP == 3   // timing experiment: stage + parse + scan
-        if (l == 0) status[d] = (int)bad + (int)(oex[0] & 1) + (int)(oex[1] & 1) + (int)(oex[2] & 1) + (int)(oex[3] & 1); wave_sync(); dit++; d = LN_AHEAD(1); continue;
+        if (l == 0) status[d] = (int)bad + (int)((oex[0] ^ osp[0]) & 1) + (int)((oex[1] ^ osp[1]) & 1) + (int)((oex[2] ^ osp[2]) & 1) + (int)((oex[3] ^ osp[3]) & 1) + (int)((hpos ^ hcnt ^ hfc) & 1); wave_sync(); dit++; d = LN_AHEAD(1); continue;
 #endif
         if (!defer) {
           const uint32_t at = vu_len(nC) + hdr_all;   // + the struct bytes: the delete set's position
@@ -1400,17 +1457,27 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
           if (size > (uint32_t)C::OUT || ((size + 15u) & ~15u) > cap || slot + size > out_cap) defer = true;
           else {
             // ---- emit into the LDS output buffer: structs (funnel copies), block headers, document header, delete set
-            uint32_t ct[LN_ROWS], cw = 0;   // destinations; the widest run (head + bytes) of the document
+            uint32_t cw = 0;   // the widest run (head + bytes) of the document
+            if (logp) {    // rows in log order: the record's own span, predicated by hs
 #pragma unroll
-            for (int r = 0; r < LN_ROWS; r++) {
-              const uint32_t b = (osp[r] >> 13) & 7u;
-              ct[r] = (oex[r] & 0xFFFFu) + ((b < 4u ? HC0 : HC1) >> (8u * (b & 3u)) & 0xFFu);
-              cw = max(cw, ln_owns(l, r, nrec) ? (ct[r] & 3u) + (osp[r] & 0x3Fu) : 0u);
+              for (int q = 0; q < LN_ROWS; q++) cw = max(cw, hs[q] ? (osp[q] & 3u) + (rec[q].span & 0x3Fu) : 0u);
+              const uint32_t cls = lean_copy_class<WIDE>(cw);
+#pragma unroll
+              for (int q = 0; q < LN_ROWS; q++)
+                lean_copy<WIDE>(lout, lin, cls, hs[q], osp[q], rec[q].span >> 16, rec[q].span & 0x3Fu);
+            } else {
+              uint32_t ct[LN_ROWS];   // destinations
+#pragma unroll
+              for (int r = 0; r < LN_ROWS; r++) {
+                const uint32_t b = (osp[r] >> 13) & 7u;
+                ct[r] = (oex[r] & 0xFFFFu) + ((b < 4u ? HC0 : HC1) >> (8u * (b & 3u)) & 0xFFu);
+                cw = max(cw, ln_owns(l, r, nrec) ? (ct[r] & 3u) + (osp[r] & 0x3Fu) : 0u);
+              }
+              const uint32_t cls = lean_copy_class<WIDE>(cw);
+#pragma unroll
+              for (int r = 0; r < LN_ROWS; r++)
+                lean_copy<WIDE>(lout, lin, cls, ln_owns(l, r, nrec), ct[r], osp[r] >> 16, osp[r] & 0x3Fu);
             }
-            const uint32_t cls = lean_copy_class<WIDE>(cw);
-#pragma unroll
-            for (int r = 0; r < LN_ROWS; r++)
-              lean_copy<WIDE>(lout, lin, cls, ln_owns(l, r, nrec), ct[r], osp[r] >> 16, osp[r] & 0x3Fu);
             if (l < nC) {
               uint32_t t = lds_vu(lout, hpos, hcnt);
               t = lds_vu(lout, t, ctl);

@@ -26,16 +26,27 @@
 //           that depends on the window; only a row holding another shape runs lean_parse,
 //           the generic grammar (multi-struct, parents, ContentDeleted, longer strings),
 //           whose dependent byte reads cost an LDS round trip each
-//   clients distinct clients by wave vote, ranked descending (scalar)
+//   clients distinct clients by wave vote, ranked descending (scalar).  Narrow kernel, every row fast: the
+//           vote also takes each block's first clock (the clock of its first record in log order: the
+//           ballot's first lane, one readlane) to lane c and to the block's records
 //   scan    log order: a record's index inside its block by one DPP scan of packed 8-bit per-block
-//           counts (a second one with more than four clients).  Sorted order: the records are
+//           counts (a second one with more than four clients)
+//   place   one of two, wave-uniform per document:
+//           log order (narrow kernel, every row decided by the fast parse, <= 4 clients): every record is
+//           one Item of one character, so a gap-free, overlap-free block is clock == first clock + index,
+//           tested where the record is; the byte offset inside the block is the exclusive prefix of the
+//           struct bytes in the lane on top of one DPP scan of the lane totals, two blocks per scan as
+//           16-bit fields (255 records of <= 29 bytes: < 2^13), a second scan with three or four
+//           clients; block totals from lane 63, block bases and header positions by scalar adds.  No LDS
+//           sorted domain (every other document): the records are
 //           scattered to LDS by (block, index) -- clock, end, packed source -- and lane l reads slots
 //           4l .. 4l+3 back as 16-byte vectors, with slot 4l - 1 for the first one's predecessor
 //           (contiguity: clock == the previous record's end), then one DPP scan of the packed
-//           (structs, bytes) gives every record's byte offset
+//           (structs, bytes) gives every record's byte offset; block bases and first clocks go
+//           through LDS to lane c
 //   emit    ds_or_b32 of funnel-shifted source dwords into a zeroed LDS output buffer
-//           (branch-free, order-free; one width class per document), then 16-byte coalesced
-//           stores
+//           (branch-free, order-free; one width class per document; rows in log order or in sorted
+//           order, as placed), then 16-byte coalesced stores
 #pragma once
 #include "ygm_common.hpp"
 #include "ygm_merge_wave.hpp"
@@ -517,6 +528,32 @@ YDEV uint32_t lds_vu(LB8* out, uint32_t t, uint32_t v) {
 YDEV uint32_t vlen32(uint32_t v) {   // bytes of the varuint encoding of v
   return 1u + (v > 0x7Fu ? 1u : 0u) + (v > 0x3FFFu ? 1u : 0u) + (v > 0x1FFFFFu ? 1u : 0u) + (v > 0xFFFFFFFu ? 1u : 0u);
 }
+// ---- log-order placement (narrow kernel; documents whose every update took the fast parse, <= 4 clients)
+// x of the first lane of the (non-empty) ballot m, wave-uniform
+YDEV uint32_t lean_first_of(uint32_t x, uint64_t m) { return rdlane(x, (uint32_t)__builtin_ctzll(m)); }
+// 16-bit field b & 1 of a packed pair
+YDEV uint32_t lean_field16(uint32_t x, uint32_t b) { return (x >> (16u * (b & 1u))) & 0xFFFFu; }
+// Struct bytes of the earlier records of a record's block, for the blocks 2 HI and 2 HI + 1 as the two 16-bit
+// fields of one scan: the exclusive prefix in log order inside the lane on top of one DPP scan of the lane
+// totals.  pre[q] (packed; lean_field16 by the block takes it out) is written for the records of those two
+// blocks and kept for the others; returns the two blocks' byte totals, packed
+template <int HI>
+YDEV uint32_t lean_byte_prefix(const bool (&hs)[LN_ROWS], const uint32_t (&blk)[LN_ROWS], const LRec (&rec)[LN_ROWS],
+                               uint32_t (&pre)[LN_ROWS]) {
+  uint32_t e[LN_ROWS], t = 0;
+  bool in[LN_ROWS];
+#pragma unroll
+  for (int q = 0; q < LN_ROWS; q++) {
+    in[q] = hs[q] && (blk[q] >> 1) == (uint32_t)HI;
+    e[q] = t;
+    t += in[q] ? (rec[q].span & 0xFFu) << (16u * (blk[q] & 1u)) : 0u;
+  }
+  const uint32_t inc = dpp_incl_add(t);
+#pragma unroll
+  for (int q = 0; q < LN_ROWS; q++) pre[q] = (HI == 0 || in[q]) ? inc - t + e[q] : pre[q];
+  return lane63(inc);
+}
+
 // one DPP step of a 64-bit inclusive max scan: (hi, lo) pairs move together (lanes the pattern does not
 // reach read (0, 0), which never wins)
 template <int CTRL, int RM, bool BC>
