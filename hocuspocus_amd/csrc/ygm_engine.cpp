@@ -70,6 +70,9 @@ int ygm_k_launch_pend_split(const uint32_t* list, uint32_t P, const uint8_t* ws,
 int ygm_k_launch_pend_join(uint32_t P, const uint8_t* ad, const uint64_t* a_off, const uint64_t* a_len, const int32_t* a_st, const uint8_t* bd,
                            const uint64_t* offs, const uint8_t* cd, const uint64_t* c_off, const uint64_t* c_len, const int32_t* c_st,
                            uint64_t* upd_off, uint32_t* doc_upd, int32_t* pst, uint8_t* dst, int pass, hipStream_t s);
+int ygm_k_launch_ver_cut(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint8_t* V, const uint64_t* v_off,
+                         uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t out_total, uint64_t* out_off, uint64_t* out_len,
+                         int32_t* status, hipStream_t s);
 int ygm_k_launch_pack(const uint8_t* src, const uint64_t* off, const uint64_t* len, const int32_t* status, uint32_t n, uint64_t* bsum,
                       uint8_t* dst, uint64_t* poff, hipStream_t s);
 int ygm_k_launch_doc_lean(int mode, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* doc_off, const uint8_t* sv_arena,
@@ -226,6 +229,7 @@ struct ygm_ctx {
   // and the two stage contexts (own streams and buffers) that double-buffer a batch's chunks
   PinBuf h_data, h_off, h_len, h_status, h_in;
   DevBuf pk_data, pk_off, pk_bsum;
+  DevBuf vr_out, vr_off, vr_len, vr_st, vr_pk, vr_pkoff;   // version restore: the cut's slots, places, lengths, statuses; the cut updates packed
   DevBuf s2_data, s2_off, s2_bsum, s2_st;   // sync step2: packed snapshots, their offsets, scan scratch, snapshot statuses
   ygm_ctx* kid[2] = {nullptr, nullptr};
   std::vector<uint32_t> h_doc_upd;
@@ -316,7 +320,9 @@ void ygm_close(ygm_ctx* c) {
   for (ygm_ctx* k : c->kid) if (k) ygm_close(k);
   if (c->pend_ctx) ygm_close(c->pend_ctx);
   for (ygm_ctx* k : c->pend_dx) if (k) ygm_close(k);
-  for (DevBuf* b : {&c->pk_data, &c->pk_off, &c->pk_bsum}) b->release();
+  for (DevBuf* b : {&c->pk_data, &c->pk_off, &c->pk_bsum, &c->s2_data, &c->s2_off, &c->s2_bsum, &c->s2_st, &c->vr_out, &c->vr_off, &c->vr_len,
+                    &c->vr_st, &c->vr_pk, &c->vr_pkoff})
+    b->release();
   for (PinBuf* b : {&c->h_data, &c->h_off, &c->h_len, &c->h_status, &c->h_in}) b->release();
   for (hipEvent_t e : {c->e0, c->e1, c->e2, c->e3}) if (e) (void)hipEventDestroy(e);
   if (c->h_meta) (void)hipHostFree(c->h_meta);
@@ -735,7 +741,8 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
   HIPCHK(hipEventRecord(c->e0, s));
   // tier 1: k_snap_text (flat text; input + workspace in LDS) into per-document slots; the documents it leaves go to
   // the count / scan / k_snap path, whose workspaces follow the slot region
-  const bool lds = n_docs && getenv("YGM_SNAP_NOLDS") == nullptr;
+  // (the flat-text tier writes updates only: a take batch, YGM_F_SNAP_VERSION, goes to k_snap whole)
+  const bool lds = n_docs && !(xf & YGM_F_SNAP_VERSION) && getenv("YGM_SNAP_NOLDS") == nullptr;
   const uint64_t slot_total = lds ? 2 * arena_bytes + 64ull * n_docs + 64 : 0;
   uint64_t lds_pay[2] = {0, 0};
   if (lds) {
@@ -813,6 +820,70 @@ static int pack_snapshots(ygm_ctx* c, hipStream_t s, const ygm_device_result& r1
     HIPCHK(hipMemcpyAsync(c->s2_off.as<uint64_t>() + n_docs, c->s2_bsum.as<uint64_t>() + nb, 8, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->s2_st.p, r1.status, 4ull * n_docs, hipMemcpyDeviceToDevice, s));
   } else HIPCHK(hipMemsetAsync(c->s2_off.p, 0, 8, s));
+  return YGM_OK;
+}
+
+// ---- version history.  take: the snapshot batch in its Y.snapshot view (YGM_F_SNAP_STATE) ending with encode_version
+int ygm_version_take_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, uint32_t n_docs,
+                               void* stream, ygm_device_result* out) {
+  if (!c || !out) return YGM_EINVAL;
+  (void)hipSetDevice(c->device);
+  return snapshot_dev(c, d_states, states_bytes, d_state_off, n_docs, stream ? (hipStream_t)stream : c->stream, out,
+                      YGM_F_SNAP_STATE | YGM_F_SNAP_VERSION);
+}
+// restore: (1) the states' no-GC snapshots in their Y.snapshot view, (2) packed, (3) cut at the versions' clocks with
+// the versions' delete sets appended (k_ver_cut, per-document slots), (4) packed again, (5) snapshotted into the new
+// documents (restored_opt); the statuses of (1) and (3) carried into the result
+int ygm_version_restore_v1_device(ygm_ctx* c, const uint8_t* d_states, const uint64_t* d_state_off, const uint8_t* d_versions,
+                                  const uint64_t* d_version_off, const uint8_t* d_restored_opt, uint32_t n_docs, void* stream,
+                                  ygm_device_result* out) {
+  if (!c || !out || ((uintptr_t)d_versions & 15u)) return YGM_EINVAL;
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  (void)hipSetDevice(c->device);
+  uint64_t sb = 0, vb = 0;
+  if (n_docs) {
+    c->stats.host_syncs++;
+    HIPCHK(hipMemcpyAsync(c->h_meta, d_state_off + n_docs, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync((uint64_t*)c->h_meta + 1, d_version_off + n_docs, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(&sb, c->h_meta, 8); memcpy(&vb, (uint64_t*)c->h_meta + 1, 8);
+  }
+  ygm_device_result r1;
+  const double k0 = c->stats.kernel_ms;
+  int e = snapshot_dev(c, d_states, sb, d_state_off, n_docs, s, &r1, YGM_F_SNAP_STATE | YGM_F_SNAP_NOGC);
+  if (e || (e = pack_snapshots(c, s, r1, n_docs))) return e;
+  const double k1 = c->stats.kernel_ms;
+  const uint64_t total = r1.payload_bytes + vb + 32ull * n_docs + 64;
+  const uint32_t nb = (n_docs + 255) / 256;
+  if (!c->vr_out.ensure(total + 64) || !c->vr_off.ensure(8ull * n_docs + 8) || !c->vr_len.ensure(8ull * n_docs + 8) ||
+      !c->vr_st.ensure(4ull * n_docs + 4) || !c->vr_pk.ensure(total + 64) || !c->vr_pkoff.ensure(8ull * n_docs + 16) ||
+      !c->s2_bsum.ensure(8ull * nb + 16))
+    return YGM_ENOMEM;
+  HIPCHK(hipEventRecord(c->e2, s));
+  if (ygm_k_launch_ver_cut(c->s2_data.as<uint8_t>(), c->s2_off.as<uint64_t>(), c->s2_st.as<int32_t>(), d_versions, d_version_off, n_docs,
+                           c->flags, c->vr_out.as<uint8_t>(), total, c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(),
+                           c->vr_st.as<int32_t>(), s))
+    return YGM_EDEVICE;
+  HIPCHK(hipEventRecord(c->e3, s));
+  uint64_t xb = 0;
+  if (n_docs) {
+    if (ygm_k_launch_pack(c->vr_out.as<uint8_t>(), c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), n_docs,
+                          c->s2_bsum.as<uint64_t>(), c->vr_pk.as<uint8_t>(), c->vr_pkoff.as<uint64_t>(), s))
+      return YGM_EDEVICE;
+    HIPCHK(hipMemcpyAsync(c->vr_pkoff.as<uint64_t>() + n_docs, c->s2_bsum.as<uint64_t>() + nb, 8, hipMemcpyDeviceToDevice, s));
+    xb = read_u64(c, s, c->vr_pkoff.as<uint64_t>() + n_docs, e);
+    if (e) return e;
+    if (xb > total) return YGM_EDEVICE;
+  } else HIPCHK(hipMemsetAsync(c->vr_pkoff.p, 0, 8, s));
+  HIPCHK(hipMemsetAsync(c->vr_pk.as<uint8_t>() + xb, 0, 64, s));   // (the snapshot kernels' tail padding)
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->e2, c->e3) == hipSuccess) c->stats.kernel_ms += ms;
+  if ((e = snapshot_dev(c, c->vr_pk.as<uint8_t>(), xb, c->vr_pkoff.as<uint64_t>(), n_docs, s, out, 0, nullptr, 0, d_restored_opt))) return e;
+  if (n_docs && ygm_k_launch_v2_status(c->vr_st.as<int32_t>(), n_docs, out->status, out->len, s)) return YGM_EDEVICE;
+  HIPCHK(hipStreamSynchronize(s));
+  if (getenv("YGM_VERSION_TIMES"))   // (tools/version_probe.py: the three stages' HIP-event times)
+    fprintf(stderr, "ygm version restore: docs %u snapshot_nogc_ms %.3f cut_ms %.3f snapshot_restored_ms %.3f\n", n_docs, k1 - k0, (double)ms,
+            c->stats.kernel_ms - k1 - (double)ms);
   return YGM_OK;
 }
 
@@ -1260,10 +1331,11 @@ struct Chunk {   // documents [d0, d1): merge updates [u0, u1) / SV-diff documen
 struct HostCall {
   int mode;   // 0 sv, 1 diff, 2 merge, 3 snapshot, 4 contains (second arena in the sv slots); update V2: 5 merge, 6 diff,
               // 7 sv, 8 V1 -> V2, 9 V2 -> V1; 10 sync step2 (states + state vectors); 11 / 12 the shared-state diff /
-              // step2 (host_shared_call: n_docs states, n_upd asks, upd_doc = the asks' states)
+              // step2 (host_shared_call: n_docs states, n_upd asks, upd_doc = the asks' states); 13 version take, 14 version
+              // restore (states + versions in the sv slots, restored_opt as opt)
   const uint8_t* arena; const uint64_t* off; const uint32_t* upd_doc; const uint8_t* sv_arena; const uint64_t* sv_off;
   uint32_t n_upd, n_docs;
-  const uint8_t* opt = nullptr;   // modes 3 / 10: n_docs option bytes, mode 12: one per state (null: none); each chunk stages its slice
+  const uint8_t* opt = nullptr;   // modes 3 / 10 / 14: n_docs option bytes, mode 12: one per state (null: none); each chunk stages its slice
 };
 }  // namespace
 
@@ -1311,7 +1383,7 @@ static void par_for(size_t n, F f) {
 // CPU copy of a chunk's inputs into the stage's pinned buffer, then the async H2D copies
 static bool is_merge(int mode) { return mode == 2 || mode == 5; }
 static int chunk_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
-  const bool two = H.mode == 1 || H.mode == 4 || H.mode == 6 || H.mode == 10;   // a second arena per document (diff: state vectors, contains: updates)
+  const bool two = H.mode == 1 || H.mode == 4 || H.mode == 6 || H.mode == 10 || H.mode == 14;   // a second arena per document (diff: state vectors, contains: updates, restore: versions)
   const uint32_t nd = C.d1 - C.d0;
   const uint64_t a0 = is_merge(H.mode) ? H.off[C.u0] : H.off[C.d0], a1 = is_merge(H.mode) ? H.off[C.u1] : H.off[C.d1];
   const uint64_t bytes = a1 - a0, ab = (bytes + 64 + 15) & ~15ull;
@@ -1377,6 +1449,10 @@ static int chunk_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint64
                                                             C.u1 - C.u0, nd, nullptr, &dr);
   else if (H.mode == 4) e = ygm_contains_v1_device(k, k->arena.as<uint8_t>(), k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
                                                    k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
+  else if (H.mode == 13) e = ygm_version_take_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
+  else if (H.mode == 14) e = ygm_version_restore_v1_device(k, k->arena.as<uint8_t>(), k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
+                                                           k->sv_offs.as<uint64_t>(), H.opt && nd ? k->opt.as<uint8_t>() : nullptr, nd,
+                                                           nullptr, &dr);
   else if (H.mode == 3) e = ygm_snapshot_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
                                                         H.opt && nd ? k->opt.as<uint8_t>() : nullptr, nd, nullptr, &dr);
   else if (H.mode == 10) e = ygm_sync_step2_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
@@ -1697,7 +1773,7 @@ int ygm_merge_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, cons
 static int host_doc_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena,
                          const uint64_t* sv_off, uint32_t n_docs, ygm_result* out, const uint8_t* opt = nullptr) {
   if (!c || !out || (n_docs && (!arena || !doc_off))) return YGM_EINVAL;
-  const bool two = mode == 1 || mode == 4 || mode == 6 || mode == 10;
+  const bool two = mode == 1 || mode == 4 || mode == 6 || mode == 10 || mode == 14;
   if (two && n_docs && (!sv_arena || !sv_off)) return YGM_EINVAL;
   for (uint32_t d = 0; d < n_docs; d++) {
     if (doc_off[d + 1] < doc_off[d]) return YGM_EINVAL;
@@ -1711,6 +1787,14 @@ static int host_doc_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint6
 int ygm_contains_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* updates, const uint64_t* update_off,
                     uint32_t n_docs, ygm_result* out) {
   return host_doc_call(c, 4, states, state_off, updates, update_off, n_docs, out);
+}
+
+int ygm_version_take_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, 13, states, state_off, nullptr, nullptr, n_docs, out);
+}
+int ygm_version_restore_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* versions, const uint64_t* version_off,
+                           const uint8_t* restored_opt, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, 14, states, state_off, versions, version_off, n_docs, out, restored_opt);
 }
 
 int ygm_snapshot_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {

@@ -53,6 +53,7 @@ constexpr int ST_UNSUP = 9;   // YGM_EUNSUPPORTED
 constexpr int ST_PEND = 64;   // internal: the output is [state, pendingDs, pending structs] for the merge kernels
 constexpr uint32_t F_SNAP_STATE = 16u;   // YGM_F_SNAP_STATE: a pending document's output is its integrated state
 constexpr uint32_t F_SNAP_NOGC = 32u;    // internal, per document (option bit YGM_DOC_NO_GC): a Y.Doc({gc: false}), no tryGcDeleteSet
+constexpr uint32_t F_SNAP_VERSION = 64u; // internal to ygm_version_take_v1: the output is the encoded Snapshot V1 (encode_version)
 constexpr uint32_t OPT_NO_GC = 1u;       // YGM_DOC_NO_GC: the only bit of a document's option byte (any other: YGM_EINVAL)
 // a document's flags from the batch's and its option byte (opt null: every byte 0); false: a bit outside the options
 YDEV bool doc_flags(uint32_t flags, const uint8_t* opt, uint32_t d, uint32_t& out) {
@@ -745,8 +746,11 @@ struct Doc {
       for (uint32_t i = 0; i < m; i++) write_item(o, seq[i]);
       if (o.n + 64u > o.cap) { fail(ST_NOMEM); return; }
     }
-    // delete set from the struct store (createDeleteSetFromStructStore, Y@10600): store insertion order
-    // (13.5 writeDeleteSet keeps the Map order; 13.6 sorts clients descending)
+    encode_ds(o);
+  }
+  // delete set from the struct store (createDeleteSetFromStructStore, Y@10600): store insertion order
+  // (13.5 writeDeleteSet keeps the Map order; 13.6 sorts clients descending)
+  YDEV void encode_ds(OutCap& o) {
     uint32_t nds = 0;
     for (uint32_t k = 0; k < n_cl; k++) {
       if (!cl[k].ni) continue;
@@ -770,6 +774,24 @@ struct Doc {
         while (i < m && deleted(seq[i])) len += it[seq[i++]].len;
         o.vu(c0); o.vu(len);
       }
+      if (o.n + 64u > o.cap) { fail(ST_NOMEM); return; }
+    }
+  }
+  // Y.encodeSnapshot(Y.snapshot(doc)) (F_SNAP_VERSION): writeDeleteSet of the store's delete set -- the section
+  // encode_state ends with -- then writeStateVector: a count and (client, next clock) pairs, in the store's insertion
+  // order in 13.5 (writeStateVector iterates the Map), client-descending otherwise (13.6 sorts)
+  YDEV void encode_version(OutCap& o) {
+    encode_ds(o);
+    if (err) return;
+    uint32_t nc = 0;
+    for (uint32_t k = 0; k < n_cl; k++) nc += cl[k].ni > 0 ? 1u : 0u;
+    o.vu(nc);
+    for (uint32_t r = 0; r < n_cl; r++) {
+      int32_t k = -1;
+      if (flags & F_COMPAT_135) { for (uint32_t j = 0; j < n_cl; j++) if (cl[j].ins == (int32_t)r) k = (int32_t)j; }
+      else k = (int32_t)(n_cl - 1 - r);
+      if (k < 0 || !cl[k].ni) continue;
+      o.vu(cl[k].id); o.vu(cl[k].state);
       if (o.n + 64u > o.cap) { fail(ST_NOMEM); return; }
     }
   }
@@ -818,7 +840,7 @@ struct Doc {
   YDEV uint32_t encode() {
     if ((!n_rest && !n_pds) || (flags & F_SNAP_STATE)) {
       OutCap o{out, 0, cap_out};
-      encode_state(o);
+      if (flags & F_SNAP_VERSION) encode_version(o); else encode_state(o);
       if (err) return 0;
       if (o.n > cap_out) { fail(ST_NOMEM); return 0; }
       return o.n;

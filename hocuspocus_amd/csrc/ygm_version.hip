@@ -1,0 +1,110 @@
+// ygm_version.hip -- version history (ygm_version_restore_v1): the cut kernel between the two snapshot passes.
+//   k_ver_cut : one wave per document.  The walk over S (the packed no-GC snapshot) finds struct boundaries one
+//               after the other, so it is wave-uniform (every lane holds the same cursor, in registers); what it
+//               finds is long contiguous runs -- a block's kept prefix, the version's delete set -- which the wave
+//               copies in 16-byte pieces at any source / destination phase, bytes only at a run's ragged ends.  The
+//               version's state vector (at most ver::MAX_SV entries) sits in LDS; a block's client is looked up by
+//               the whole wave, lane l testing entries l, l + 64, ..., then one ballot.
+// Reads are aligned 16-byte pieces: up to 31 bytes past a run's end, inside the 64 readable bytes that follow each
+// arena (pack_snapshots pads S; the host API pads the versions, the device form asks for it).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "ygm_common.hpp"
+#include "ygm_version.hpp"
+
+namespace ygm {
+
+constexpr int VR_NT = 64;
+
+YDEV uint64_t vr_fsh(uint64_t a, uint64_t b, uint32_t s) { return s ? (a >> s) | (b << (64u - s)) : a; }
+
+struct WaveW {
+  uint32_t l;
+  YDEV uint32_t lane() const { return l; }
+  YDEV int32_t find(const ver::SvEnt* t, uint32_t n, uint32_t client) const {
+    for (uint32_t b = 0; b < n; b += VR_NT) {
+      const uint32_t i = b + l;
+      const unsigned long long m = __ballot(i < n && t[i].client == client);
+      if (m) return (int32_t)(b + (uint32_t)__ffsll((long long)m) - 1u);
+    }
+    return -1;
+  }
+  // one lane stores, the wave (the whole workgroup) sees it after the barrier
+  YDEV void put(ver::SvEnt* t, uint32_t i, uint32_t client, uint32_t clock) const {
+    if (l == 0) { t[i].client = client; t[i].clock = clock; }
+    __syncthreads();
+  }
+  // d[0, n) = s[0, n): bytes up to the destination's 16-byte boundary, then aligned 16-byte stores whose source is
+  // two aligned 16-byte loads shifted by its phase (one load when the phases agree), then the last bytes
+  YDEV void copy(uint8_t* d, const uint8_t* s, uint32_t n) const {
+    uint32_t head = (uint32_t)(0u - (uint32_t)(uintptr_t)d) & 15u;
+    if (head > n) head = n;
+    if (l < head) d[l] = s[l];
+    d += head; s += head; n -= head;
+    const uint32_t nch = n >> 4, ph = (uint32_t)(uintptr_t)s & 15u;
+    const uint4* sa = (const uint4*)(s - ph);
+    uint4* da = (uint4*)d;
+    if (ph == 0) {
+      for (uint32_t c = l; c < nch; c += VR_NT) da[c] = sa[c];
+    } else {
+      const uint32_t sh = 8u * (ph & 7u);
+      for (uint32_t c = l; c < nch; c += VR_NT) {
+        const uint4 lo = sa[c], hi = sa[c + 1];
+        const uint64_t q0 = (uint64_t)lo.x | ((uint64_t)lo.y << 32), q1 = (uint64_t)lo.z | ((uint64_t)lo.w << 32);
+        const uint64_t q2 = (uint64_t)hi.x | ((uint64_t)hi.y << 32), q3 = (uint64_t)hi.z | ((uint64_t)hi.w << 32);
+        const uint64_t a = ph < 8 ? q0 : q1, b = ph < 8 ? q1 : q2, e = ph < 8 ? q2 : q3;
+        const uint64_t r0 = vr_fsh(a, b, sh), r1 = vr_fsh(b, e, sh);
+        da[c] = make_uint4((uint32_t)r0, (uint32_t)(r0 >> 32), (uint32_t)r1, (uint32_t)(r1 >> 32));
+      }
+    }
+    const uint32_t t0 = nch << 4;
+    if (l < n - t0) d[t0 + l] = s[t0 + l];
+  }
+};
+
+// Document d's slot: al16(s_off[d] + v_off[d] + 32 d), capacity |S| + |version| + 16 (the header and the delete set
+// come from the version, every block from S and no longer than there).  A document whose snapshot was refused
+// (s_st) keeps that status.
+__global__ __launch_bounds__(VR_NT) void k_ver_cut(const uint8_t* __restrict__ S, const uint64_t* __restrict__ s_off,
+                                                  const int32_t* __restrict__ s_st, const uint8_t* __restrict__ V,
+                                                  const uint64_t* __restrict__ v_off, uint32_t n_docs, uint32_t flags,
+                                                  uint8_t* __restrict__ out, uint64_t out_total, uint64_t* __restrict__ out_off,
+                                                  uint64_t* __restrict__ out_len, int32_t* __restrict__ status) {
+  __shared__ ver::SvEnt tbl[ver::MAX_SV];
+  const uint32_t d = blockIdx.x;
+  if (d >= n_docs) return;
+  const uint64_t a = s_off[d], b = s_off[d + 1], va = v_off[d], vb = v_off[d + 1];
+  const uint64_t slot = (a + va + 32ull * d + 15ull) & ~15ull;
+  int st = s_st[d];
+  uint32_t ol = 0;
+  if (st == ST_OK) {
+    if (b < a || vb < va || b - a >= (1ull << 30) || vb - va >= (1ull << 30)) st = ST_INVAL;
+    else {
+      const uint32_t sn = (uint32_t)(b - a), vn = (uint32_t)(vb - va), cap = sn + vn + 16u;
+      if (slot + cap > out_total) st = ST_NOMEM;
+      else st = ver::cut_doc(WaveW{threadIdx.x}, S + a, sn, V + va, vn, flags, tbl, out + slot, cap, ol);
+    }
+  }
+  if (threadIdx.x == 0) { out_off[d] = slot; out_len[d] = st == ST_OK ? ol : 0u; status[d] = st; }
+}
+
+}  // namespace ygm
+
+using namespace ygm;
+
+extern "C" {
+
+int ygm_k_launch_ver_cut(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint8_t* V, const uint64_t* v_off,
+                         uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t out_total, uint64_t* out_off, uint64_t* out_len,
+                         int32_t* status, hipStream_t s) {
+  if (n_docs == 0) return 0;
+  hipLaunchKernelGGL(k_ver_cut, dim3(n_docs), dim3(VR_NT), 0, s, S, s_off, s_st, V, v_off, n_docs, flags, out, out_total, out_off, out_len,
+                     status);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", __func__, hipGetErrorString(e)); return -1; }
+  return 0;
+}
+
+}  // extern "C"

@@ -75,7 +75,8 @@ EXPORTS = ("ygm_open", "ygm_close", "ygm_merge_v1", "ygm_diff_v1", "ygm_sv_from_
            "ygm_diff_shared_v1", "ygm_sync_step2_shared_v1", "ygm_diff_shared_v1_device",
            "ygm_sync_step2_shared_v1_device",
            "ygm_snapshot_opts_v1", "ygm_sync_step2_opts_v1", "ygm_sync_step2_shared_opts_v1",
-           "ygm_snapshot_opts_v1_device", "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device")
+           "ygm_snapshot_opts_v1_device", "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device",
+           "ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device")
 
 
 def lib():
@@ -125,7 +126,14 @@ def lib():
         L.ygm_sync_step2_opts_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
         L.ygm_sync_step2_shared_opts_v1_device.argtypes = [vp, vp, u64, vp, vp, u32, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
         for f in ("ygm_snapshot_opts_v1", "ygm_sync_step2_opts_v1", "ygm_sync_step2_shared_opts_v1", "ygm_snapshot_opts_v1_device",
-                  "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device"):
+                  "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device",
+           "ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device"):
+            getattr(L, f).restype = i32
+        L.ygm_version_take_v1.argtypes = [vp, vp, vp, u32, ctypes.POINTER(_Result)]
+        L.ygm_version_restore_v1.argtypes = [vp, vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
+        L.ygm_version_take_v1_device.argtypes = [vp, vp, u64, vp, u32, vp, ctypes.POINTER(_DevResult)]
+        L.ygm_version_restore_v1_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
+        for f in ("ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device"):
             getattr(L, f).restype = i32
         L.ygm_merge_v2.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
         L.ygm_diff_v2.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
@@ -477,6 +485,56 @@ class Engine:
         if st != OK:
             raise YjsError(st)
         return [(s, None if s != OK else b == b"\x01") for s, b in self._unpack(res)]
+
+    # ------------------------------------------------------------ version history
+    def take_version_batch(self, states):
+        """Versions of stored documents: Y.encodeSnapshot(Y.snapshot(doc)) for doc = Y.applyUpdate(new Y.Doc(), state)
+        (ygm_version_take_v1) -> list of (status, bytes | None).  A state with pending parts is seen through its
+        integrated part, as Y.snapshot sees the store."""
+        arena, off = _pack([bytes(s) for s in states])
+        res = _Result()
+        st = lib().ygm_version_take_v1(self._ctx, arena or None, _ptr(off), len(states), ctypes.byref(res))
+        if st != OK:
+            raise YjsError(st)
+        return self._unpack(res)
+
+    def restore_version_batch(self, states, versions, opts=None):
+        """Old versions of gc: false documents: Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc,
+        Y.decodeSnapshot(version), newDoc)) for doc = Y.applyUpdate(new Y.Doc({gc: false}), state)
+        (ygm_version_restore_v1) -> list of (status, bytes | None).  opts as snapshot_batch, one per pair: DOC_NO_GC /
+        True restores into new Y.Doc({gc: false}).  To restore several versions of one document pass its state once
+        per version."""
+        if len(states) != len(versions):
+            raise ValueError("one version per state")
+        sa, so = _pack([bytes(s) for s in states])
+        va, vo = _pack([bytes(v) for v in versions])
+        res = _Result()
+        o = _opts(opts, len(states))
+        st = lib().ygm_version_restore_v1(self._ctx, sa or None, _ptr(so), va or None, _ptr(vo), _ptr(o) if o is not None and len(o) else None,
+                                          len(states), ctypes.byref(res))
+        if st != OK:
+            raise YjsError(st)
+        return self._unpack(res)
+
+    def version_take_device(self, d_states, states_bytes, d_state_off, n_docs, stream=0) -> "DeviceResult":
+        """Device-resident take batch (ygm_version_take_v1_device)."""
+        r = _DevResult()
+        st = lib().ygm_version_take_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off), n_docs,
+                                              stream or None, ctypes.byref(r))
+        if st != OK:
+            raise YjsError(st)
+        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+
+    def version_restore_device(self, d_states, d_state_off, d_versions, d_version_off, n_docs, stream=0, d_restored_opt=0) -> "DeviceResult":
+        """Device-resident restore batch (ygm_version_restore_v1_device): both arenas followed by TAIL_PAD readable
+        bytes, d_versions 16-byte aligned; d_restored_opt: a device pointer / tensor of n_docs option bytes (0: none)."""
+        r = _DevResult()
+        none = d_restored_opt is None or (not hasattr(d_restored_opt, "data_ptr") and not d_restored_opt)
+        st = lib().ygm_version_restore_v1_device(self._ctx, _dptr(d_states), _dptr(d_state_off), _dptr(d_versions), _dptr(d_version_off),
+                                                 None if none else _dptr(d_restored_opt, n_docs), n_docs, stream or None, ctypes.byref(r))
+        if st != OK:
+            raise YjsError(st)
+        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
 
     def snapshot_device(self, d_arena, arena_bytes, d_doc_off, n_docs, stream=0, d_doc_opt=0) -> "DeviceResult":
         """Device-resident snapshot batch; d_doc_opt: a device pointer / tensor of n_docs option bytes (0: none)."""

@@ -57,6 +57,9 @@ extern "C" {
 #define YGM_F_KEEP_SUB 4u     /* internal to ygm_sync_step2_v1: diffs keep each struct's parentSub bit (0x20) */
 #define YGM_F_SNAP_STATE 16u  /* internal to ygm_contains_v1: such a state's snapshot is its integrated part alone
                                  (Y.snapshot(doc): the store's state vector and delete set) */
+#define YGM_F_SNAP_NOGC 32u   /* internal to ygm_version_restore_v1: every document of the batch is snapshotted as a
+                                 Y.Doc({gc: false}) (what YGM_DOC_NO_GC sets per document) */
+#define YGM_F_SNAP_VERSION 64u /* internal to ygm_version_take_v1: the snapshot batch ends with the encoded Snapshot V1 */
 
 typedef struct ygm_ctx ygm_ctx;
 
@@ -99,7 +102,8 @@ typedef struct {
                                           (finished by merging [state, pendingDs, pending structs] on the GPU) */
   uint64_t docs_snapshot;              /* documents the snapshot kernels were run on (ygm_snapshot_v1, and the snapshots
                                           inside ygm_contains_v1 / ygm_sync_step2_v1 / the shared-state forms: there one
-                                          per state and chunk, not one per ask) */
+                                          per state and chunk, not one per ask; one per document of
+                                          ygm_version_take_v1, two per document of ygm_version_restore_v1) */
 } ygm_stats_t;
 
 /* Opens the engine on HIP device `device` (one context per GPU; contexts are
@@ -176,6 +180,43 @@ int ygm_sync_step2_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state
  * that leaves pending parts takes the three-way merge, of which only the state part depends on the option. */
 int ygm_sync_step2_opts_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *state_opt,
                            const uint8_t *sv_arena, const uint64_t *sv_off, uint32_t n_docs, ygm_result *out);
+
+/* ---- version history: batched Y.snapshot and Y.createDocFromSnapshot --------
+ * What gc: false is for: a version per store window, and an old version shown to a client.
+ *
+ * ygm_version_take_v1: Y.encodeSnapshot(Y.snapshot(doc)), doc = Y.applyUpdate(new Y.Doc(), state) -- the encoded
+ * Snapshot V1: writeDeleteSet of the store's delete set, then writeStateVector.  states / state_off as
+ * ygm_snapshot_v1.  A state that leaves pending structs / a pending delete set is seen through its integrated part,
+ * as Y.snapshot(doc) sees the store.  The delete-set section is the one a snapshot ends with; the state vector is
+ * a count and (client, next clock) pairs, in the store's insertion order under YGM_F_COMPAT_135 (13.5's
+ * writeStateVector iterates the Map: clients integrated as 3 then 9 give ... 02 03 06 09 03) and client-descending
+ * otherwise (13.6 sorts; like the rest of the default mode, not pinned by vectors of a 13.6 bundle).  The delete set
+ * is the same with or without garbage collection, so there is no options form. */
+int ygm_version_take_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, uint32_t n_docs, ygm_result *out);
+/* ygm_version_restore_v1: Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), newDoc)),
+ * doc = Y.applyUpdate(new Y.Doc({gc: false}), state); newDoc = new Y.Doc(), or new Y.Doc({gc: false}) when
+ * restored_opt[d] has YGM_DOC_NO_GC (restored_opt: n_docs bytes or NULL; a byte with any other bit gives that
+ * document YGM_EINVAL and nothing else).  versions / version_off: one encoded Snapshot V1 per document.  Computed as
+ * the no-GC snapshot S of the state's integrated part, the cut of S at the version's clocks followed by the version's
+ * delete set (one parse: a straddled Item's content is shortened as ContentX.splice does, U+FFFD for a cut surrogate
+ * pair in both modes; a straddled GC struct stays whole, yjs splits only Items), and the snapshot of that update into
+ * newDoc.  A version that is not causally closed, or whose delete set reaches past the kept clocks, leaves pending
+ * parts there, answered as ygm_snapshot_v1 answers them.  A state's refusal (YGM_EUNSUPPORTED, YGM_EMALFORMED, ...)
+ * is the document's status.  Per document, the version gives:
+ *   truncated version                                              YGM_EMALFORMED
+ *   a varuint above 2^53                                           YGM_ERANGE
+ *   a non-minimal varuint in the version                           YGM_ENONCANON
+ *   a client repeated in its delete set or in its state vector     YGM_ENONCANON  (yjs would re-encode;
+ *                                                                  Y.encodeSnapshot never writes these)
+ *   a version clock above the state's clock for that client        YGM_EINVAL     (yjs throws)
+ *   a version client with clock > 0 that the state does not have   YGM_EINVAL     (yjs throws)
+ *   more than 4096 state-vector entries (or delete-set clients),
+ *   a client id past 32 bits                                       YGM_EUNSUPPORTED
+ * Bytes after the state vector are ignored, as decodeSnapshot ignores them.  Each refusal affects only its own
+ * document.  There is no form that restores many versions from one state: to restore several versions of one
+ * document, pass its state once per version. */
+int ygm_version_restore_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *versions,
+                           const uint64_t *version_off, const uint8_t *restored_opt, uint32_t n_docs, ygm_result *out);
 
 /* ---- shared-state forms: many state vectors answered from one state ---------
  * A reconnect storm sends many SyncStep1 messages for one document.  These forms take n_docs states and n_asks
@@ -304,6 +345,16 @@ int ygm_sync_step2_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t sta
                              ygm_device_result *out);
 int ygm_sync_step2_opts_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                                   const uint8_t *d_state_opt, const uint8_t *d_sv_arena, const uint64_t *d_sv_off,
+                                  uint32_t n_docs, void *stream, ygm_device_result *out);
+
+/* Version history, device-resident (ygm_version_take_v1 / ygm_version_restore_v1 above): two arenas as
+ * ygm_contains_v1_device, option bytes as ygm_snapshot_opts_v1_device (d_restored_opt NULL: none set).  The cut kernel
+ * reads aligned 16-byte pieces: d_versions must be 16-byte aligned (YGM_EINVAL otherwise) and, like d_states, be
+ * followed by 64 readable bytes. */
+int ygm_version_take_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
+                               uint32_t n_docs, void *stream, ygm_device_result *out);
+int ygm_version_restore_v1_device(ygm_ctx *ctx, const uint8_t *d_states, const uint64_t *d_state_off,
+                                  const uint8_t *d_versions, const uint64_t *d_version_off, const uint8_t *d_restored_opt,
                                   uint32_t n_docs, void *stream, ygm_device_result *out);
 
 /* Shared-state forms, device-resident: d_ask_doc (u32, n_asks entries) as ask_doc above; d_sv_off has n_asks + 1

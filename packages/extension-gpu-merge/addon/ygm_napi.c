@@ -292,6 +292,8 @@ static void job_execute(Job *j) {
   else if (j->op == 12) j->rc = ygm_sv_from_update_v2(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   else if (j->op == 13) j->rc = ygm_convert_v1_to_v2(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   else if (j->op == 14) j->rc = ygm_convert_v2_to_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
+  else if (j->op == 15) j->rc = ygm_version_take_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
+  else if (j->op == 16) j->rc = ygm_version_restore_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->opt, j->n_docs, &r);
   else j->rc = ygm_sv_from_update_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   if (j->rc != YGM_OK) return;
   /* results are context-owned: copy out before the next batch may reuse them */
@@ -442,7 +444,7 @@ static napi_value js_merge(napi_env env, napi_callback_info info) {
 
 /* diffMany(h, arena, lens, svArena, svLens) */
 static napi_value js_diff(napi_env env, napi_callback_info info) {
-  size_t argc = 6; napi_value argv[6];   /* (step2Many: an optional sixth argument, the states' option bytes) */
+  size_t argc = 6; napi_value argv[6];   /* (step2Many: an optional sixth argument, the states' option bytes; restoreVersionMany: the restored documents') */
   void *opd = NULL;
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
   if (argc < 5) { napi_throw_type_error(env, NULL, "diffMany(handle, arena, lens, svArena, svLens)"); return NULL; }
@@ -459,7 +461,7 @@ static napi_value js_diff(napi_env env, napi_callback_info info) {
   j->sv_off = lens_to_off((const uint32_t *)slens, j->n_docs);
   free(lens); free(slens);
   if (j->off[j->n_docs] != an || j->sv_off[j->n_docs] != sn) { job_free(j); napi_throw_range_error(env, NULL, "diffMany: lengths do not match arenas"); return NULL; }
-  if (j->op == 5 && get_opts(env, argc, argv, 5, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "step2Many: one option byte per state"); return NULL; }
+  if ((j->op == 5 || j->op == 16) && get_opts(env, argc, argv, 5, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "step2Many / restoreVersionMany: one option byte per state"); return NULL; }
   return submit(env, j, argv[0]);
 }
 
@@ -572,6 +574,10 @@ static napi_value init(napi_env env, napi_value exports) {
     { "svManyV2", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)12 },
     { "convertManyV1ToV2", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)13 },
     { "convertManyV2ToV1", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)14 },
+    /* version history: Y.encodeSnapshot(Y.snapshot(doc)) per state; Y.createDocFromSnapshot per (state, version)
+       [, option bytes of the restored documents] (ygm_version_take_v1 / ygm_version_restore_v1) */
+    { "takeVersionMany", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)15 },
+    { "restoreVersionMany", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)16 },
     { "stats", NULL, js_stats, NULL, NULL, NULL, napi_default, NULL },
     { "strerror", NULL, js_strerror, NULL, NULL, NULL, napi_default, NULL },
   };

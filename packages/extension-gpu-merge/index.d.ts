@@ -43,6 +43,13 @@ export declare class GpuEngine {
   snapshotMany (states: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** Y.snapshotContainsUpdate(Y.snapshot(doc), update), states being normalized (snapshotMany) states */
   containsMany (states: Uint8Array[], updates: Uint8Array[]): Promise<(boolean | YgmError)[]>
+  /** version history: Y.encodeSnapshot(Y.snapshot(doc)) of doc = Y.applyUpdate(new Y.Doc(), state); the single form shares a batch window */
+  takeVersion (state: Uint8Array): Promise<Uint8Array>
+  takeVersionMany (states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  /** Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), new Y.Doc(opts))) of doc =
+   *  Y.applyUpdate(new Y.Doc({ gc: false }), state); several versions of one document: its state once per version */
+  restoreVersion (state: Uint8Array, version: Uint8Array, opts?: DocOptions): Promise<Uint8Array>
+  restoreVersionMany (states: Uint8Array[], versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** the context's counters (ygm_stats_t), camel-cased: calls, docs, kernelMs, h2dMs, d2hMs, hostSyncs, docsPending,
    *  docsSnapshot (documents the snapshot kernels ran on: one per state for step2Shared, one per pair for step2Many), ... */
   stats (): Record<string, number>
@@ -70,6 +77,8 @@ export declare class GpuEnginePool {
   snapshot (update: Uint8Array, documentName?: string, opts?: DocOptions): Promise<Uint8Array>
   snapshotMany (names: string[], states: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   containsMany (names: string[], states: Uint8Array[], updates: Uint8Array[]): Promise<(boolean | YgmError)[]>
+  takeVersionMany (names: string[], states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  restoreVersionMany (names: string[], states: Uint8Array[], versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   stats (): Record<string, number>[]
   /** node-wide totals: every per-device counter summed over the pool, plus `devices` */
   statsTotal (): Record<string, number>
@@ -138,6 +147,11 @@ export declare class GpuMerge implements Extension {
   onStoreDocument (data: onStoreDocumentPayload): Promise<void>
   afterUnloadDocument (data: afterUnloadDocumentPayload): Promise<void>
   onDestroy (): Promise<void>
+  /** one version (yjs's encoded snapshot) per loaded document, one GPU batch; unloaded or refused documents are left out */
+  takeVersions (names: string[]): Promise<Map<string, Uint8Array>>
+  /** the documents as they were at the versions (Y.createDocFromSnapshot), one GPU batch, one settled result per entry;
+   *  a gc: true document's entry is rejected with "originDoc must not be garbage collected" */
+  restoreVersions (entries: { documentName: string, version: Uint8Array, gc?: boolean }[]): Promise<({ status: 'fulfilled', value: Uint8Array } | { status: 'rejected', reason: Error })[]>
   /** batched SyncStep1 responder over the captured state (snapshot + updates since) */
   syncResponder (): SyncResponder
   /** batched extension-redis fan-out over the same captured state */

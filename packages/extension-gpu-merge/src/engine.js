@@ -135,7 +135,8 @@ class GpuEngine {
     this.batchWindowMs = opts.batchWindowMs === undefined ? 2 : opts.batchWindowMs
     this.maxBatchDocs = opts.maxBatchDocs || 65536
     this.handle = loadAddon().open(this.device, this.flags)
-    this.batchers = { merge: new Batcher(this, 'merge'), diff: new Batcher(this, 'diff'), sv: new Batcher(this, 'sv'), snapshot: new Batcher(this, 'snapshot') }
+    this.batchers = { merge: new Batcher(this, 'merge'), diff: new Batcher(this, 'diff'), sv: new Batcher(this, 'sv'), snapshot: new Batcher(this, 'snapshot'),
+      takeVersion: new Batcher(this, 'takeVersion'), restoreVersion: new Batcher(this, 'restoreVersion') }
     this.timing = {}
     this._last = {}
     this.chain = Promise.resolve()
@@ -164,12 +165,16 @@ class GpuEngine {
         if (op === 'step2') return a.step2Many(this.handle, u.arena, u.lens, s.arena, s.lens, optBytes(jobs.map(j => j[2] || 0), jobs.length))
         return ({ diff: a.diffMany, contains: a.containsMany, diffV2: a.diffManyV2 })[op](this.handle, u.arena, u.lens, s.arena, s.lens)
       }
+      if (op === 'restoreVersion') {   // a job is [state, version, option byte]
+        const u = packBlobs(jobs.map(j => j[0])); const v = packBlobs(jobs.map(j => j[1]))
+        return a.restoreVersionMany(this.handle, u.arena, u.lens, v.arena, v.lens, optBytes(jobs.map(j => j[2] || 0), jobs.length))
+      }
       if (op === 'snapshot') {   // a job is an update, or { update, opt } for one with an option byte: both kinds share a window
         const u = packBlobs(jobs.map(j => j instanceof Uint8Array ? j : j.update))
         return a.snapshotMany(this.handle, u.arena, u.lens, optBytes(jobs.map(j => j instanceof Uint8Array ? 0 : j.opt), jobs.length))
       }
       const u = packBlobs(jobs)
-      const unary = { snapshot: a.snapshotMany, sv: a.svMany, svV2: a.svManyV2, v1ToV2: a.convertManyV1ToV2, v2ToV1: a.convertManyV2ToV1 }
+      const unary = { snapshot: a.snapshotMany, takeVersion: a.takeVersionMany, sv: a.svMany, svV2: a.svManyV2, v1ToV2: a.convertManyV1ToV2, v2ToV1: a.convertManyV2ToV1 }
       return unary[op](this.handle, u.arena, u.lens)
     }
     const p = this.chain.then(run, run)
@@ -243,6 +248,24 @@ class GpuEngine {
   async containsMany (states, updates) {
     const r = await this._run('contains', states.map((s, i) => [s, updates[i]]))
     return unpack(r).map(x => x instanceof Error ? x : x[0] === 1)
+  }
+
+  /**
+   * Version history.  takeVersion: Y.encodeSnapshot(Y.snapshot(doc)) of doc = Y.applyUpdate(new Y.Doc(), state);
+   * restoreVersion: Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), newDoc)) of
+   * doc = Y.applyUpdate(new Y.Doc({ gc: false }), state), newDoc = new Y.Doc() or, with { gc: false }, new
+   * Y.Doc({ gc: false }).  The single forms share a batch with the calls of the same window; the *Many forms are
+   * explicit batches (opts as snapshotMany's, one per pair).  To restore several versions of a document pass its
+   * state once per version.
+   */
+  takeVersion (state) { return this.batchers.takeVersion.push(state instanceof Uint8Array ? state : Uint8Array.from(state)) }
+  restoreVersion (state, version, { gc } = {}) { return this.batchers.restoreVersion.push([state, version, gc === false ? DOC_NO_GC : 0]) }
+  async takeVersionMany (states) { const r = await this._run('takeVersion', states); return unpack(r) }
+  async restoreVersionMany (states, versions, opts) {
+    if (versions.length !== states.length) throw new YgmError(8, 'one version per state')
+    const o = optBytes(opts, states.length)
+    const r = await this._run('restoreVersion', states.map((s, i) => [s, versions[i], o ? o[i] : 0]))
+    return unpack(r)
   }
 
   /** update format V2 (yjs providers other than Hocuspocus's V1 path): Y.mergeUpdatesV2 / Y.diffUpdateV2 /
@@ -349,6 +372,11 @@ class GpuEnginePool {
     return this._many(names, [states, Array.from(opts)], (e, a, o) => e.snapshotMany(a, o))
   }
   containsMany (names, states, updates) { return this._many(names, [states, updates], (e, a, b) => e.containsMany(a, b)) }
+  takeVersionMany (names, states) { return this._many(names, [states], (e, a) => e.takeVersionMany(a)) }
+  restoreVersionMany (names, states, versions, opts) {
+    if (!opts) return this._many(names, [states, versions], (e, a, b) => e.restoreVersionMany(a, b))
+    return this._many(names, [states, versions, Array.from(opts)], (e, a, b, o) => e.restoreVersionMany(a, b, o))
+  }
   stats () { return this.engines.map(e => e.stats()) }
   /**
    * Node-wide totals (the reference's server-wide counters, Hocuspocus.ts:138-160): every numeric field of the

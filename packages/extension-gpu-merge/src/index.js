@@ -136,6 +136,67 @@ class GpuMerge {
     return new RedisFanout({ engine: this._engine(), getState: r.getState, getDocOptions: r.getDocOptions, publish, identifier, prefix, windowMs })
   }
 
+  // the named documents' current states: base and log merged as the responder merges them (one merge batch for those
+  // with a log); null for a document that is not loaded
+  async _statesOf (names) {
+    const eng = this._engine()
+    const parts = names.map(n => { const e = this.docs.get(n); return e ? (e.base ? [e.base] : []).concat(e.log.toArray()) : null })
+    const multi = parts.map((p, i) => p && p.length > 1 ? i : -1).filter(i => i >= 0)
+    const merged = !multi.length ? [] : typeof eng.shardOf === 'function'
+      ? await eng.mergeMany(multi.map(i => names[i]), multi.map(i => parts[i])) : await eng.mergeMany(multi.map(i => parts[i]))
+    const out = parts.map(p => !p ? null : p.length === 1 ? p[0] : p.length === 0 ? Uint8Array.from([0, 0]) : null)
+    multi.forEach((i, k) => { out[i] = merged[k] })
+    return out
+  }
+
+  /**
+   * Version history (INTEGRATION.md "Version history").  takeVersions(names): one version -- yjs's encoded snapshot,
+   * Y.encodeSnapshot(Y.snapshot(doc)) -- per loaded document, in one GPU batch over the captured states (base and log
+   * merged as the responder merges them) -> Map name -> Uint8Array; a document that is not loaded, or whose state
+   * the engine refuses, is left out of the map.
+   */
+  async takeVersions (names) {
+    const eng = this._engine()
+    const states = await this._statesOf(names)
+    const idx = names.map((_, i) => i).filter(i => states[i] && !(states[i] instanceof Error))
+    const pooled = typeof eng.shardOf === 'function'
+    const res = !idx.length ? [] : pooled ? await eng.takeVersionMany(idx.map(i => names[i]), idx.map(i => states[i])) : await eng.takeVersionMany(idx.map(i => states[i]))
+    const out = new Map()
+    idx.forEach((i, k) => { if (!(res[k] instanceof Error)) out.set(names[i], new Uint8Array(res[k])) })
+    return out
+  }
+
+  /**
+   * restoreVersions([{ documentName, version, gc }]): per entry the update of the document as it was at `version`,
+   * Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), new Y.Doc({ gc }))) (gc default
+   * true), in one GPU batch.  Returns one settled result per entry, { status: 'fulfilled', value } or { status:
+   * 'rejected', reason }: a document that resolves to gc: true is rejected with yjs's own "originDoc must not be
+   * garbage collected", one that is not loaded or that the engine refuses with that error -- each without
+   * disturbing the other entries.  There is no CPU path.
+   */
+  async restoreVersions (entries) {
+    const eng = this._engine()
+    const out = new Array(entries.length)
+    const live = []
+    entries.forEach((e, i) => {
+      if (!this.docs.has(e.documentName)) out[i] = { status: 'rejected', reason: new Error('GpuMerge: document ' + e.documentName + ' is not loaded') }
+      else if (this._gcOf(e.documentName) !== false) out[i] = { status: 'rejected', reason: new Error('originDoc must not be garbage collected') }
+      else live.push(i)
+    })
+    if (live.length) {
+      const names = Array.from(new Set(live.map(i => entries[i].documentName)))
+      const states = await this._statesOf(names)
+      const stateOf = i => states[names.indexOf(entries[i].documentName)]
+      const ok = live.filter(i => { const s = stateOf(i); if (s instanceof Error || !s) { out[i] = { status: 'rejected', reason: s || new Error('no state') }; return false } return true })
+      const opts = ok.map(i => entries[i].gc === false ? 1 : 0)
+      const res = !ok.length ? [] : typeof eng.shardOf === 'function'
+        ? await eng.restoreVersionMany(ok.map(i => entries[i].documentName), ok.map(stateOf), ok.map(i => entries[i].version), opts)
+        : await eng.restoreVersionMany(ok.map(stateOf), ok.map(i => entries[i].version), opts)
+      ok.forEach((i, k) => { out[i] = res[k] instanceof Error ? { status: 'rejected', reason: res[k] } : { status: 'fulfilled', value: new Uint8Array(res[k]) } })
+    }
+    return out
+  }
+
   async onConfigure () { this._engine() }
 
   /** fetch -> (GPU merge of snapshot + log rows) -> Y.applyUpdate, as Database.onLoadDocument (Database.ts:44-50) */
