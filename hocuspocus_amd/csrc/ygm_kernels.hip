@@ -1201,7 +1201,9 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         for (int q = g; q < g + YGM_LN_FASTGROUP; q++) {
           const bool valid = ln_owns(l, q, k);
           bool hd;
-          slow[q] = !lean_parse_fast(F[q - g], us[q], un[q], rec[q], hd) && valid;
+          const bool fast = q == 0 ? lean_parse_fast<true>(F[q - g], us[q], un[q], valid, rec[q], hd)
+                                   : lean_parse_fast<false>(F[q - g], us[q], un[q], valid, rec[q], hd);
+          slow[q] = !fast && valid;
           hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
           hasd[q] = valid && hd;
         }
@@ -1240,8 +1242,9 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     if (l == 0) status[d] = (int)bad; wave_sync(); dit++; d = LN_AHEAD(1); continue;
 #endif
     if (!defer) {
-      // ---- clients, discovered in descending order (wave max over the unassigned records): a
-      //      record's block is its client's rank; lane c of `ctl` holds block c's client
+      // ---- clients: a record's block is its client's rank, descending; lane c of `ctl` holds block c's client.
+      //      All-fast documents of the narrow kernel: by first sight (below); every other document: discovered in
+      //      descending order (wave max over the unassigned records)
       uint32_t blk[LN_ROWS];
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) blk[q] = hs[q] ? 0xFFu : 0xFEu;
@@ -1252,26 +1255,65 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
       uint32_t fcl = 0, fcb[LN_ROWS];
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) fcb[q] = 0;
-      for (int it = 0; it <= LN_CMAX; it++) {
+      // All-fast documents: the vote by first sight.  Clients are discovered in log order -- the candidate is the
+      // client of the first record not yet assigned (the ballot's first lane, that lane's lowest unassigned slot),
+      // and the same record's clock is the block's first clock -- and the matching records get the order of sight
+      // as a provisional tag (8 t: the bit offset of the tag's entry in the table below).  The at most four ids are
+      // then ranked on the scalar unit (rank = the count of larger ids: block order stays client-descending) and the
+      // tags replaced by the ranks, one bit-field extract per row.  A fifth client ends it: the tags are dropped
+      // and the document takes the descending loop below, like every document that is not all-fast
+      bool sighted = false;   // (wave-uniform) the document was voted here: at most four clients, log-order placement
+      if (!WIDE && allfast) {
+        uint32_t cid[4] = {0u, 0u, 0u, 0u}, fck[4] = {0u, 0u, 0u, 0u};
+        bool more = true;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          const bool u0 = blk[0] == 0xFFu, u1 = blk[1] == 0xFFu, u2 = blk[2] == 0xFFu, u3 = blk[3] == 0xFFu;
+          const uint64_t m = __builtin_amdgcn_ballot_w64(u0 || u1 || u2 || u3);
+          if (m == 0) { more = false; break; }
+          const uint32_t fl = (uint32_t)__builtin_ctzll(m);
+          const uint32_t cand = rdlane(u0 ? rec[0].client : u1 ? rec[1].client : u2 ? rec[2].client : rec[3].client, fl);
+          const uint32_t fc = rdlane(u0 ? rec[0].clock : u1 ? rec[1].clock : u2 ? rec[2].clock : rec[3].clock, fl);
+          cid[t] = cand; fck[t] = fc; nC = (uint32_t)t + 1u;
+#pragma unroll
+          for (int q = 0; q < LN_ROWS; q++) {
+            const bool hit = blk[q] == 0xFFu && rec[q].client == cand;
+            blk[q] = hit ? 8u * (uint32_t)t : blk[q];
+            fcb[q] = hit ? fc : fcb[q];
+          }
+        }
+        if (more) more = __builtin_amdgcn_ballot_w64(blk[0] == 0xFFu || blk[1] == 0xFFu || blk[2] == 0xFFu || blk[3] == 0xFFu) != 0;
+        if (more) {   // a fifth client
+#pragma unroll
+          for (int q = 0; q < LN_ROWS; q++) blk[q] = hs[q] ? 0xFFu : 0xFEu;
+          nC = 0;
+        } else {
+          sighted = true;
+          // rank of tag t among the ids (distinct; an absent tag's id is 0, larger than none): lane r of ctl / fcl gets
+          // the tag's client and first clock.  Tags from the last down: an absent tag ranks nC, or nC - 1 beside a
+          // client 0, whose own write then comes after it
+          uint32_t tab = 0;
+#pragma unroll
+          for (int t = 3; t >= 0; t--) {
+            uint32_t r = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) if (j != t) r = lean_sadd_gt(r, cid[j], cid[t]);
+            tab |= r << (8 * t);
+            lean_wrlane2(ctl, cid[t], fcl, fck[t], r);
+          }
+          // (a row without structs keeps no tag: what the extract leaves there is never read -- every use of blk below
+          // is under hs)
+#pragma unroll
+          for (int q = 0; q < LN_ROWS; q++) blk[q] = __builtin_amdgcn_ubfe(tab, blk[q], 8u);
+        }
+      }
+      for (int it = 0; !sighted && it <= LN_CMAX; it++) {
         uint32_t mx = 0; bool any = false;
 #pragma unroll
         for (int q = 0; q < LN_ROWS; q++) { const bool un_ = blk[q] == 0xFFu; any |= un_; mx = max(mx, un_ ? rec[q].client : 0u); }
         if (__ballot(any) == 0) break;
         if (nC == (uint32_t)LN_CMAX) { defer = true; break; }
         const uint32_t cand = lane63(dpp_incl_max(mx));
-        if (!WIDE && allfast) {
-          bool hit = false;
-          uint32_t lc = 0;
-#pragma unroll
-          for (int q = LN_ROWS - 1; q >= 0; q--) {
-            const bool m = blk[q] == 0xFFu && rec[q].client == cand;
-            hit |= m; lc = m ? rec[q].clock : lc;
-          }
-          const uint32_t fc = lean_first_of(lc, __ballot(hit));   // (some record holds cand: the ballot is not empty)
-#pragma unroll
-          for (int q = 0; q < LN_ROWS; q++) fcb[q] = (blk[q] == 0xFFu && rec[q].client == cand) ? fc : fcb[q];
-          fcl = l == nC ? fc : fcl;
-        }
 #pragma unroll
         for (int q = 0; q < LN_ROWS; q++) if (blk[q] == 0xFFu && rec[q].client == cand) blk[q] = nC;
         ctl = l == nC ? cand : ctl;
@@ -1317,7 +1359,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         // ---- log-order placement (narrow kernel): every update is one Item of one character or a deletion, at
         //      most four clients.  A record's place in its block is idx, known where the record is: no sorted
         //      domain, no LDS
-        const bool logp = !WIDE && allfast && nC <= 4u;
+        const bool logp = sighted;
         if (logp) {
           // contiguity: a gap-free, overlap-free block is clock == first clock + idx for every record (what
           // "clock == the previous record's end" says by induction; the fast parse refuses clock 0xFFFFFFFF)

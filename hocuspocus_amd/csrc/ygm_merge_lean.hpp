@@ -26,9 +26,10 @@
 //           that depends on the window; only a row holding another shape runs lean_parse,
 //           the generic grammar (multi-struct, parents, ContentDeleted, longer strings),
 //           whose dependent byte reads cost an LDS round trip each
-//   clients distinct clients by wave vote, ranked descending (scalar).  Narrow kernel, every row fast: the
-//           vote also takes each block's first clock (the clock of its first record in log order: the
-//           ballot's first lane, one readlane) to lane c and to the block's records
+//   clients distinct clients by wave vote, in descending order (one wave max per client).  Narrow kernel, every row
+//           fast: the vote by first sight -- the candidate is the client of the first unassigned record in log
+//           order (one ballot, two readlanes: the second brings that record's clock, the block's first clock), a
+//           fifth client falls back to the descending vote, and the at most four ids are ranked on the scalar unit
 //   scan    log order: a record's index inside its block by one DPP scan of packed 8-bit per-block
 //           counts (a second one with more than four clients)
 //   place   one of two, wave-uniform per document:
@@ -353,8 +354,16 @@ YDEV void lean_fast_load(LB8* in, uint32_t s, uint32_t n, LFastIn& F) {
   const uint32_t t = s + (n > 3u ? n : 3u);
   F.tl = in[t - 3u]; F.td = in[t - 1u];
 }
-// true: R is the update's record (R.ok) and hasd whether its delete set is non-empty
-YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, LRec& R, bool& hasd) {
+#ifndef YGM_LN_KEYGATE
+#define YGM_LN_KEYGATE 1      // 0 (experiment): the parent-ykey shape is evaluated for every row
+#endif
+// true: R is the update's record (R.ok) and hasd whether its delete set is non-empty.
+// Called by the whole wave, one row at a time (valid: the lane's slot of this row holds an update).  The parent-ykey
+// shape is evaluated only for a row that has a valid lane with neither origin -- one ballot and one scalar branch
+// per row: in a debounce log that is update 0 alone, slot 0 of lane 0.  KEYROW (row 0) evaluates it without asking.
+// A lane the branch skips is not the parent-ykey shape (it has an origin, or it is not valid: n == 0, no shape fits)
+template <bool KEYROW>
+YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, LRec& R, bool& hasd) {
   const uint32_t (&d)[8] = F.d;
   const uint32_t H = lean_hmask(d);
   uint32_t Z = 0;
@@ -386,24 +395,25 @@ YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, LRec& R, boo
   const uint32_t ip = e + 1u;                  // the info byte: byte ck_n of cw (ck_n <= 5), the two bytes after it too
   const uint32_t x3 = (uint32_t)(cw >> (8u * (ck_n & 7u)));
   const uint32_t info = x3 & 0xFFu;
+  const uint32_t nsk = ((info >> 6) & 1u) + ((info >> 7) & 1u);
   // origin and/or right origin: the 2nd / 4th terminator from ip + 1 (a missing one lands past the window)
   const uint32_t pp = ip + 1u < 31u ? ip + 1u : 31u;
   const uint32_t t0 = (T >> pp) | 0x80000000u, t1 = t0 & (t0 - 1u), t2 = t1 & (t1 - 1u), t3 = t2 & (t2 - 1u);
-  const uint32_t nsk = ((info >> 6) & 1u) + ((info >> 7) & 1u);
-  uint32_t pl = nsk == 2u ? pp + lnctz(t3) + 1u : pp + lnctz(t1) + 1u;   // the string length's position
+  const uint32_t pl = nsk == 2u ? pp + lnctz(t3) + 1u : pp + lnctz(t1) + 1u;   // the string length's position
+  bool fits = pl + 3u == n;
   bool shape = nsk != 0u && (info & 0x3Fu) == 4u;
 #if YGM_LN_FASTPARENT
-  {
+  if (KEYROW || !YGM_LN_KEYGATE || __ballot(valid && nsk == 0u) != 0) {
     // parent ykey: info 0x04, parentInfo 1, key length, ASCII key
     const uint32_t lk = (x3 >> 16) & 0xFFu;
     const uint32_t kp = ip + 3u < 31u ? ip + 3u : 31u;
     const bool par = x3 << 16 == 0x01040000u && lk < 32u && ((HV >> kp) & ((1u << (lk & 31u)) - 1u)) == 0u;
-    pl = nsk == 0u ? ip + 3u + lk : pl;
+    fits = nsk == 0u ? ip + 6u + lk == n : fits;
     shape = shape || (nsk == 0u && par);
   }
 #endif
   // the length byte, one ASCII character and the delete set's count end the update
-  const bool item = bad == 0u && shape && pl + 3u == n && n <= 32u && F.tl == 1u && ((HV >> ((n - 2u) & 31u)) & 1u) == 0u;
+  const bool item = bad == 0u && shape && fits && n <= 32u && F.tl == 1u && ((HV >> ((n - 2u) & 31u)) & 1u) == 0u;
   const bool dsonly = b0 == 0u && n >= 2u && n <= 32u;
   R.ok = true;
   R.client = item ? client : 0u; R.clock = item ? clock : 0u; R.clen = item ? 1u : 0u;
@@ -529,8 +539,19 @@ YDEV uint32_t vlen32(uint32_t v) {   // bytes of the varuint encoding of v
   return 1u + (v > 0x7Fu ? 1u : 0u) + (v > 0x3FFFu ? 1u : 0u) + (v > 0x1FFFFFu ? 1u : 0u) + (v > 0xFFFFFFFu ? 1u : 0u);
 }
 // ---- log-order placement (narrow kernel; documents whose every update took the fast parse, <= 4 clients)
-// x of the first lane of the (non-empty) ballot m, wave-uniform
-YDEV uint32_t lean_first_of(uint32_t x, uint64_t m) { return rdlane(x, (uint32_t)__builtin_ctzll(m)); }
+// r + (a > b), unsigned, wave-uniform operands: one scalar compare and one add with carry.  (Written out: the compiler
+// keeps a uniform comparison as a lane mask and counts such masks with VALU selects and carries)
+YDEV uint32_t lean_sadd_gt(uint32_t r, uint32_t a, uint32_t b) {
+  asm("s_cmp_gt_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(r) : "s"(a), "s"(b) : "scc");
+  return r;
+}
+// lane `lane` (wave-uniform, < 64) of x and of y replaced by the wave-uniform vx and vy.  (One instruction reads one
+// SGPR, so the lane select goes through m0, which the compiler reserves: saved and put back in the same statement)
+YDEV void lean_wrlane2(uint32_t& x, uint32_t vx, uint32_t& y, uint32_t vy, uint32_t lane) {
+  uint32_t keep;
+  asm("s_mov_b32 %2, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tv_writelane_b32 %0, %3, m0\n\tv_writelane_b32 %1, %4, m0\n\ts_mov_b32 m0, %2"
+      : "+v"(x), "+v"(y), "=&s"(keep) : "s"(vx), "s"(vy), "s"(lane));
+}
 // 16-bit field b & 1 of a packed pair
 YDEV uint32_t lean_field16(uint32_t x, uint32_t b) { return (x >> (16u * (b & 1u))) & 0xFFFFu; }
 // Struct bytes of the earlier records of a record's block, for the blocks 2 HI and 2 HI + 1 as the two 16-bit
