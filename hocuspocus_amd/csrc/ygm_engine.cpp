@@ -567,6 +567,10 @@ int ygm_merge_v1_device_finish(ygm_ctx* c, ygm_device_result* out) {
     if (hipEventElapsedTime(&ms0, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms0;
     c->stats.docs_seq += n_seq;
   }
+  // YGM_TIER_COUNTS (testing knob): the call's raw tier counters, one stderr line (all 0 when the chain did not run)
+  if (getenv("YGM_TIER_COUNTS"))
+    fprintf(stderr, "ygm merge tiers: docs %u lean_defer %u wide_defer %u to_wave %u to_workgroup %u to_large %u to_seq %u\n", P.n_docs,
+            m.lean_defer, m.wide_defer, m.route_n, m.defer_count, m.fb_count, m.big_defer);
   const uint64_t extent = P.slot_total + m.cursor;
   c->stats.calls++; c->stats.docs += P.n_docs; c->stats.updates += P.n_upd;
   c->stats.docs_fast += n_gen - m.fb_count;   // finished by the wave / workgroup tiers (tier 4 counted above)

@@ -3855,6 +3855,14 @@ int ygm_k_launch_merge_lean_wide(const uint8_t* arena, const uint64_t* upd_off, 
   return launch_rc(__func__);
 }
 
+// YGM_WAVE_GRID / YGM_FAST_GRID (testing knobs, as YGM_V12F_GRID of the V2 transcoders): a positive value replaces the
+// cached resident count of the wave / workgroup kernel -- a small grid gives every wave or workgroup many documents,
+// so its LDS is reused across them.  Read on every launch (never cached); unset, zero or negative: the cached count.
+static uint32_t grid_knob(const char* name) {
+  if (const char* e = getenv(name)) { const long v = atol(e); if (v > 0 && v <= 0x7FFFFFFFl) return (uint32_t)v; }
+  return 0;
+}
+
 int ygm_k_launch_merge_wave(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs,
                             const unsigned int* n_dev, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
                             int32_t* status, void* meta, uint32_t* defer_list, uint32_t* fb_list, uint64_t out_cap, hipStream_t s) {
@@ -3862,7 +3870,8 @@ int ygm_k_launch_merge_wave(const uint8_t* arena, const uint64_t* upd_off, const
   // persistent: exactly the waves that are resident at once (LDS / VGPR occupancy x CUs), so no wave starts
   // its grid-stride share after the others have finished theirs; n_docs is the upper bound of the device count
   static std::atomic<uint32_t> cache[YGM_MAX_DEVICES];
-  const uint32_t resident = per_device(cache, [] { const char* g = getenv("YGM_WAVE_GRID"); return g ? (uint32_t)atoi(g) : resident_blocks(k_merge_wave, WAVE, 2048u); });
+  const uint32_t env = grid_knob("YGM_WAVE_GRID");
+  const uint32_t resident = env ? env : per_device(cache, [] { return resident_blocks(k_merge_wave, WAVE, 2048u); });
   const uint32_t grid = n_docs < resident ? n_docs : resident;
   hipLaunchKernelGGL(k_merge_wave, dim3(grid), dim3(WAVE), 0, s, arena, upd_off, doc_upd, docs, n_dev, n_docs,
                      flags, out, out_off, out_len, status, (DocMeta*)meta, defer_list, fb_list, out_cap);
@@ -3884,7 +3893,8 @@ int ygm_k_launch_merge_fast(const uint8_t* arena, const uint64_t* upd_off, const
                             int32_t* status, uint64_t slot_total, void* meta, uint32_t* fb_list, uint64_t out_cap, hipStream_t s) {
   if (n_docs == 0) return 0;
   static std::atomic<uint32_t> cache[YGM_MAX_DEVICES];   // persistent: the resident workgroups (see ygm_k_launch_merge_wave)
-  const uint32_t resident = per_device(cache, [] { const char* g = getenv("YGM_FAST_GRID"); return g ? (uint32_t)atoi(g) : resident_blocks(k_merge_fast, M_NT, 512u); });
+  const uint32_t env = grid_knob("YGM_FAST_GRID");
+  const uint32_t resident = env ? env : per_device(cache, [] { return resident_blocks(k_merge_fast, M_NT, 512u); });
   const uint32_t grid = n_docs < resident ? n_docs : resident;
   hipLaunchKernelGGL(k_merge_fast, dim3(grid), dim3(M_NT), 0, s, arena, upd_off, doc_upd, docs, n_dev, n_docs, flags, out, out_off, out_len,
                      status, slot_total, (DocMeta*)meta, fb_list, out_cap);
