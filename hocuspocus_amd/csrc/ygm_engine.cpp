@@ -73,6 +73,9 @@ int ygm_k_launch_pend_join(uint32_t P, const uint8_t* ad, const uint64_t* a_off,
 int ygm_k_launch_ver_cut(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint8_t* V, const uint64_t* v_off,
                          uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t out_total, uint64_t* out_off, uint64_t* out_len,
                          int32_t* status, hipStream_t s);
+int ygm_k_launch_ver_cut_gather(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint32_t* ix, const uint64_t* ask_base,
+                                const uint8_t* V, const uint64_t* v_off, uint32_t n_asks, uint32_t flags, uint8_t* out, uint64_t out_total,
+                                uint64_t* out_off, uint64_t* out_len, int32_t* status, hipStream_t s);
 int ygm_k_launch_pack(const uint8_t* src, const uint64_t* off, const uint64_t* len, const int32_t* status, uint32_t n, uint64_t* bsum,
                       uint8_t* dst, uint64_t* poff, hipStream_t s);
 int ygm_k_launch_doc_lean(int mode, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* doc_off, const uint8_t* sv_arena,
@@ -890,6 +893,81 @@ int ygm_version_restore_v1_device(ygm_ctx* c, const uint8_t* d_states, const uin
             c->stats.kernel_ms - k1 - (double)ms);
   return YGM_OK;
 }
+// k_snap's documents per wave for the states of a shared-state call (0: its default).  k_snap runs 16 documents per wave
+// and its lanes diverge by document.  The per-pair call over these asks would hold n_asks / n_states copies of a state
+// on neighbouring lanes (no divergence between them): the same number of waves here, with fewer documents each
+// (`parity`), is never more serial than that.  While the states fit one resident round of k_snap's waves with fewer per
+// wave still (`fill`: 256 CUs x 3 workgroups of 40 KB of LDS), they take that: the shared batch is the smaller one,
+// lanes are what it has to spare (profiles/step2_shared/README.md, profiles/version_shared/README.md)
+static uint32_t shared_snap_dpw(uint32_t n_states, uint32_t n_asks) {
+  if (n_asks <= n_states) return 0;
+  const uint32_t parity = std::max<uint32_t>(1u, (uint32_t)(16ull * n_states / n_asks));
+  const uint32_t fill = std::max<uint32_t>(1u, (n_states + 767u) / 768u);
+  return std::min(parity, fill);
+}
+// restore of many versions per state: (1) and (2) over the n_states states, each snapshotted once; the ask plan over the
+// packed snapshots' offsets (the checked state id per ask and the scan of the asks' snapshot lengths, what sizes the
+// cut's slots); (3) the gather cut over the n_asks asks, reading the packed snapshots in place; (4), (5) over the asks
+// with their option bytes.  The cut carries a refused id's YGM_EINVAL and a state's refusal to the ask
+int ygm_version_restore_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
+                                         uint32_t n_states, const uint8_t* d_versions, const uint64_t* d_version_off,
+                                         const uint32_t* d_ask_state, const uint8_t* d_restored_opt, uint32_t n_asks, void* stream,
+                                         ygm_device_result* out) {
+  if (!c || !out || ((uintptr_t)d_versions & 15u) || (n_states && !d_state_off) || (n_asks && (!d_version_off || !d_ask_state)))
+    return YGM_EINVAL;
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  (void)hipSetDevice(c->device);
+  ygm_device_result r1;
+  const double k0 = c->stats.kernel_ms;
+  int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_states, s, &r1, YGM_F_SNAP_STATE | YGM_F_SNAP_NOGC, nullptr,
+                       shared_snap_dpw(n_states, n_asks));
+  if (e || (e = pack_snapshots(c, s, r1, n_states))) return e;
+  const double k1 = c->stats.kernel_ms;
+  if ((e = ask_plan(c, s, c->s2_off.as<uint64_t>(), n_states, d_ask_state, n_asks))) return e;
+  uint64_t ab = 0, vb = 0;   // the asks' snapshot bytes, the versions' bytes: the one read that sizes the cut's slots
+  if (n_asks) {
+    c->stats.host_syncs++;
+    HIPCHK(hipMemcpyAsync(c->h_meta, c->ask_base.as<uint64_t>() + n_asks, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync((uint64_t*)c->h_meta + 1, d_version_off + n_asks, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(&ab, c->h_meta, 8); memcpy(&vb, (uint64_t*)c->h_meta + 1, 8);
+  }
+  const uint64_t total = ab + vb + 32ull * n_asks + 64;
+  const uint32_t nb = (n_asks + 255) / 256;
+  if (!c->vr_out.ensure(total + 64) || !c->vr_off.ensure(8ull * n_asks + 8) || !c->vr_len.ensure(8ull * n_asks + 8) ||
+      !c->vr_st.ensure(4ull * n_asks + 4) || !c->vr_pk.ensure(total + 64) || !c->vr_pkoff.ensure(8ull * n_asks + 16) ||
+      !c->s2_bsum.ensure(8ull * nb + 16))
+    return YGM_ENOMEM;
+  HIPCHK(hipEventRecord(c->e2, s));
+  if (ygm_k_launch_ver_cut_gather(c->s2_data.as<uint8_t>(), c->s2_off.as<uint64_t>(), c->s2_st.as<int32_t>(), c->ask_ix.as<uint32_t>(),
+                                  c->ask_base.as<uint64_t>(), d_versions, d_version_off, n_asks, c->flags, c->vr_out.as<uint8_t>(), total,
+                                  c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), s))
+    return YGM_EDEVICE;
+  HIPCHK(hipEventRecord(c->e3, s));
+  uint64_t xb = 0;
+  if (n_asks) {
+    if (ygm_k_launch_pack(c->vr_out.as<uint8_t>(), c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), n_asks,
+                          c->s2_bsum.as<uint64_t>(), c->vr_pk.as<uint8_t>(), c->vr_pkoff.as<uint64_t>(), s))
+      return YGM_EDEVICE;
+    HIPCHK(hipMemcpyAsync(c->vr_pkoff.as<uint64_t>() + n_asks, c->s2_bsum.as<uint64_t>() + nb, 8, hipMemcpyDeviceToDevice, s));
+    xb = read_u64(c, s, c->vr_pkoff.as<uint64_t>() + n_asks, e);
+    if (e) return e;
+    if (xb > total) return YGM_EDEVICE;
+  } else HIPCHK(hipMemsetAsync(c->vr_pkoff.p, 0, 8, s));
+  HIPCHK(hipMemsetAsync(c->vr_pk.as<uint8_t>() + xb, 0, 64, s));   // (the snapshot kernels' tail padding)
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->e2, c->e3) == hipSuccess) c->stats.kernel_ms += ms;
+  if ((e = snapshot_dev(c, c->vr_pk.as<uint8_t>(), xb, c->vr_pkoff.as<uint64_t>(), n_asks, s, out, 0, nullptr, 0, d_restored_opt))) return e;
+  // the carries: the cut's status over the restored document's, then (as the other shared forms) id and state to ask
+  if (n_asks && (ygm_k_launch_v2_status(c->vr_st.as<int32_t>(), n_asks, out->status, out->len, s) ||
+                 ygm_k_launch_ask_status(c->ask_ix.as<uint32_t>(), n_asks, c->s2_st.as<int32_t>(), out->status, out->len, s)))
+    return YGM_EDEVICE;
+  HIPCHK(hipStreamSynchronize(s));
+  if (getenv("YGM_VERSION_TIMES"))   // (tools/version_probe.py: the three stages' HIP-event times)
+    fprintf(stderr, "ygm version restore shared: states %u asks %u snapshot_nogc_ms %.3f cut_ms %.3f snapshot_restored_ms %.3f\n", n_states,
+            n_asks, k1 - k0, (double)ms, c->stats.kernel_ms - k1 - (double)ms);
+  return YGM_OK;
+}
 
 // Read-only SyncStep2: the states' Y.snapshot view first -- the snapshot batch with YGM_F_SNAP_STATE (a state that
 // leaves pending structs / a pending delete set is seen through its integrated part, as Y.snapshot(doc) sees the
@@ -1076,18 +1154,7 @@ int ygm_sync_step2_shared_opts_v1_device(ygm_ctx* c, const uint8_t* d_states, ui
   ygm_device_result r1;
   uint32_t P = 0, PA = 0;   // states the snapshot leaves pending; their asks
   uint64_t ptot[4] = {0, 0, 0, 0};
-  // k_snap runs 16 documents per wave and its lanes diverge by document.  The per-pair call over these asks would hold
-  // n_asks / n_states copies of a state on neighbouring lanes (no divergence between them): the same number of waves
-  // here, with fewer documents each (`parity`), is never more serial than that.  While the states fit one resident
-  // round of k_snap's waves with fewer per wave still (`fill`: 256 CUs x 3 workgroups of 40 KB of LDS), they take that:
-  // the shared batch is the smaller one, lanes are what it has to spare (profiles/step2_shared/README.md)
-  uint32_t dpw = 0;
-  if (n_asks > n_states) {
-    const uint32_t parity = std::max<uint32_t>(1u, (uint32_t)(16ull * n_states / n_asks));
-    const uint32_t fill = std::max<uint32_t>(1u, (n_states + 767u) / 768u);
-    dpw = std::min(parity, fill);
-  }
-  int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_states, s, &r1, 0, &P, dpw, d_state_opt);
+  int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_states, s, &r1, 0, &P, shared_snap_dpw(n_states, n_asks), d_state_opt);
   if (e) return e;
   if (P && n_asks) {
     if ((e = ask_plan(c, s, d_state_off, n_states, d_ask_state, n_asks))) return e;
@@ -1336,10 +1403,11 @@ struct HostCall {
   int mode;   // 0 sv, 1 diff, 2 merge, 3 snapshot, 4 contains (second arena in the sv slots); update V2: 5 merge, 6 diff,
               // 7 sv, 8 V1 -> V2, 9 V2 -> V1; 10 sync step2 (states + state vectors); 11 / 12 the shared-state diff /
               // step2 (host_shared_call: n_docs states, n_upd asks, upd_doc = the asks' states); 13 version take, 14 version
-              // restore (states + versions in the sv slots, restored_opt as opt)
+              // restore (states + versions in the sv slots, restored_opt as opt); 15 the shared-state version restore
+              // (host_shared_call: versions in the sv slots, restored_opt per ask)
   const uint8_t* arena; const uint64_t* off; const uint32_t* upd_doc; const uint8_t* sv_arena; const uint64_t* sv_off;
   uint32_t n_upd, n_docs;
-  const uint8_t* opt = nullptr;   // modes 3 / 10 / 14: n_docs option bytes, mode 12: one per state (null: none); each chunk stages its slice
+  const uint8_t* opt = nullptr;   // modes 3 / 10 / 14: n_docs option bytes, mode 12: one per state, mode 15: one per ask (null: none); each chunk stages its slice
 };
 }  // namespace
 
@@ -1619,7 +1687,10 @@ static int shared_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
   const uint64_t a0 = H.off[C.u0], bytes = H.off[C.u1] - a0, ab = (bytes + 64 + 15) & ~15ull;
   const uint64_t s0 = H.sv_off[C.d0], svb = H.sv_off[C.d1] - s0, sb = (svb + 64 + 15) & ~15ull;
   const uint64_t n_off = (uint64_t)ns + 1, n_sv = (uint64_t)na + 1;
-  const uint64_t n_opt = H.opt ? (uint64_t)ns : 0;   // the chunk's states' option bytes (a split state's byte in each of its chunks)
+  // the chunk's states' option bytes (a split state's byte in each of its chunks); the version restore's belong to the
+  // restored documents: the chunk's asks' bytes
+  const bool ask_opt = H.mode == 15;
+  const uint64_t n_opt = H.opt ? (uint64_t)(ask_opt ? na : ns) : 0;
   if (!k->h_in.ensure(ab + 8 * n_off + sb + 8 * n_sv + 4ull * na + n_opt + 64)) return YGM_ENOMEM;
   uint8_t* P = k->h_in.as<uint8_t>();
   if (bytes) par_memcpy(P, H.arena + a0, bytes);
@@ -1634,7 +1705,7 @@ static int shared_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
   uint32_t* ra = (uint32_t*)(q + sb + 8 * n_sv);
   for (uint32_t j = 0; j < na; j++) ra[j] = H.upd_doc[C.d0 + j] - C.u0;
   uint8_t* po = (uint8_t*)(ra + na);
-  if (n_opt) memcpy(po, H.opt + C.u0, n_opt);
+  if (n_opt) memcpy(po, H.opt + (ask_opt ? C.d0 : C.u0), n_opt);
   if (!k->arena.ensure(ab) || !k->offs.ensure(8 * n_off) || !k->sv_arena.ensure(sb) || !k->sv_offs.ensure(8 * n_sv) ||
       !k->docs.ensure(4ull * na + 4) || (n_opt && !k->opt.ensure(n_opt)))
     return YGM_ENOMEM;
@@ -1656,6 +1727,9 @@ static int shared_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint6
   if (H.mode == 12) e = ygm_sync_step2_shared_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
                                                              H.opt && ns ? k->opt.as<uint8_t>() : nullptr, ns, k->sv_arena.as<uint8_t>(),
                                                              k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
+  else if (H.mode == 15) e = ygm_version_restore_shared_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), ns,
+                                                                  k->sv_arena.as<uint8_t>(), k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(),
+                                                                  H.opt && na ? k->opt.as<uint8_t>() : nullptr, na, nullptr, &dr);
   else e = ygm_diff_shared_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), ns, k->sv_arena.as<uint8_t>(),
                                      k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
   if (e) return e;
@@ -1799,6 +1873,12 @@ int ygm_version_take_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state
 int ygm_version_restore_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* versions, const uint64_t* version_off,
                            const uint8_t* restored_opt, uint32_t n_docs, ygm_result* out) {
   return host_doc_call(c, 14, states, state_off, versions, version_off, n_docs, out, restored_opt);
+}
+
+int ygm_version_restore_shared_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, uint32_t n_states, const uint8_t* versions,
+                                  const uint64_t* version_off, const uint32_t* ask_state, const uint8_t* restored_opt, uint32_t n_asks,
+                                  ygm_result* out) {
+  return host_shared_call(c, 15, states, state_off, n_states, versions, version_off, ask_state, n_asks, out, restored_opt);
 }
 
 int ygm_snapshot_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {

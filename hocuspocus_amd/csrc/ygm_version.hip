@@ -1,10 +1,13 @@
-// ygm_version.hip -- version history (ygm_version_restore_v1): the cut kernel between the two snapshot passes.
+// ygm_version.hip -- version history (ygm_version_restore_v1 / ygm_version_restore_shared_v1): the cut kernel between the two snapshot passes.
 //   k_ver_cut : one wave per document.  The walk over S (the packed no-GC snapshot) finds struct boundaries one
 //               after the other, so it is wave-uniform (every lane holds the same cursor, in registers); what it
 //               finds is long contiguous runs -- a block's kept prefix, the version's delete set -- which the wave
 //               copies in 16-byte pieces at any source / destination phase, bytes only at a run's ragged ends.  The
 //               version's state vector (at most ver::MAX_SV entries) sits in LDS; a block's client is looked up by
 //               the whole wave, lane l testing entries l, l + 64, ..., then one ballot.
+//   k_ver_cut_gather : the same cut for asks that share states (ygm_version_restore_shared_v1): one wave per ask, ask a
+//               reading the packed snapshot of state ix[a] in place and its own version; the asks of one state sit on
+//               neighbouring workgroups, so all but the first read of S come from L2 / MALL.  S is only read.
 // Reads are aligned 16-byte pieces: up to 31 bytes past a run's end, inside the 64 readable bytes that follow each
 // arena (pack_snapshots pads S; the host API pads the versions, the device form asks for it).
 #include <hip/hip_runtime.h>
@@ -90,6 +93,38 @@ __global__ __launch_bounds__(VR_NT) void k_ver_cut(const uint8_t* __restrict__ S
   if (threadIdx.x == 0) { out_off[d] = slot; out_len[d] = st == ST_OK ? ol : 0u; status[d] = st; }
 }
 
+// The gather form.  ix / ask_base are the plan of k_ask_plan over s_off: the checked state id per ask (VR_ASK_BAD: an id
+// the plan refused, never used as an index -- the ask carries ST_INVAL) and the exclusive scan of the asks' snapshot
+// lengths.  Ask a's slot: al16(ask_base[a] + v_off[a] + 32 a), capacity |S| + |version| + 16 as above; an ask of a
+// refused id or of a refused state writes its offset, length 0 and status, nothing else.
+constexpr uint32_t VR_ASK_BAD = 0xFFFFFFFFu;   // (DW_ASK_BAD of the plan kernel, ygm_walk.hip)
+
+__global__ __launch_bounds__(VR_NT) void k_ver_cut_gather(const uint8_t* __restrict__ S, const uint64_t* __restrict__ s_off,
+                                                         const int32_t* __restrict__ s_st, const uint32_t* __restrict__ ix,
+                                                         const uint64_t* __restrict__ ask_base, const uint8_t* __restrict__ V,
+                                                         const uint64_t* __restrict__ v_off, uint32_t n_asks, uint32_t flags,
+                                                         uint8_t* __restrict__ out, uint64_t out_total, uint64_t* __restrict__ out_off,
+                                                         uint64_t* __restrict__ out_len, int32_t* __restrict__ status) {
+  __shared__ ver::SvEnt tbl[ver::MAX_SV];
+  const uint32_t q = blockIdx.x;
+  if (q >= n_asks) return;
+  const uint32_t sd = ix[q];
+  const uint64_t va = v_off[q], vb = v_off[q + 1];
+  const uint64_t slot = (ask_base[q] + va + 32ull * q + 15ull) & ~15ull;
+  int st = sd == VR_ASK_BAD ? (int)ST_INVAL : s_st[sd];
+  uint32_t ol = 0;
+  if (st == ST_OK) {
+    const uint64_t a = s_off[sd], b = s_off[sd + 1];
+    if (b < a || vb < va || b - a >= (1ull << 30) || vb - va >= (1ull << 30)) st = ST_INVAL;
+    else {
+      const uint32_t sn = (uint32_t)(b - a), vn = (uint32_t)(vb - va), cap = sn + vn + 16u;
+      if (slot + cap > out_total) st = ST_NOMEM;
+      else st = ver::cut_doc(WaveW{threadIdx.x}, S + a, sn, V + va, vn, flags, tbl, out + slot, cap, ol);
+    }
+  }
+  if (threadIdx.x == 0) { out_off[q] = slot; out_len[q] = st == ST_OK ? ol : 0u; status[q] = st; }
+}
+
 }  // namespace ygm
 
 using namespace ygm;
@@ -102,6 +137,17 @@ int ygm_k_launch_ver_cut(const uint8_t* S, const uint64_t* s_off, const int32_t*
   if (n_docs == 0) return 0;
   hipLaunchKernelGGL(k_ver_cut, dim3(n_docs), dim3(VR_NT), 0, s, S, s_off, s_st, V, v_off, n_docs, flags, out, out_total, out_off, out_len,
                      status);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", __func__, hipGetErrorString(e)); return -1; }
+  return 0;
+}
+
+int ygm_k_launch_ver_cut_gather(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint32_t* ix, const uint64_t* ask_base,
+                                const uint8_t* V, const uint64_t* v_off, uint32_t n_asks, uint32_t flags, uint8_t* out, uint64_t out_total,
+                                uint64_t* out_off, uint64_t* out_len, int32_t* status, hipStream_t s) {
+  if (n_asks == 0) return 0;
+  hipLaunchKernelGGL(k_ver_cut_gather, dim3(n_asks), dim3(VR_NT), 0, s, S, s_off, s_st, ix, ask_base, V, v_off, n_asks, flags, out, out_total,
+                     out_off, out_len, status);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", __func__, hipGetErrorString(e)); return -1; }
   return 0;

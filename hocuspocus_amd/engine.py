@@ -76,7 +76,8 @@ EXPORTS = ("ygm_open", "ygm_close", "ygm_merge_v1", "ygm_diff_v1", "ygm_sv_from_
            "ygm_sync_step2_shared_v1_device",
            "ygm_snapshot_opts_v1", "ygm_sync_step2_opts_v1", "ygm_sync_step2_shared_opts_v1",
            "ygm_snapshot_opts_v1_device", "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device",
-           "ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device")
+           "ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device",
+           "ygm_version_restore_shared_v1", "ygm_version_restore_shared_v1_device")
 
 
 def lib():
@@ -134,6 +135,10 @@ def lib():
         L.ygm_version_take_v1_device.argtypes = [vp, vp, u64, vp, u32, vp, ctypes.POINTER(_DevResult)]
         L.ygm_version_restore_v1_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
         for f in ("ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device"):
+            getattr(L, f).restype = i32
+        L.ygm_version_restore_shared_v1.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
+        L.ygm_version_restore_shared_v1_device.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
+        for f in ("ygm_version_restore_shared_v1", "ygm_version_restore_shared_v1_device"):
             getattr(L, f).restype = i32
         L.ygm_merge_v2.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
         L.ygm_diff_v2.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
@@ -502,8 +507,8 @@ class Engine:
         """Old versions of gc: false documents: Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc,
         Y.decodeSnapshot(version), newDoc)) for doc = Y.applyUpdate(new Y.Doc({gc: false}), state)
         (ygm_version_restore_v1) -> list of (status, bytes | None).  opts as snapshot_batch, one per pair: DOC_NO_GC /
-        True restores into new Y.Doc({gc: false}).  To restore several versions of one document pass its state once
-        per version."""
+        True restores into new Y.Doc({gc: false}).  To restore several versions of one document use
+        restore_version_shared_batch: here its state is staged and snapshotted once per version."""
         if len(states) != len(versions):
             raise ValueError("one version per state")
         sa, so = _pack([bytes(s) for s in states])
@@ -512,6 +517,26 @@ class Engine:
         o = _opts(opts, len(states))
         st = lib().ygm_version_restore_v1(self._ctx, sa or None, _ptr(so), va or None, _ptr(vo), _ptr(o) if o is not None and len(o) else None,
                                           len(states), ctypes.byref(res))
+        if st != OK:
+            raise YjsError(st)
+        return self._unpack(res)
+
+    def restore_version_shared_batch(self, states, ask_state, versions, opts=None):
+        """Many versions restored from one stored state (ygm_version_restore_shared_v1): ask a restores versions[a] from
+        states[ask_state[a]], byte for byte and status for status what restore_version_batch gives for that pair, but
+        every state is uploaded and given its no-GC snapshot once however many asks name it.  ask_state as ask_doc in
+        diff_update_shared_batch.  opts as snapshot_batch, one per ask: the option belongs to the restored document.
+        -> list of (status, bytes | None) per ask."""
+        if len(ask_state) != len(versions):
+            raise ValueError("one state index per version")
+        sa, so = _pack([bytes(s) for s in states])
+        va, vo = _pack([bytes(v) for v in versions])
+        ask = np.ascontiguousarray(np.asarray(ask_state, dtype=np.int64).astype(np.uint32))
+        res = _Result()
+        o = _opts(opts, len(versions))
+        st = lib().ygm_version_restore_shared_v1(self._ctx, sa or None, _ptr(so), len(states), va or None, _ptr(vo),
+                                                 _ptr(ask) if len(ask) else None, _ptr(o) if o is not None and len(o) else None,
+                                                 len(ask), ctypes.byref(res))
         if st != OK:
             raise YjsError(st)
         return self._unpack(res)
@@ -532,6 +557,22 @@ class Engine:
         none = d_restored_opt is None or (not hasattr(d_restored_opt, "data_ptr") and not d_restored_opt)
         st = lib().ygm_version_restore_v1_device(self._ctx, _dptr(d_states), _dptr(d_state_off), _dptr(d_versions), _dptr(d_version_off),
                                                  None if none else _dptr(d_restored_opt, n_docs), n_docs, stream or None, ctypes.byref(r))
+        if st != OK:
+            raise YjsError(st)
+        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+
+    def version_restore_shared_device(self, d_states, states_bytes, d_state_off, n_states, d_versions, d_version_off, d_ask_state, n_asks,
+                                      stream=0, d_restored_opt=0) -> "DeviceResult":
+        """Device-resident shared restore batch (ygm_version_restore_shared_v1_device): n_states states, n_asks versions,
+        d_ask_state (u32) naming each ask's state; arenas as version_restore_device; d_restored_opt: a device pointer /
+        tensor of n_asks option bytes (0: none).  Results are indexed by ask; an ask whose id is out of range or below
+        its predecessor carries EINVAL."""
+        r = _DevResult()
+        none = d_restored_opt is None or (not hasattr(d_restored_opt, "data_ptr") and not d_restored_opt)
+        st = lib().ygm_version_restore_shared_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off),
+                                                        n_states, _dptr(d_versions), _dptr(d_version_off), _dptr(d_ask_state),
+                                                        None if none else _dptr(d_restored_opt, n_asks), n_asks, stream or None,
+                                                        ctypes.byref(r))
         if st != OK:
             raise YjsError(st)
         return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)

@@ -103,7 +103,8 @@ typedef struct {
   uint64_t docs_snapshot;              /* documents the snapshot kernels were run on (ygm_snapshot_v1, and the snapshots
                                           inside ygm_contains_v1 / ygm_sync_step2_v1 / the shared-state forms: there one
                                           per state and chunk, not one per ask; one per document of
-                                          ygm_version_take_v1, two per document of ygm_version_restore_v1) */
+                                          ygm_version_take_v1, two per document of ygm_version_restore_v1, one per state
+                                          and chunk plus one per ask of ygm_version_restore_shared_v1) */
 } ygm_stats_t;
 
 /* Opens the engine on HIP device `device` (one context per GPU; contexts are
@@ -213,8 +214,8 @@ int ygm_version_take_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *sta
  *   more than 4096 state-vector entries (or delete-set clients),
  *   a client id past 32 bits                                       YGM_EUNSUPPORTED
  * Bytes after the state vector are ignored, as decodeSnapshot ignores them.  Each refusal affects only its own
- * document.  There is no form that restores many versions from one state: to restore several versions of one
- * document, pass its state once per version. */
+ * document.  To restore several versions of one document, use ygm_version_restore_shared_v1 below: the pair form
+ * stages and snapshots the state once per version. */
 int ygm_version_restore_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *versions,
                            const uint64_t *version_off, const uint8_t *restored_opt, uint32_t n_docs, ygm_result *out);
 
@@ -247,6 +248,20 @@ int ygm_sync_step2_shared_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t
 int ygm_sync_step2_shared_opts_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *state_opt,
                                   uint32_t n_states, const uint8_t *sv_arena, const uint64_t *sv_off,
                                   const uint32_t *ask_state, uint32_t n_asks, ygm_result *out);
+/* ygm_version_restore_v1 over shared states: many versions restored from one stored state (a history sidebar, a
+ * scrubber, an export of every version of a document).  n_states states, n_asks versions, ask_state[a] naming the
+ * state that version a is restored from, under the rules of ask_state above.  One result per ask, in ask order
+ * (out->n_docs == n_asks), each byte-identical, with identical status, to what ygm_version_restore_v1 returns for the
+ * pair (state[ask_state[a]], version[a], restored_opt[a]), in both modes.  Each state is staged once and given its
+ * no-GC snapshot once; the cut reads that snapshot in place for every ask; only the restored documents are
+ * snapshotted per ask.  restored_opt holds one byte per ask (n_asks bytes, or NULL): the option belongs to the new
+ * document, not to the state; a byte with any bit other than YGM_DOC_NO_GC gives that ask YGM_EINVAL and nothing
+ * else.  A state's refusal is the status of each of its asks; a bad version fails only its own ask, by the table
+ * under ygm_version_restore_v1.  Chunks are cut as for ygm_sync_step2_shared_v1: a split state is staged and
+ * snapshotted once per chunk, and a chunk stages its asks' option bytes. */
+int ygm_version_restore_shared_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, uint32_t n_states,
+                                  const uint8_t *versions, const uint64_t *version_off, const uint32_t *ask_state,
+                                  const uint8_t *restored_opt, uint32_t n_asks, ygm_result *out);
 
 /* ---- update format V2 ------------------------------------
  * The same operations over yjs's column-encoded update format V2 (UpdateEncoderV2 / UpdateDecoderV2,
@@ -372,6 +387,16 @@ int ygm_sync_step2_shared_opts_v1_device(ygm_ctx *ctx, const uint8_t *d_states, 
                                          const uint64_t *d_state_off, const uint8_t *d_state_opt, uint32_t n_states,
                                          const uint8_t *d_sv_arena, const uint64_t *d_sv_off, const uint32_t *d_ask_state,
                                          uint32_t n_asks, void *stream, ygm_device_result *out);
+/* ygm_version_restore_shared_v1, device-resident: d_version_off has n_asks + 1 entries, d_restored_opt n_asks bytes
+ * (NULL: none set).  The ask plan runs over the packed no-GC snapshots: ask a's cut goes to the slot
+ * al16(ask_base[a] + d_version_off[a] + 32 * a), ask_base the exclusive scan, over asks, of the ask's snapshot
+ * length.  As in the pair form, d_versions must be 16-byte aligned (YGM_EINVAL otherwise) and both arenas be followed
+ * by 64 readable bytes.  ygm_stats_t.docs_snapshot grows by n_states + n_asks. */
+int ygm_version_restore_shared_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes,
+                                         const uint64_t *d_state_off, uint32_t n_states, const uint8_t *d_versions,
+                                         const uint64_t *d_version_off, const uint32_t *d_ask_state,
+                                         const uint8_t *d_restored_opt, uint32_t n_asks, void *stream,
+                                         ygm_device_result *out);
 
 /* update V2, device-resident (outputs packed in document order: off[d] increasing) */
 int ygm_merge_v2_device(ygm_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_upd_off,

@@ -294,6 +294,7 @@ static void job_execute(Job *j) {
   else if (j->op == 14) j->rc = ygm_convert_v2_to_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   else if (j->op == 15) j->rc = ygm_version_take_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   else if (j->op == 16) j->rc = ygm_version_restore_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->opt, j->n_docs, &r);
+  else if (j->op == 17) j->rc = ygm_version_restore_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->opt, j->n_upd, &r);
   else j->rc = ygm_sv_from_update_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   if (j->rc != YGM_OK) return;
   /* results are context-owned: copy out before the next batch may reuse them */
@@ -507,9 +508,11 @@ static napi_value js_contains(napi_env env, napi_callback_info info) {
 }
 
 /* diffShared / step2Shared(h, states, stateLens, svArena, svLens, askState:Uint32Array): one result per ask (state
-   vector), ask a answered from state askState[a] (non-decreasing); n_docs = states, n_upd = asks, docs = askState */
+   vector), ask a answered from state askState[a] (non-decreasing); n_docs = states, n_upd = asks, docs = askState.
+   restoreVersionShared(h, states, stateLens, versions, versionLens, askState[, opts]): the same shape with one version
+   per ask, and one option byte per ask -- the option belongs to the restored document (ygm_version_restore_shared_v1) */
 static napi_value js_shared(napi_env env, napi_callback_info info) {
-  size_t argc = 7; napi_value argv[7];   /* (step2Shared: an optional seventh argument, one option byte per state) */
+  size_t argc = 7; napi_value argv[7];   /* (an optional seventh argument: step2Shared, one option byte per state; restoreVersionShared, per ask) */
   void *opd = NULL;
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
   if (argc < 6) { napi_throw_type_error(env, NULL, "step2Shared(handle, states, stateLens, svArena, svLens, askState)"); return NULL; }
@@ -528,6 +531,7 @@ static napi_value js_shared(napi_env env, napi_callback_info info) {
   free(lens); free(slens);
   if (j->off[j->n_docs] != an || j->sv_off[j->n_upd] != sn) { job_free(j); napi_throw_range_error(env, NULL, "step2Shared: lengths do not match arenas"); return NULL; }
   if (j->op == 7 && get_opts(env, argc, argv, 6, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "step2Shared: one option byte per state"); return NULL; }
+  if (j->op == 17 && get_opts(env, argc, argv, 6, j->n_upd, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "restoreVersionShared: one option byte per version"); return NULL; }
   return submit(env, j, argv[0]);
 }
 
@@ -578,6 +582,8 @@ static napi_value init(napi_env env, napi_value exports) {
        [, option bytes of the restored documents] (ygm_version_take_v1 / ygm_version_restore_v1) */
     { "takeVersionMany", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)15 },
     { "restoreVersionMany", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)16 },
+    /* many versions restored from one state: one result and one option byte per ask */
+    { "restoreVersionShared", NULL, js_shared, NULL, NULL, NULL, napi_default, (void *)(intptr_t)17 },
     { "stats", NULL, js_stats, NULL, NULL, NULL, napi_default, NULL },
     { "strerror", NULL, js_strerror, NULL, NULL, NULL, napi_default, NULL },
   };

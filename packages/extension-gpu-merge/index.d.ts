@@ -47,9 +47,14 @@ export declare class GpuEngine {
   takeVersion (state: Uint8Array): Promise<Uint8Array>
   takeVersionMany (states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   /** Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), new Y.Doc(opts))) of doc =
-   *  Y.applyUpdate(new Y.Doc({ gc: false }), state); several versions of one document: its state once per version */
+   *  Y.applyUpdate(new Y.Doc({ gc: false }), state); several versions of one document: restoreVersionShared */
   restoreVersion (state: Uint8Array, version: Uint8Array, opts?: DocOptions): Promise<Uint8Array>
   restoreVersionMany (states: Uint8Array[], versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
+  /** Many versions restored from shared states: ask a restores versions[a] from states[askState[a]]; one result per ask,
+   *  in caller order, equal to restoreVersionMany of the pair.  Each state is uploaded and given its no-GC snapshot once.
+   *  opts: one option per ask (the option belongs to the restored document).  An askState entry that names no state
+   *  rejects with YgmError EINVAL. */
+  restoreVersionShared (states: Uint8Array[], askState: ArrayLike<number>, versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** the context's counters (ygm_stats_t), camel-cased: calls, docs, kernelMs, h2dMs, d2hMs, hostSyncs, docsPending,
    *  docsSnapshot (documents the snapshot kernels ran on: one per state for step2Shared, one per pair for step2Many), ... */
   stats (): Record<string, number>
@@ -79,6 +84,8 @@ export declare class GpuEnginePool {
   containsMany (names: string[], states: Uint8Array[], updates: Uint8Array[]): Promise<(boolean | YgmError)[]>
   takeVersionMany (names: string[], states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   restoreVersionMany (names: string[], states: Uint8Array[], versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
+  /** names[i] naming states[i], routed as step2Shared; opts: one option per ask */
+  restoreVersionShared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   stats (): Record<string, number>[]
   /** node-wide totals: every per-device counter summed over the pool, plus `devices` */
   statsTotal (): Record<string, number>

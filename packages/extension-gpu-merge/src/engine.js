@@ -217,7 +217,17 @@ class GpuEngine {
    */
   diffShared (states, askState, svs) { return this._shared('diffShared', states, askState, svs) }
   step2Shared (states, askState, svs, opts) { return this._shared('step2Shared', states, askState, svs, optBytes(opts, states.length)) }
-  async _shared (op, states, askState, svs, opt) {
+  /**
+   * Many versions restored from shared states (a history sidebar, a scrubber, an export of every version): ask a restores
+   * versions[a] from states[askState[a]], byte for byte what restoreVersionMany gives for the pair -- but every state
+   * is uploaded and given its no-GC snapshot once, however many versions name it.  opts: one option per ask (as
+   * restoreVersionMany's, one per pair): the option belongs to the restored document, not to the state.
+   */
+  restoreVersionShared (states, askState, versions, opts) {
+    return this._shared('restoreVersionShared', states, askState, versions, optBytes(opts, versions.length), true)
+  }
+
+  async _shared (op, states, askState, svs, opt, optPerAsk) {
     const n = svs.length
     if (askState.length !== n) throw new YgmError(8, 'one state index per state vector')
     for (let a = 0; a < n; a++) {
@@ -226,7 +236,8 @@ class GpuEngine {
     const order = Array.from({ length: n }, (_, a) => a).sort((x, y) => askState[x] - askState[y] || x - y)
     const run = () => {
       const u = packBlobs(states); const v = packBlobs(order.map(a => svs[a]))
-      return loadAddon()[op](this.handle, u.arena, u.lens, v.arena, v.lens, Uint32Array.from(order, a => askState[a]), opt)
+      const o = opt && optPerAsk ? Uint8Array.from(order, a => opt[a]) : opt   // (per-ask bytes travel with their asks)
+      return loadAddon()[op](this.handle, u.arena, u.lens, v.arena, v.lens, Uint32Array.from(order, a => askState[a]), o)
     }
     const p = this.chain.then(run, run)
     this.chain = p.catch(() => {})
@@ -255,8 +266,9 @@ class GpuEngine {
    * restoreVersion: Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), newDoc)) of
    * doc = Y.applyUpdate(new Y.Doc({ gc: false }), state), newDoc = new Y.Doc() or, with { gc: false }, new
    * Y.Doc({ gc: false }).  The single forms share a batch with the calls of the same window; the *Many forms are
-   * explicit batches (opts as snapshotMany's, one per pair).  To restore several versions of a document pass its
-   * state once per version.
+   * explicit batches (opts as snapshotMany's, one per pair).  To restore several versions of a document use
+   * restoreVersionShared: the pair forms stage and snapshot its state once per version (the batched single call keeps
+   * the pair form; states are not compared by content).
    */
   takeVersion (state) { return this.batchers.takeVersion.push(state instanceof Uint8Array ? state : Uint8Array.from(state)) }
   restoreVersion (state, version, { gc } = {}) { return this.batchers.restoreVersion.push([state, version, gc === false ? DOC_NO_GC : 0]) }
@@ -343,17 +355,20 @@ class GpuEnginePool {
    */
   diffShared (names, states, askState, svs) { return this._sharedMany('diffShared', names, states, askState, svs) }
   step2Shared (names, states, askState, svs, opts) { return this._sharedMany('step2Shared', names, states, askState, svs, opts) }
-  async _sharedMany (op, names, states, askState, svs, opts) {
-    if (opts && opts.length !== states.length) throw new YgmError(8, 'one option per state')
+  /** restoreVersionShared with one name per state; opts: one option per ask, routed with its ask */
+  restoreVersionShared (names, states, askState, versions, opts) { return this._sharedMany('restoreVersionShared', names, states, askState, versions, opts, true) }
+  async _sharedMany (op, names, states, askState, svs, opts, optPerAsk) {
+    if (opts && opts.length !== (optPerAsk ? svs.length : states.length)) throw new YgmError(8, optPerAsk ? 'one option per ask' : 'one option per state')
     if (names.length !== states.length || askState.length !== svs.length) throw new YgmError(8, 'one name per state, one state index per state vector')
     const shard = names.map(n => this.shardOf(n))
     const local = new Array(states.length)   // a state's index inside its shard
     const parts = this.engines.map(() => ({ states: [], asks: [], opts: [] }))
-    states.forEach((s, i) => { local[i] = parts[shard[i]].states.length; parts[shard[i]].states.push(s); if (opts) parts[shard[i]].opts.push(opts[i]) })
+    states.forEach((s, i) => { local[i] = parts[shard[i]].states.length; parts[shard[i]].states.push(s); if (opts && !optPerAsk) parts[shard[i]].opts.push(opts[i]) })
     for (let a = 0; a < svs.length; a++) {
       const i = askState[a]
       if (!Number.isInteger(i) || i < 0 || i >= states.length) throw new YgmError(8, 'ask names no state')
       parts[shard[i]].asks.push(a)
+      if (opts && optPerAsk) parts[shard[i]].opts.push(opts[a])
     }
     const out = new Array(svs.length)
     await Promise.all(parts.map(async (p, e) => {

@@ -172,7 +172,9 @@ class GpuMerge {
    * true), in one GPU batch.  Returns one settled result per entry, { status: 'fulfilled', value } or { status:
    * 'rejected', reason }: a document that resolves to gc: true is rejected with yjs's own "originDoc must not be
    * garbage collected", one that is not loaded or that the engine refuses with that error -- each without
-   * disturbing the other entries.  There is no CPU path.
+   * disturbing the other entries.  There is no CPU path.  With an engine that has restoreVersionShared the entries are
+   * grouped by document (stable within a document) and each document's state goes up, and is snapshotted, once for
+   * all of its versions; the results return in the caller's entry order either way.
    */
   async restoreVersions (entries) {
     const eng = this._engine()
@@ -188,11 +190,25 @@ class GpuMerge {
       const states = await this._statesOf(names)
       const stateOf = i => states[names.indexOf(entries[i].documentName)]
       const ok = live.filter(i => { const s = stateOf(i); if (s instanceof Error || !s) { out[i] = { status: 'rejected', reason: s || new Error('no state') }; return false } return true })
+      const settle = (i, r) => { out[i] = r instanceof Error ? { status: 'rejected', reason: r } : { status: 'fulfilled', value: new Uint8Array(r) } }
+      const pooled = typeof eng.shardOf === 'function'
+      if (ok.length && typeof eng.restoreVersionShared === 'function') {
+        const docs = Array.from(new Set(ok.map(i => entries[i].documentName)))   // the admitted documents, first seen first
+        const at = new Map(docs.map((n, k) => [n, k]))
+        const order = ok.slice().sort((x, y) => at.get(entries[x].documentName) - at.get(entries[y].documentName) || x - y)
+        const sts = docs.map(n => states[names.indexOf(n)])
+        const askState = order.map(i => at.get(entries[i].documentName))
+        const versions = order.map(i => entries[i].version)
+        const opts = order.map(i => entries[i].gc === false ? 1 : 0)
+        const res = pooled ? await eng.restoreVersionShared(docs, sts, askState, versions, opts) : await eng.restoreVersionShared(sts, askState, versions, opts)
+        order.forEach((i, k) => settle(i, res[k]))
+        return out
+      }
       const opts = ok.map(i => entries[i].gc === false ? 1 : 0)
-      const res = !ok.length ? [] : typeof eng.shardOf === 'function'
+      const res = !ok.length ? [] : pooled
         ? await eng.restoreVersionMany(ok.map(i => entries[i].documentName), ok.map(stateOf), ok.map(i => entries[i].version), opts)
         : await eng.restoreVersionMany(ok.map(stateOf), ok.map(i => entries[i].version), opts)
-      ok.forEach((i, k) => { out[i] = res[k] instanceof Error ? { status: 'rejected', reason: res[k] } : { status: 'fulfilled', value: new Uint8Array(res[k]) } })
+      ok.forEach((i, k) => settle(i, res[k]))
     }
     return out
   }
