@@ -1105,6 +1105,11 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
       for (int j = 0; j < (C::IN + 16 * WAVE - 1) / (16 * WAVE); j++) {
         const uint32_t c = l + WAVE * j;
         if (c < nch) *(LB128*)(lin + 16 * c) = v[j];
+        if (!WIDE) {   // the chunk's varuint masks, one halfword each, for the fast parse (bit arrays in the idle output buffer)
+          uint32_t mh, mz;
+          lean_chunk_masks(v[j], mh, mz);
+          if (c < nch) { ((LB16*)lout)[c] = (uint16_t)mh; ((LB16*)(lout + LN_MASKB))[c] = (uint16_t)mz; }
+        }
       }
       if (LENS) {   // offsets: the exclusive prefix of the lane's four lengths on top of ONE wave scan of the lane totals
         uint32_t tot = 0;
@@ -1183,7 +1188,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     for (int q = 0; q < LN_ROWS; q++) { hs[q] = false; hasd[q] = false; }
     if (go && !WIDE && YGM_LN_FASTPARSE) {
       allfast = true;
-      // phase-major: the windows and tail bytes of YGM_LN_FASTGROUP rows are loaded (invalid lanes: the first
+      // phase-major: the windows, mask bits and tail bytes of YGM_LN_FASTGROUP rows are loaded (invalid lanes: the first
       // update, 0 bytes), then those rows' fast parses run, straight-line; a row with a valid lane that is not
       // fast is parsed again, whole, by lean_parse
 #pragma unroll
@@ -1196,7 +1201,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
       for (int g = 0; g < LN_ROWS; g += YGM_LN_FASTGROUP) {
         LFastIn F[YGM_LN_FASTGROUP];
 #pragma unroll
-        for (int q = g; q < g + YGM_LN_FASTGROUP; q++) lean_fast_load(lin, us[q], un[q], F[q - g]);
+        for (int q = g; q < g + YGM_LN_FASTGROUP; q++) lean_fast_load(lin, lout, us[q], un[q], F[q - g]);
 #pragma unroll
         for (int q = g; q < g + YGM_LN_FASTGROUP; q++) {
           const bool valid = ln_owns(l, q, k);

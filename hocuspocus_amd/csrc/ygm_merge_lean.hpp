@@ -14,7 +14,10 @@
 // k_merge_fast -> k_merge_seq), which also produce every error status.
 //
 // Phases (all in registers except the two LDS byte buffers):
-//   stage   every 16-byte chunk load of the document issued before the first wait
+//   stage   every 16-byte chunk load of the document issued before the first wait.  Narrow kernel: each chunk's
+//           two varuint byte masks (top bit set, zero byte) are made here, once per staged byte, from the
+//           prefetch registers, and kept as two LDS bit arrays in the output buffer, idle until the placement
+//           (lean_chunk_masks)
 //   parse   four updates per lane, blocked: lane l owns updates 4l .. 4l+3 (slot q = update 4l + q; row q = slot q of every lane), so a
 //           prefix sum in log order is three adds inside the lane and ONE wave scan of the lane totals;
 //           an update's bytes are
@@ -22,10 +25,11 @@
 //           register window (64 in the wide kernel); varuint ends come from a terminator bit
 //           mask (no byte loop).  Narrow kernel: phase-major -- the loads of all four rows
 //           are issued together and lean_parse_fast decides the single-Item / delete-
-//           set-only shapes from the window and the update's last three bytes, with no read
-//           that depends on the window; only a row holding another shape runs lean_parse,
-//           the generic grammar (multi-struct, parents, ContentDeleted, longer strings),
-//           whose dependent byte reads cost an LDS round trip each
+//           set-only shapes from a 16-byte window (five ds_read_b32: all it decodes lies in bytes 0..14),
+//           the update's 32 bits of either staged mask (one ds_read2_b32 and one v_alignbit each) and its
+//           last three bytes, with no read that depends on the window; only a row holding another shape
+//           runs lean_parse, the generic grammar (multi-struct, parents, ContentDeleted, longer strings),
+//           on a 32-byte window and masks of its own, whose dependent byte reads cost an LDS round trip each
 //   clients distinct clients by wave vote, in descending order (one wave max per client).  Narrow kernel, every row
 //           fast: the vote by first sight -- the candidate is the client of the first unassigned record in log
 //           order (one ballot, two readlanes: the second brings that record's clock, the block's first clock), a
@@ -46,7 +50,8 @@
 //           (structs, bytes) gives every record's byte offset; block bases and first clocks go
 //           through LDS to lane c
 //   emit    ds_or_b32 of funnel-shifted source dwords into a zeroed LDS output buffer
-//           (branch-free, order-free; one width class per document; rows in log order or in sorted
+//           (branch-free, order-free; one width class per document -- 5 dwords per struct when every struct
+//           is a one-character Item's, else 6 or 9; rows in log order or in sorted
 //           order, as placed), then 16-byte coalesced stores
 #pragma once
 #include "ygm_common.hpp"
@@ -89,6 +94,7 @@ template <int WIDE>
 struct alignas(16) LeanLdsT {
   uint8_t in[LnCfg<WIDE>::IN + (WIDE ? 96 : YGM_LN_INSLACK)];   // + slack: window / copy reads reach up to 76 bytes past an update's start
   uint8_t out[LnCfg<WIDE>::OUT + 80 + (WIDE ? 0 : YGM_LN_PAD)];   // + slack: lds_or_copy ORs zero into up to 68 bytes past a range
+  // (narrow kernel: from the staging to the end of the parse its first 2 LN_MASKB bytes hold the staged bytes' two mask arrays)
 };
 static_assert(LN_IN % 16 == 0 && YGM_LN_INSLACK >= 80 && YGM_LN_INSLACK % 16 == 0, "staging granules and slack");
 typedef LeanLdsT<0> LeanLds;
@@ -345,12 +351,38 @@ YDEV LRec lean_parse(LB8* in, uint32_t s, uint32_t n) {
 #ifndef YGM_LN_FASTPARENT
 #define YGM_LN_FASTPARENT 1   // 0 (experiment): the parent-ykey first insert is left to lean_parse
 #endif
+// The fast parse's two byte masks -- H: top bit set, Z: zero byte ("haszero": may also flag a 0x01 right above a zero byte) -- are
+// properties of the staged bytes, not of an update, so they are made once per staged 16-byte chunk, from the prefetch
+// registers at staging, and kept as two LDS bit arrays (bit b <-> staged byte b) in the output buffer, which is idle
+// until the placement.  An update's 32 mask bits are then two dwords of each array and one v_alignbit.  Bits of bytes
+// the document does not hold (past its end, or of an earlier document of the wave) are cut by V like stale window
+// bytes; Z's false positive depends on where the dwords begin (here the chunk's, not the update's), but the byte
+// below it is 0x00 or 0x01 and has no top bit, so it never passes "& (HV << 1)": the decisions do not depend on it
+constexpr int LN_MASKB = LN_IN / 8 + 8;   // bytes of one bit array; + slack: the dword after the last update's
+static_assert(LN_MASKB % 4 == 0 && 2 * LN_MASKB <= LN_OUT, "two bit arrays of whole dwords in the output buffer");
+typedef __attribute__((address_space(3))) uint16_t LB16;
+// the two masks of one staged chunk: bit i <-> byte i of its 16 bytes (dot4 weights by dword: bits 7..14 of each half)
+YDEV void lean_chunk_masks(const u32x4& v, uint32_t& h, uint32_t& z) {
+  constexpr uint32_t M = 0x80808080u, W0 = 0x08040201u, W1 = 0x80402010u, ONES = 0x01010101u;
+  const uint32_t ha = __builtin_amdgcn_udot4(v[1] & M, W1, __builtin_amdgcn_udot4(v[0] & M, W0, 0u, false), false);
+  const uint32_t hb = __builtin_amdgcn_udot4(v[3] & M, W1, __builtin_amdgcn_udot4(v[2] & M, W0, 0u, false), false);
+  h = (ha >> 7) | (hb << 1);
+  const uint32_t za = __builtin_amdgcn_udot4((v[1] - ONES) & ~v[1] & M, W1, __builtin_amdgcn_udot4((v[0] - ONES) & ~v[0] & M, W0, 0u, false), false);
+  const uint32_t zb = __builtin_amdgcn_udot4((v[3] - ONES) & ~v[3] & M, W1, __builtin_amdgcn_udot4((v[2] - ONES) & ~v[2] & M, W0, 0u, false), false);
+  z = (za >> 7) | (zb << 1);
+}
 struct LFastIn {
-  uint32_t d[8];     // the update's 32-byte window
+  uint32_t d[4];     // the update's first 16 bytes (block header, client, clock, info byte and the two bytes after it)
+  uint32_t H, Z;     // its 32 mask bits (bit i <-> byte i)
   uint32_t tl, td;   // bytes n - 3 (the string length of the fast shape) and n - 1 (its delete-set count)
 };
-YDEV void lean_fast_load(LB8* in, uint32_t s, uint32_t n, LFastIn& F) {
-  lean_window(in, s, F.d);
+// masks: the H bit array, the Z array LN_MASKB bytes after it
+YDEV void lean_fast_load(LB8* in, LB8* masks, uint32_t s, uint32_t n, LFastIn& F) {
+  lean_windowW<16>(in, s, F.d);
+  const LB32* mh = (const LB32*)masks + (s >> 5);
+  const LB32* mz = mh + LN_MASKB / 4;
+  F.H = __builtin_amdgcn_alignbit(mh[1], mh[0], s & 31u);
+  F.Z = __builtin_amdgcn_alignbit(mz[1], mz[0], s & 31u);
   const uint32_t t = s + (n > 3u ? n : 3u);
   F.tl = in[t - 3u]; F.td = in[t - 1u];
 }
@@ -364,12 +396,8 @@ YDEV void lean_fast_load(LB8* in, uint32_t s, uint32_t n, LFastIn& F) {
 // A lane the branch skips is not the parent-ykey shape (it has an origin, or it is not valid: n == 0, no shape fits)
 template <bool KEYROW>
 YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, LRec& R, bool& hasd) {
-  const uint32_t (&d)[8] = F.d;
-  const uint32_t H = lean_hmask(d);
-  uint32_t Z = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++)
-    Z |= top8((d[2 * j] - 0x01010101u) & ~d[2 * j], (d[2 * j + 1] - 0x01010101u) & ~d[2 * j + 1]) << (8 * j);
+  const uint32_t (&d)[4] = F.d;
+  const uint32_t H = F.H, Z = F.Z;
   const uint32_t V = n >= 32u ? 0xFFFFFFFFu : ((1u << n) - 1u);
   const uint32_t T = ~H & V, HV = H & V;
   // lean_parse's whole-window checks (a varuint of >= 8 bytes, a zero byte after a top-bit byte)
@@ -492,7 +520,7 @@ YDEV void lean_ds_next(LDsCur& c, uint32_t& client, uint32_t& clock, uint32_t& l
 // ZEROED output buffer: every destination dword the range touches gets ds_or_b32 of the
 // funnel-shifted source bytes masked to the range.  Byte ranges of different lanes are
 // disjoint, so the ORs commute: no edge cases, no ordering between lanes.  ND (wave-uniform)
-// bounds the destination dwords: head + n <= 4 ND (lean_copy picks 6 or 9).
+// bounds the destination dwords: head + n <= 4 ND (lean_copy picks 5, 6 or 9).
 template <int ND>
 YDEV void lds_or_copy(LB8* out, LB8* in, uint32_t t, uint32_t s, uint32_t n) {
   const uint32_t head = t & 3u;
@@ -516,16 +544,22 @@ YDEV void lds_or_copy(LB8* out, LB8* in, uint32_t t, uint32_t s, uint32_t n) {
 }
 // struct copies: 6 destination dwords when every run of the document fits (C2 structs are <= 19 bytes),
 // else 9, else (the wide kernel's runs of up to 63 bytes) 17 -- one decision per document (cw: the lane's
-// widest head + bytes), wave-uniform
+// widest head + bytes), wave-uniform.  Narrow kernel: 5 when every run fits that (class 3; a debounce log's structs
+// are <= 17 bytes)
+#ifndef YGM_LN_COPY5
+#define YGM_LN_COPY5 1        // 0 (experiment): no 5-dword class
+#endif
 template <int WIDE>
 YDEV uint32_t lean_copy_class(uint32_t cw) {
+  if (!WIDE && YGM_LN_COPY5 && __ballot(cw > 20u) == 0) return 3u;
   if (__ballot(cw > 24u) == 0) return 0u;
   return (!WIDE || __ballot(cw > 36u) == 0) ? 1u : 2u;
 }
 template <int WIDE>
 YDEV void lean_copy(LB8* out, LB8* in, uint32_t cls, bool go, uint32_t t, uint32_t s, uint32_t n) {
   if (!go) return;
-  if (cls == 0u) lds_or_copy<6>(out, in, t, s, n);
+  if (!WIDE && YGM_LN_COPY5 && cls == 3u) lds_or_copy<5>(out, in, t, s, n);
+  else if (cls == 0u) lds_or_copy<6>(out, in, t, s, n);
   else if (!WIDE || cls == 1u) lds_or_copy<9>(out, in, t, s, n);
   else lds_or_copy<17>(out, in, t, s, n);
 }
