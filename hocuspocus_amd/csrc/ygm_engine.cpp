@@ -752,6 +752,7 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
   const bool lds = n_docs && !(xf & YGM_F_SNAP_VERSION) && getenv("YGM_SNAP_NOLDS") == nullptr;
   const uint64_t slot_total = lds ? 2 * arena_bytes + 64ull * n_docs + 64 : 0;
   uint64_t lds_pay[2] = {0, 0};
+  uint64_t text_first = 0;   // (YGM_TIER_COUNTS: what launch 0 took)
   if (lds) {
     if (!c->sn_ws.ensure(slot_total + 64) || !c->sn_claim.ensure((size_t)n_docs + 16) || !c->sn_pay.ensure(16)) return YGM_ENOMEM;
     HIPCHK(hipMemsetAsync(c->sn_pay.p, 0, 16, s));
@@ -762,6 +763,7 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
       HIPCHK(hipMemcpyAsync(c->h_meta, c->sn_pay.p, 16, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       memcpy(lds_pay, c->h_meta, 16);
+      if (again == 0) text_first = lds_pay[1];
     }
   }
   uint64_t total = 0;   // workspace bytes: one read of the scanned total
@@ -794,6 +796,12 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
     HIPCHK(hipEventSynchronize(c->e1));
   }
   m.payload += lds_pay[0];
+  // YGM_TIER_COUNTS (testing knob): the tier that finished the call's documents, one stderr line (general: the count /
+  // scan / k_snap path, the documents it left pending among them)
+  if (getenv("YGM_TIER_COUNTS"))
+    fprintf(stderr, "ygm snapshot tiers: docs %u text_first %llu text_second %llu general %llu pending %u\n", n_docs,
+            (unsigned long long)text_first, (unsigned long long)(lds_pay[1] - text_first), (unsigned long long)(n_docs - lds_pay[1]),
+            m.fb_count);
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
   c->stats.calls++; c->stats.docs += n_docs; c->stats.bytes_in += arena_bytes; c->stats.bytes_out += m.payload;

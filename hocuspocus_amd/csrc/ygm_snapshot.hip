@@ -471,7 +471,7 @@ int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32
                            uint64_t* out_len, int32_t* status, uint8_t* claim, unsigned long long* pay, int again, uint64_t slot_total,
                            const uint8_t* opt, hipStream_t s) {
   if (n_docs == 0) return 0;
-  // again == 0: 6 KiB of LDS per document (209 parts); again == 1: 24 KiB for the documents the first launch left.
+  // again == 0: 6 KiB of LDS per document (207 parts); again == 1: 24 KiB (865 parts) for the documents the first launch left.
   // YGM_SNAP_TEXT="KiB" picks another measured size for the first launch.
   if (again) {
     hipLaunchKernelGGL((k_snap_text<24576>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
