@@ -47,6 +47,12 @@ int ygm_k_launch_snap_plan(const uint8_t* arena, const uint64_t* doc_off, uint32
 int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
                            uint64_t* out_len, int32_t* status, uint8_t* claim, unsigned long long* pay, int again, uint64_t slot_total,
                            const uint8_t* opt, hipStream_t s);
+int ygm_k_launch_text_flat(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
+                           uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, uint8_t* claim,
+                           unsigned long long* pay, int again, uint64_t slot_total, hipStream_t s);
+int ygm_k_launch_text(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
+                      uint32_t flags, uint32_t mode, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
+                      uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim, uint64_t base, hipStream_t s);
 int ygm_k_launch_cont_plan(const uint8_t* st_arena, const uint64_t* st_off, uint32_t n_docs, uint32_t flags, uint64_t* ws_off, uint64_t* bs,
                            hipStream_t s);
 int ygm_k_launch_cont(const uint8_t* st_arena, const uint64_t* st_off, const uint8_t* up_arena, const uint64_t* up_off, uint32_t n_docs,
@@ -820,6 +826,72 @@ int ygm_snapshot_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_by
                            void* stream, ygm_device_result* out) {
   return ygm_snapshot_opts_v1_device(c, d_arena, arena_bytes, d_doc_off, nullptr, n_docs, stream, out);
 }
+// ---- plain text of stored documents: the snapshot batch's tiers with another last stage.  k_text_flat at k_snap_text's
+// two LDS sizes into the per-document slots, then the count / scan launches and k_text over the workspaces that follow
+// the slot region, for the documents the flat tier left.  Nothing is left pending: a state with pending parts is read
+// through its integrated part.  The context's snapshot buffers serve (one batch in flight per context).
+int ygm_text_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, const uint8_t* d_names,
+                       const uint64_t* d_name_off, uint32_t mode, uint32_t n_docs, void* stream, ygm_device_result* out) {
+  if (!c || !out || mode > YGM_TEXT_DEEP || (n_docs && (!d_state_off || !d_name_off))) return YGM_EINVAL;
+  (void)hipSetDevice(c->device);
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  const uint32_t fl = c->flags;
+  const uint32_t nb = (n_docs + 1 + 255) / 256;
+  if (!c->sn_cnt.ensure(16ull * n_docs + 16) || !c->sn_off.ensure(8ull * n_docs + 16) || !c->sn_bs.ensure(8ull * nb + 16) ||
+      !c->out_off.ensure(8ull * n_docs + 8) || !c->out_len.ensure(8ull * n_docs + 8) || !c->status.ensure(4ull * n_docs + 4))
+    return YGM_ENOMEM;
+  void* meta = c->meta_slot(2);
+  HIPCHK(hipMemsetAsync(meta, 0, sizeof(Meta), s));
+  HIPCHK(hipEventRecord(c->e0, s));
+  const bool lds = n_docs && getenv("YGM_SNAP_NOLDS") == nullptr;
+  const uint64_t slot_total = lds ? 2 * states_bytes + 64ull * n_docs + 64 : 0;
+  uint64_t lds_pay[2] = {0, 0};
+  uint64_t flat_first = 0;
+  if (lds) {
+    if (!c->sn_ws.ensure(slot_total + 64) || !c->sn_claim.ensure((size_t)n_docs + 16) || !c->sn_pay.ensure(16)) return YGM_ENOMEM;
+    HIPCHK(hipMemsetAsync(c->sn_pay.p, 0, 16, s));
+    for (int again = 0; again < 2 && lds_pay[1] < n_docs; again++) {
+      if (ygm_k_launch_text_flat(d_states, d_state_off, d_names, d_name_off, n_docs, fl, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(),
+                                 c->out_len.as<uint64_t>(), c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(),
+                                 c->sn_pay.as<unsigned long long>(), again, slot_total, s))
+        return YGM_EDEVICE;
+      c->stats.host_syncs++;
+      HIPCHK(hipMemcpyAsync(c->h_meta, c->sn_pay.p, 16, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      memcpy(lds_pay, c->h_meta, 16);
+      if (again == 0) flat_first = lds_pay[1];
+    }
+  }
+  uint64_t total = 0;
+  Meta m;
+  memset(&m, 0, sizeof(m));
+  if (n_docs && (!lds || lds_pay[1] < n_docs)) {
+    const uint8_t* claim = lds ? c->sn_claim.as<uint8_t>() : nullptr;
+    if (ygm_k_launch_snap_plan(d_states, d_state_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), claim, s))
+      return YGM_EDEVICE;
+    int e = 0;
+    total = read_u64(c, s, c->sn_off.as<uint64_t>() + n_docs, e);
+    if (e) return e;
+    if (!c->sn_ws.ensure(slot_total + total + 64, slot_total, s)) return YGM_ENOMEM;
+    if (ygm_k_launch_text(d_states, d_state_off, d_names, d_name_off, n_docs, fl, mode, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
+                          c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
+                          (unsigned long long*)((uint8_t*)meta + offsetof(Meta, payload)), claim, slot_total, s))
+      return YGM_EDEVICE;
+    if ((e = read_meta(c, s, m, meta))) return e;
+  }
+  HIPCHK(hipEventRecord(c->e1, s));
+  HIPCHK(hipEventSynchronize(c->e1));
+  m.payload += lds_pay[0];
+  if (getenv("YGM_TIER_COUNTS"))   // (testing knob, as the snapshot's line: the tier that finished the call's documents)
+    fprintf(stderr, "ygm text tiers: docs %u flat_first %llu flat_second %llu general %llu\n", n_docs, (unsigned long long)flat_first,
+            (unsigned long long)(lds_pay[1] - flat_first), (unsigned long long)(n_docs - lds_pay[1]));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
+  c->stats.calls++; c->stats.docs += n_docs; c->stats.bytes_in += states_bytes; c->stats.bytes_out += m.payload;
+  out->data = c->sn_ws.as<uint8_t>(); out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
+  out->status = c->status.as<int32_t>(); out->data_bytes = slot_total + total; out->payload_bytes = m.payload;
+  return YGM_OK;
+}
 // a snapshot batch's outputs packed into one arena on the device (k_pack_*: offsets n + 1, the total at [n]) with its
 // statuses, for kernels that read documents by offsets (step2's diff, contains)
 static int pack_snapshots(ygm_ctx* c, hipStream_t s, const ygm_device_result& r1, uint32_t n_docs) {
@@ -1412,10 +1484,12 @@ struct HostCall {
               // 7 sv, 8 V1 -> V2, 9 V2 -> V1; 10 sync step2 (states + state vectors); 11 / 12 the shared-state diff /
               // step2 (host_shared_call: n_docs states, n_upd asks, upd_doc = the asks' states); 13 version take, 14 version
               // restore (states + versions in the sv slots, restored_opt as opt); 15 the shared-state version restore
-              // (host_shared_call: versions in the sv slots, restored_opt per ask)
+              // (host_shared_call: versions in the sv slots, restored_opt per ask); 16 text (states + root names in the
+              // sv slots, text_mode)
   const uint8_t* arena; const uint64_t* off; const uint32_t* upd_doc; const uint8_t* sv_arena; const uint64_t* sv_off;
   uint32_t n_upd, n_docs;
   const uint8_t* opt = nullptr;   // modes 3 / 10 / 14: n_docs option bytes, mode 12: one per state, mode 15: one per ask (null: none); each chunk stages its slice
+  uint32_t text_mode = 0;         // mode 16: YGM_TEXT_FLAT / YGM_TEXT_DEEP
 };
 }  // namespace
 
@@ -1463,7 +1537,7 @@ static void par_for(size_t n, F f) {
 // CPU copy of a chunk's inputs into the stage's pinned buffer, then the async H2D copies
 static bool is_merge(int mode) { return mode == 2 || mode == 5; }
 static int chunk_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
-  const bool two = H.mode == 1 || H.mode == 4 || H.mode == 6 || H.mode == 10 || H.mode == 14;   // a second arena per document (diff: state vectors, contains: updates, restore: versions)
+  const bool two = H.mode == 1 || H.mode == 4 || H.mode == 6 || H.mode == 10 || H.mode == 14 || H.mode == 16;   // a second arena per document (diff: state vectors, contains: updates, restore: versions, text: root names)
   const uint32_t nd = C.d1 - C.d0;
   const uint64_t a0 = is_merge(H.mode) ? H.off[C.u0] : H.off[C.d0], a1 = is_merge(H.mode) ? H.off[C.u1] : H.off[C.d1];
   const uint64_t bytes = a1 - a0, ab = (bytes + 64 + 15) & ~15ull;
@@ -1538,6 +1612,8 @@ static int chunk_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint64
   else if (H.mode == 10) e = ygm_sync_step2_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
                                                            H.opt && nd ? k->opt.as<uint8_t>() : nullptr, k->sv_arena.as<uint8_t>(),
                                                            k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
+  else if (H.mode == 16) e = ygm_text_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
+                                                k->sv_offs.as<uint64_t>(), H.text_mode, nd, nullptr, &dr);
   else if (H.mode == 1) e = ygm_diff_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
                                                k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
   else e = ygm_sv_from_update_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
@@ -1859,7 +1935,7 @@ int ygm_merge_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, cons
 static int host_doc_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena,
                          const uint64_t* sv_off, uint32_t n_docs, ygm_result* out, const uint8_t* opt = nullptr) {
   if (!c || !out || (n_docs && (!arena || !doc_off))) return YGM_EINVAL;
-  const bool two = mode == 1 || mode == 4 || mode == 6 || mode == 10 || mode == 14;
+  const bool two = mode == 1 || mode == 4 || mode == 6 || mode == 10 || mode == 14 || mode == 16;
   if (two && n_docs && (!sv_arena || !sv_off)) return YGM_EINVAL;
   for (uint32_t d = 0; d < n_docs; d++) {
     if (doc_off[d + 1] < doc_off[d]) return YGM_EINVAL;
@@ -1891,6 +1967,17 @@ int ygm_version_restore_shared_v1(ygm_ctx* c, const uint8_t* states, const uint6
 
 int ygm_snapshot_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
   return host_doc_call(c, 3, arena, doc_off, nullptr, nullptr, n_docs, out);
+}
+int ygm_text_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* names, const uint64_t* name_off, uint32_t mode,
+                uint32_t n_docs, ygm_result* out) {
+  if (!c || !out || mode > YGM_TEXT_DEEP || (n_docs && (!states || !state_off || !name_off))) return YGM_EINVAL;
+  for (uint32_t d = 0; d < n_docs; d++) if (state_off[d + 1] < state_off[d] || name_off[d + 1] < name_off[d]) return YGM_EINVAL;
+  static const uint64_t zero_off[1] = {0};
+  static const uint8_t no_names[1] = {0};   // (every name empty: the arena may be NULL)
+  if (n_docs && !names) { if (name_off[n_docs] != name_off[0]) return YGM_EINVAL; names = no_names; }   // (no byte of it is read)
+  HostCall H{16, states, n_docs ? state_off : zero_off, nullptr, names, n_docs ? name_off : zero_off, 0, n_docs};
+  H.text_mode = mode;
+  return host_call(c, H, out);
 }
 int ygm_snapshot_opts_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* doc_opt, uint32_t n_docs, ygm_result* out) {
   return host_doc_call(c, 3, arena, doc_off, nullptr, nullptr, n_docs, out, doc_opt);

@@ -84,6 +84,10 @@ class ShardedEngine:
         return self._run(names, [states, svs, list(bytes(opts) if isinstance(opts, (bytes, bytearray, memoryview)) else opts)],
                          lambda e, s, v, o: e.sync_step2_batch(s, v, o))
 
+    def text_batch(self, doc_names, states, names, deep=False):
+        """Engine.text_batch by shard: doc_names route the states, names are their root names."""
+        return self._run(doc_names, [states, names], lambda e, s, n: e.text_batch(s, n, deep=deep))
+
     def close(self):
         self._pool.shutdown()
         for e in self.engines:

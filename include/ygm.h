@@ -163,6 +163,32 @@ int ygm_contains_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_o
                     const uint64_t *update_off, uint32_t n_docs, ygm_result *out);
 /* (ygm_contains_v1 has no options form: Y.snapshot(doc) is a state vector and a delete set, and both are the same
  * with or without garbage collection, so the answer for a gc: false document is the one above.) */
+/* ---- plain text of stored documents ----------------------------------------
+ * What a stored document says, without loading it into a Y.Doc: for doc = Y.applyUpdate(new Y.Doc(), state) and a
+ * root name (UTF-8 bytes, compared bytewise with the root-type names in the update), document d's output is
+ *   YGM_TEXT_FLAT  the UTF-8 of doc.getText(name).toString() (yjs YText.toString: from the type's _start along
+ *                  right, every item that is not deleted, is countable and holds a ContentString appends its string;
+ *                  embeds, formats, Any, JSON, binary, nested types and sub-documents are skipped);
+ *   YGM_TEXT_DEEP  the same walk that also descends, at a live ContentType item, into that type's list and on return
+ *                  appends one 0x0A unless the output is still empty or already ends in 0x0A -- the text of an
+ *                  XmlFragment / Tiptap document, whose strings live in XmlText nodes below the root.  Map entries
+ *                  (items with a parentSub) are on no list: attributes and Y.Map values contribute nothing.
+ * A string cut through a surrogate pair by a concurrent insert or a delete carries U+FFFD on both sides, as
+ * ContentString.splice leaves it.  states / state_off as ygm_snapshot_v1; names / name_off: one root name per
+ * document (n_docs + 1 offsets; names may be NULL when every name is empty).  A name the update has no root for
+ * gives the empty text with YGM_OK (doc.getText creates an empty type).  A state that leaves pending structs / a
+ * pending delete set is read through its integrated part, as ygm_version_take_v1 reads it, with YGM_OK.  Any other
+ * status is the one the state's parse and integration give in ygm_snapshot_v1 (YGM_EMALFORMED, YGM_ERANGE,
+ * YGM_EUNSUPPORTED, ...) and affects only its own document.  A mode other than the two is YGM_EINVAL for the call.
+ * Outputs are packed in document order.
+ * (ygm_text_v1 has no options form: the text depends neither on YGM_F_COMPAT_135 nor on garbage collection -- a
+ * deleted item is skipped whether or not its content was collected.)
+ * (Replaces no single reference interface: the reference's server code never calls getText().toString(); this is
+ * the batched form of the per-document load-and-walk a search indexer, a webhook body or a version preview does.) */
+#define YGM_TEXT_FLAT 0u
+#define YGM_TEXT_DEEP 1u
+int ygm_text_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *names,
+                const uint64_t *name_off, uint32_t mode, uint32_t n_docs, ygm_result *out);
 /* SyncStep2 payload of a stored document: Y.encodeStateAsUpdate(doc, sv) for doc = Y.applyUpdate(new Y.Doc(), state)
  * -- what the reference sends in reply to a SyncStep1 (packages/server/src/MessageReceiver.ts:137-138) for a
  * document loaded from stored bytes (extension-database Database.ts:44-50).  Computed as the doc-normalized
@@ -355,6 +381,13 @@ int ygm_snapshot_opts_v1_device(ygm_ctx *ctx, const uint8_t *d_arena, uint64_t a
 
 int ygm_contains_v1_device(ygm_ctx *ctx, const uint8_t *d_states, const uint64_t *d_state_off, const uint8_t *d_updates,
                            const uint64_t *d_update_off, uint32_t n_docs, void *stream, ygm_device_result *out);
+/* ygm_text_v1, device-resident, as ygm_snapshot_v1_device: 64 readable bytes must follow both arenas, results are
+ * not packed (a flat-text document asked by its root name has its text in its slot, align16(2 * d_state_off[d] +
+ * 64 * d); any other in the workspace region after the slots), payload_bytes is the sum of the lengths.
+ * (Replaces no single reference interface, as ygm_text_v1.) */
+int ygm_text_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
+                       const uint8_t *d_names, const uint64_t *d_name_off, uint32_t mode, uint32_t n_docs, void *stream,
+                       ygm_device_result *out);
 int ygm_sync_step2_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                              const uint8_t *d_sv_arena, const uint64_t *d_sv_off, uint32_t n_docs, void *stream,
                              ygm_device_result *out);

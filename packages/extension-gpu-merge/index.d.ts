@@ -46,6 +46,9 @@ export declare class GpuEngine {
   /** version history: Y.encodeSnapshot(Y.snapshot(doc)) of doc = Y.applyUpdate(new Y.Doc(), state); the single form shares a batch window */
   takeVersion (state: Uint8Array): Promise<Uint8Array>
   takeVersionMany (states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  /** plain text of stored documents: doc.getText(names[i]).toString() of doc = Y.applyUpdate(new Y.Doc(), states[i]); deep:
+   *  also descends into nested types (XmlFragment / Tiptap), one '\n' after each; an absent root name gives '' */
+  textMany (states: Uint8Array[], names: (string | Uint8Array)[], opts?: { deep?: boolean }): Promise<(string | YgmError)[]>
   /** Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), new Y.Doc(opts))) of doc =
    *  Y.applyUpdate(new Y.Doc({ gc: false }), state); several versions of one document: restoreVersionShared */
   restoreVersion (state: Uint8Array, version: Uint8Array, opts?: DocOptions): Promise<Uint8Array>
@@ -83,6 +86,8 @@ export declare class GpuEnginePool {
   snapshotMany (names: string[], states: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   containsMany (names: string[], states: Uint8Array[], updates: Uint8Array[]): Promise<(boolean | YgmError)[]>
   takeVersionMany (names: string[], states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
+  /** docNames[i] routes states[i]; names[i] is its root name */
+  textMany (docNames: string[], states: Uint8Array[], names: (string | Uint8Array)[], opts?: { deep?: boolean }): Promise<(string | YgmError)[]>
   restoreVersionMany (names: string[], states: Uint8Array[], versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** names[i] naming states[i], routed as step2Shared; opts: one option per ask */
   restoreVersionShared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
@@ -159,6 +164,10 @@ export declare class GpuMerge implements Extension {
   /** the documents as they were at the versions (Y.createDocFromSnapshot), one GPU batch, one settled result per entry;
    *  a gc: true document's entry is rejected with "originDoc must not be garbage collected" */
   restoreVersions (entries: { documentName: string, version: Uint8Array, gc?: boolean }[]): Promise<({ status: 'fulfilled', value: Uint8Array } | { status: 'rejected', reason: Error })[]>
+  /** what each loaded document says (field 'default', deep true by default), one GPU batch; unloaded or refused documents are left out */
+  textOf (names: string[], opts?: { field?: string, deep?: boolean }): Promise<Map<string, string>>
+  /** restoreVersions followed by one text batch over the fulfilled results, settled per entry */
+  versionTexts (entries: { documentName: string, version: Uint8Array, gc?: boolean }[], opts?: { field?: string, deep?: boolean }): Promise<({ status: 'fulfilled', value: string } | { status: 'rejected', reason: Error })[]>
   /** batched SyncStep1 responder over the captured state (snapshot + updates since) */
   syncResponder (): SyncResponder
   /** batched extension-redis fan-out over the same captured state */

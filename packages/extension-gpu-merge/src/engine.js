@@ -116,6 +116,8 @@ function packBlobs (blobs) {
 
 /** YGM_DOC_NO_GC: the option byte of a document created with gc: false (yDocOptions, Hocuspocus.ts:331-344) */
 const DOC_NO_GC = 1
+/** YGM_TEXT_FLAT / YGM_TEXT_DEEP: the modes of ygm_text_v1 */
+const TEXT_FLAT = 0; const TEXT_DEEP = 1
 // per-document options -> option bytes, or undefined when none is set (the plain native entry points): an entry is an
 // option byte, `true` (no-GC), or { gc: boolean } as in yDocOptions; a Uint8Array is taken as it is
 function optBytes (opts, n) {
@@ -164,6 +166,10 @@ class GpuEngine {
         const u = packBlobs(jobs.map(j => j[0])); const s = packBlobs(jobs.map(j => j[1]))
         if (op === 'step2') return a.step2Many(this.handle, u.arena, u.lens, s.arena, s.lens, optBytes(jobs.map(j => j[2] || 0), jobs.length))
         return ({ diff: a.diffMany, contains: a.containsMany, diffV2: a.diffManyV2 })[op](this.handle, u.arena, u.lens, s.arena, s.lens)
+      }
+      if (op === 'text' || op === 'textDeep') {   // a job is [state, root name bytes]
+        const u = packBlobs(jobs.map(j => j[0])); const n = packBlobs(jobs.map(j => j[1]))
+        return a.text(this.handle, u.arena, u.lens, n.arena, n.lens, op === 'textDeep' ? TEXT_DEEP : TEXT_FLAT)
       }
       if (op === 'restoreVersion') {   // a job is [state, version, option byte]
         const u = packBlobs(jobs.map(j => j[0])); const v = packBlobs(jobs.map(j => j[1]))
@@ -280,6 +286,19 @@ class GpuEngine {
     return unpack(r)
   }
 
+  /**
+   * Plain text of stored documents, as an explicit batch: for doc = Y.applyUpdate(new Y.Doc(), states[i]) the string
+   * doc.getText(names[i]).toString(), or with { deep: true } the walk that also descends into nested types -- the text
+   * of an XmlFragment / Tiptap document, one '\n' after each nested type unless the text is still empty or already
+   * ends in one (ygm_text_v1).  names: strings or UTF-8 bytes.  A name the state has no root for gives ''.
+   */
+  async textMany (states, names, { deep = false } = {}) {
+    if (names.length !== states.length) throw new YgmError(8, 'one root name per state')
+    const jobs = states.map((s, i) => [s, names[i] instanceof Uint8Array ? names[i] : Buffer.from(String(names[i]), 'utf8')])
+    const r = await this._run(deep ? 'textDeep' : 'text', jobs)
+    return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
+  }
+
   /** update format V2 (yjs providers other than Hocuspocus's V1 path): Y.mergeUpdatesV2 / Y.diffUpdateV2 /
    *  Y.encodeStateVectorFromUpdateV2 / yjs 13.6 Y.convertUpdateFormatV1ToV2 / V2ToV1, as explicit batches */
   async mergeManyV2 (docs) { const r = await this._run('mergeV2', docs); return unpack(r) }
@@ -392,6 +411,8 @@ class GpuEnginePool {
     if (!opts) return this._many(names, [states, versions], (e, a, b) => e.restoreVersionMany(a, b))
     return this._many(names, [states, versions, Array.from(opts)], (e, a, b, o) => e.restoreVersionMany(a, b, o))
   }
+  /** textMany with one document name per state (the shard), beside its root name */
+  textMany (docNames, states, names, opts) { return this._many(docNames, [states, names], (e, a, b) => e.textMany(a, b, opts)) }
   stats () { return this.engines.map(e => e.stats()) }
   /**
    * Node-wide totals (the reference's server-wide counters, Hocuspocus.ts:138-160): every numeric field of the
@@ -406,4 +427,4 @@ class GpuEnginePool {
   close () { this.engines.forEach(e => e.close()) }
 }
 
-module.exports = { packJobs, GpuEngine, GpuEnginePool, fnv1a64, YgmError, STATUS, loadAddon, DOC_NO_GC, optBytes }
+module.exports = { packJobs, GpuEngine, GpuEnginePool, fnv1a64, YgmError, STATUS, loadAddon, DOC_NO_GC, TEXT_FLAT, TEXT_DEEP, optBytes }

@@ -213,6 +213,45 @@ class GpuMerge {
     return out
   }
 
+  /**
+   * Plain text (INTEGRATION.md "Text of a document / of a version").  textOf(names, { field, deep }): what each loaded
+   * document says, in one GPU batch over the captured states (base and log merged as takeVersions merges them) ->
+   * Map name -> string.  deep: false is doc.getText(field).toString(); deep: true (the default: Tiptap documents keep
+   * their text in XmlText nodes under the XmlFragment `field`) also descends into nested types, one '\n' after each
+   * unless the text is still empty or already ends in one.  A document that is not loaded, or whose state the engine
+   * refuses, is left out of the map.
+   */
+  async textOf (names, { field = 'default', deep = true } = {}) {
+    const eng = this._engine()
+    const states = await this._statesOf(names)
+    const idx = names.map((_, i) => i).filter(i => states[i] && !(states[i] instanceof Error))
+    const fields = idx.map(() => field)
+    const res = !idx.length ? [] : typeof eng.shardOf === 'function'
+      ? await eng.textMany(idx.map(i => names[i]), idx.map(i => states[i]), fields, { deep })
+      : await eng.textMany(idx.map(i => states[i]), fields, { deep })
+    const out = new Map()
+    idx.forEach((i, k) => { if (!(res[k] instanceof Error)) out.set(names[i], res[k]) })
+    return out
+  }
+
+  /**
+   * versionTexts(entries, { field, deep }): restoreVersions(entries) followed by one text batch over the fulfilled
+   * results -- a one-line preview per saved version without a Y.Doc per version.  Settled per entry as
+   * restoreVersions is: { status: 'fulfilled', value: string } or { status: 'rejected', reason }.
+   */
+  async versionTexts (entries, { field = 'default', deep = true } = {}) {
+    const eng = this._engine()
+    const out = await this.restoreVersions(entries)
+    const ok = out.map((r, i) => r.status === 'fulfilled' ? i : -1).filter(i => i >= 0)
+    if (!ok.length) return out
+    const fields = ok.map(() => field)
+    const res = typeof eng.shardOf === 'function'
+      ? await eng.textMany(ok.map(i => entries[i].documentName), ok.map(i => out[i].value), fields, { deep })
+      : await eng.textMany(ok.map(i => out[i].value), fields, { deep })
+    ok.forEach((i, k) => { out[i] = res[k] instanceof Error ? { status: 'rejected', reason: res[k] } : { status: 'fulfilled', value: res[k] } })
+    return out
+  }
+
   async onConfigure () { this._engine() }
 
   /** fetch -> (GPU merge of snapshot + log rows) -> Y.applyUpdate, as Database.onLoadDocument (Database.ts:44-50) */

@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hocuspocus_amd", "csrc")
-SRC = ("ygm_kernels.hip", "ygm_walk.hip", "ygm_snapshot.hip", "ygm_version.hip", "ygm_v2.hip")
+SRC = ("ygm_kernels.hip", "ygm_walk.hip", "ygm_snapshot.hip", "ygm_text.hip", "ygm_version.hip", "ygm_v2.hip")
 
 
 def remarks(src):
