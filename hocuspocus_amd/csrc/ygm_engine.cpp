@@ -16,151 +16,26 @@
 #include <vector>
 
 #include "../../include/ygm.h"
-
-extern "C" {
-size_t ygm_k_meta_bytes();
-int ygm_k_meta_layout(size_t* sz, size_t* off_big_started, size_t* off_big_scur, size_t* off_payload_sh);
-size_t ygm_k_seq_reader_bytes();
-size_t ygm_k_drec_bytes();
-int ygm_k_launch_doc(int mode, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                     const uint32_t* docs, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                     uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap, hipStream_t s);
-size_t ygm_k_sv_table_bytes(uint32_t n_docs);
-int ygm_k_launch_ask_plan(const uint64_t* doc_off, uint32_t n_docs, const uint32_t* ask_doc, uint32_t n_asks, uint32_t* ask_ix,
-                          uint64_t* ask_base, uint64_t* bs, hipStream_t s);
-int ygm_k_launch_ask_status(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, int32_t* status, uint64_t* len, hipStream_t s);
-int ygm_k_launch_ask_pending(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, uint32_t* list, unsigned int* n_out,
-                             hipStream_t s);
-int ygm_k_launch_doc_lean_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                                 const uint32_t* ask_ix, const uint64_t* ask_base, uint32_t n_asks, uint8_t* out, uint64_t* out_off,
-                                 uint64_t* out_len, int32_t* status, void* meta, uint32_t* defer_list, uint64_t out_cap, uint8_t* tbl,
-                                 uint32_t* tbl_n, hipStream_t s);
-int ygm_k_launch_doc_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                            const uint32_t* docs, const uint32_t* ask_ix, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out,
-                            uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap,
-                            hipStream_t s);
-int ygm_k_launch_pend_split_g(const uint32_t* list, uint32_t P, const uint32_t* ask_ix, const uint8_t* ws, const uint64_t* out_off,
-                              const uint8_t* sv, const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc,
-                              uint8_t* dsv, int pass, hipStream_t s);
-int ygm_k_launch_snap_plan(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, void* cnt, uint64_t* ws_off,
-                           uint64_t* bs, const uint8_t* claim, hipStream_t s);
-int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                           uint64_t* out_len, int32_t* status, uint8_t* claim, unsigned long long* pay, int again, uint64_t slot_total,
-                           const uint8_t* opt, hipStream_t s);
-int ygm_k_launch_text_flat(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
-                           uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, uint8_t* claim,
-                           unsigned long long* pay, int again, uint64_t slot_total, hipStream_t s);
-int ygm_k_launch_text(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
-                      uint32_t flags, uint32_t mode, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
-                      uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim, uint64_t base, hipStream_t s);
-int ygm_k_launch_cont_plan(const uint8_t* st_arena, const uint64_t* st_off, uint32_t n_docs, uint32_t flags, uint64_t* ws_off, uint64_t* bs,
-                           hipStream_t s);
-int ygm_k_launch_cont(const uint8_t* st_arena, const uint64_t* st_off, const uint8_t* up_arena, const uint64_t* up_off, uint32_t n_docs,
-                      uint32_t flags, const uint64_t* ws_off, uint8_t* ws, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
-                      int32_t* status, hipStream_t s);
-int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
-                      uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
-                      uint64_t base, uint32_t* pend_list, unsigned int* pend_n, hipStream_t s);
-int ygm_k_launch_snap_w(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
-                        uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
-                        uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, const uint8_t* opt, hipStream_t s);
-int ygm_k_launch_pend_plan(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, uint64_t* upd_off, uint32_t* doc_upd,
-                           hipStream_t s);
-int ygm_k_launch_pend_copy(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const uint64_t* upd_off, uint8_t* dst,
-                           hipStream_t s);
-int ygm_k_launch_pend_fix(const uint32_t* list, uint32_t P, const uint64_t* m_off, const uint64_t* m_len, const int32_t* m_st,
-                          const int32_t* pst, uint64_t tail, uint64_t* out_off, uint64_t* out_len, int32_t* status, hipStream_t s);
-int ygm_k_launch_pend_split(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const uint8_t* sv,
-                            const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc, uint8_t* dsv, int pass,
-                            hipStream_t s);
-int ygm_k_launch_pend_join(uint32_t P, const uint8_t* ad, const uint64_t* a_off, const uint64_t* a_len, const int32_t* a_st, const uint8_t* bd,
-                           const uint64_t* offs, const uint8_t* cd, const uint64_t* c_off, const uint64_t* c_len, const int32_t* c_st,
-                           uint64_t* upd_off, uint32_t* doc_upd, int32_t* pst, uint8_t* dst, int pass, hipStream_t s);
-int ygm_k_launch_ver_cut(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint8_t* V, const uint64_t* v_off,
-                         uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t out_total, uint64_t* out_off, uint64_t* out_len,
-                         int32_t* status, hipStream_t s);
-int ygm_k_launch_ver_cut_gather(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint32_t* ix, const uint64_t* ask_base,
-                                const uint8_t* V, const uint64_t* v_off, uint32_t n_asks, uint32_t flags, uint8_t* out, uint64_t out_total,
-                                uint64_t* out_off, uint64_t* out_len, int32_t* status, hipStream_t s);
-int ygm_k_launch_pack(const uint8_t* src, const uint64_t* off, const uint64_t* len, const int32_t* status, uint32_t n, uint64_t* bsum,
-                      uint8_t* dst, uint64_t* poff, hipStream_t s);
-int ygm_k_launch_doc_lean(int mode, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* doc_off, const uint8_t* sv_arena,
-                          uint64_t sv_bytes, const uint64_t* sv_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                          uint64_t* out_len, int32_t* status, void* meta, uint32_t* defer_list, uint64_t out_cap, uint8_t* tbl,
-                          uint32_t* tbl_n, hipStream_t s);
-uint32_t ygm_k_lean_stage_bytes();
-int ygm_k_launch_merge_lean(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, uint32_t flags,
-                            uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, void* meta_next,
-                            uint32_t* defer_list, uint64_t out_cap, hipStream_t s, const uint64_t* doc_off, const uint16_t* upd_len);
-int ygm_k_launch_big_wait(void* meta, uint32_t n_large, hipStream_t s);
-int ygm_k_launch_build_off(const uint64_t* doc_off, const uint16_t* upd_len, const uint32_t* doc_upd, const uint32_t* list, uint32_t n,
-                           uint64_t* upd_off, hipStream_t s);
-int ygm_k_launch_merge_lean_wide(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, const uint32_t* list,
-                                 uint32_t n_list, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status,
-                                 void* meta, void* meta_next, uint32_t* defer_list, uint64_t out_cap, const uint16_t* upd_len,
-                                 hipStream_t s);
-int ygm_k_launch_merge_wave(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs,
-                            const unsigned int* n_dev, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
-                            int32_t* status, void* meta, uint32_t* defer_list, uint32_t* fb_list, uint64_t out_cap, hipStream_t s);
-int ygm_k_launch_route_big(const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs, const unsigned int* n_dev, uint32_t n_docs,
-                           uint32_t flags, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, uint32_t* fb_list, uint32_t* rest,
-                           hipStream_t s);
-int ygm_k_launch_merge_fast(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs,
-                            const unsigned int* n_dev, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
-                            int32_t* status, uint64_t slot_total, void* meta, uint32_t* fb_list, uint64_t out_cap, hipStream_t s);
-int ygm_k_launch_merge_seq(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list, uint32_t n_fb,
-                           uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta,
-                           void* readers, int* order, int* tmp, const uint8_t** ubase, uint32_t* ulen, uint64_t upd_cap,
-                           uint32_t* cnt, void* drec, uint64_t byte_cap, uint64_t slot_total, uint64_t out_cap, hipStream_t s);
-int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s);
-size_t ygm_k_v2_cols();
-int ygm_k_launch_v21(int pass, const uint8_t* arena, const uint64_t* upd_off, uint32_t n_upd, const uint32_t* doc_upd, uint32_t n_docs,
-                     uint32_t mode, uint32_t flags, uint64_t* len_or_off, int32_t* st, uint8_t* out, uint8_t* cl, hipStream_t s);
-int ygm_k_launch_v12_count(const uint8_t* v1, const uint64_t* v1_off, const uint64_t* v1_len, const int32_t* v1_st, const uint8_t* v2a,
-                           uint64_t v2n, const uint64_t* upd_off, const uint32_t* doc_upd, const int32_t* ust, uint32_t n_docs, uint32_t mode,
-                           uint32_t flags, uint32_t* L, uint64_t* tot, int32_t* st, const uint8_t* claim, hipStream_t s);
-int ygm_k_launch_v12_write(const uint8_t* v1, const uint64_t* v1_off, const uint64_t* v1_len, const uint8_t* v2a, uint64_t v2n,
-                           const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, uint32_t mode, uint32_t flags, const uint32_t* L,
-                           const uint64_t* off, int32_t* st, uint8_t* out, uint64_t* out_len, const uint8_t* claim, uint64_t base, uint64_t* fo,
-                           hipStream_t s);
-int ygm_k_launch_v12_fast(const uint8_t* v1, const uint64_t* v1_off, const uint64_t* v1_len, const int32_t* v1_st, const uint64_t* slot_off,
-                          const uint32_t* doc_upd, const int32_t* ust, uint32_t n_docs, uint8_t* out, uint64_t* fo, uint64_t* olen, int32_t* ost,
-                          uint8_t* claim, unsigned long long* payload, uint8_t* scr, uint64_t slot_total, hipStream_t s);
-size_t ygm_k_v12_fast_scratch();
-int ygm_k_launch_v2_status(const int32_t* ust, uint32_t n, int32_t* status, uint64_t* len, hipStream_t s);
-int ygm_k_launch_v2_lens(const uint64_t* off, const int32_t* st, uint32_t n, uint64_t* len, hipStream_t s);
-size_t ygm_k_big_blk_bytes();
-size_t ygm_k_big_rec_bytes();
-int ygm_k_launch_big_scan(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list,
-                          uint32_t n_fb, uint32_t flags, void* scan, uint64_t fb_bytes, hipStream_t s);
-int ygm_k_launch_merge_big(int large, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list,
-                           uint32_t n_fb, const uint32_t* fbx, uint32_t n, uint32_t* up_list, uint32_t flags, uint8_t* out,
-                           uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, uint32_t* fb2_list, void* blk,
-                           uint64_t blk_cap, void* rec, uint64_t rec_cap, uint64_t slot_total, uint64_t out_cap, void* scan,
-                           uint64_t fb_bytes, hipStream_t s);
-size_t ygm_k_big_scan_bytes(uint32_t n_fb, uint64_t fb_bytes);
-void ygm_k_big_lists(void* scan, uint32_t n_fb, uint64_t fb_bytes, unsigned long long** cnt, uint32_t** llist, uint32_t** mlist);
-}
+#include "ygm_chunks.hpp"
+#include "ygm_docmeta.hpp"
+#include "ygm_launch.hpp"
 
 namespace {
 
-// mirrors ygm::DocMeta (ygm_docmeta.hpp) field for field; sizeof is a multiple of 16.  ygm_open checks the layout
-// against the kernels' own (ygm_k_meta_layout): read_meta and the counter memsets depend on it
-struct Meta {
-  unsigned int ticket, fault, fb_count, defer_count, lean_defer, big_defer, wide_defer, mid_defer, big_started, route_n;
-  unsigned long long big_scur;
-  unsigned long long fast_total, cursor, payload, fb_upds, fb_bytes, scr_upd_cursor, scr_byte_cursor, big_cursor;
-  unsigned long long payload_sh[16 * 16];
-  unsigned long long payload_total() const {
-    unsigned long long t = payload;
-    for (unsigned long long x : payload_sh) t += x;
-    return t;
-  }
-};
+using Meta = ygm::DocMeta;   // the per-launch device counters: the kernels' own struct (read_meta, the counter memsets)
+unsigned long long payload_total(const Meta& m) {
+  unsigned long long t = m.payload;
+  for (unsigned long long x : m.payload_sh) t += x;
+  return t;
+}
 
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   // keep > 0: the first `keep` bytes survive a regrowth (copied on stream s, which is then synchronised)
   bool ensure(size_t n, size_t keep = 0, hipStream_t s = nullptr) {
     if (n <= cap && p) return true;
@@ -189,6 +64,10 @@ struct DevBuf {
 struct PinBuf {
   void* p = nullptr;
   size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { release(); }
   bool ensure(size_t n, size_t keep = 0) {   // keep: leading bytes preserved across a regrowth
     if (n <= cap && p) return true;
     size_t c = std::max<size_t>(n, 4096);
@@ -285,14 +164,6 @@ const char* ygm_strerror(int code) {
 int ygm_open(int device, uint32_t flags, ygm_ctx** out) {
   if (!out) return YGM_EINVAL;
   *out = nullptr;
-  {   // the host mirror of the device counters must match the kernels' struct
-    size_t sz = 0, o1 = 0, o2 = 0, o3 = 0;
-    ygm_k_meta_layout(&sz, &o1, &o2, &o3);
-    if (sz != sizeof(Meta) || o1 != offsetof(Meta, big_started) || o2 != offsetof(Meta, big_scur) || o3 != offsetof(Meta, payload_sh)) {
-      fprintf(stderr, "ygm: host / device counter layouts differ (%zu vs %zu bytes)\n", sz, sizeof(Meta));
-      return YGM_EINVAL;
-    }
-  }
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return YGM_EDEVICE;
   ygm_ctx* c = new ygm_ctx();
@@ -320,24 +191,14 @@ void ygm_close(ygm_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-  for (DevBuf* b : {&c->arena, &c->offs, &c->docs, &c->sv_arena, &c->sv_offs, &c->opt, &c->out, &c->out_off, &c->out_len, &c->status,
-                    &c->lb, &c->meta, &c->fb_list, &c->defer_list, &c->defer2_list, &c->defer_w_list, &c->route_list, &c->s_readers, &c->s_order, &c->s_tmp, &c->s_ubase, &c->s_ulen, &c->s_cnt,
-                    &c->s_drec, &c->big_blk, &c->big_rec, &c->big_list, &c->big_scan, &c->big_up, &c->lens_off, &c->sv_tbl, &c->sv_tn, &c->ask_ix, &c->ask_base, &c->ask_bs, &c->ask_pl, &c->ask_pn, &c->sn_cnt, &c->sn_off, &c->sn_bs, &c->sn_ws, &c->sn_claim, &c->sn_pay,
-                    &c->sn_pend, &c->pn_off, &c->pn_du, &c->pn_arena,
-                    &c->pq_off, &c->pq_a, &c->pq_b, &c->pq_c, &c->pq_s, &c->pq_st, &c->v2_len, &c->v2_st, &c->v2_bs, &c->v2_v1, &c->v2_L, &c->v2_out, &c->v2_off, &c->v2_olen, &c->v2_ost, &c->v2_fo, &c->v2_claim, &c->v2_pay, &c->v2_scr, &c->v21_cl})
-    b->release();
   for (ygm_ctx* k : c->kid) if (k) ygm_close(k);
   if (c->pend_ctx) ygm_close(c->pend_ctx);
   for (ygm_ctx* k : c->pend_dx) if (k) ygm_close(k);
-  for (DevBuf* b : {&c->pk_data, &c->pk_off, &c->pk_bsum, &c->s2_data, &c->s2_off, &c->s2_bsum, &c->s2_st, &c->vr_out, &c->vr_off, &c->vr_len,
-                    &c->vr_st, &c->vr_pk, &c->vr_pkoff})
-    b->release();
-  for (PinBuf* b : {&c->h_data, &c->h_off, &c->h_len, &c->h_status, &c->h_in}) b->release();
   for (hipEvent_t e : {c->e0, c->e1, c->e2, c->e3}) if (e) (void)hipEventDestroy(e);
   if (c->h_meta) (void)hipHostFree(c->h_meta);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  delete c;
+  delete c;   // every DevBuf / PinBuf member frees itself
 }
 
 int ygm_stats(ygm_ctx* c, ygm_stats_t* out) {
@@ -584,9 +445,9 @@ int ygm_merge_v1_device_finish(ygm_ctx* c, ygm_device_result* out) {
   c->stats.calls++; c->stats.docs += P.n_docs; c->stats.updates += P.n_upd;
   c->stats.docs_fast += n_gen - m.fb_count;   // finished by the wave / workgroup tiers (tier 4 counted above)
   c->stats.docs_lean += P.n_docs - n_gen;      // finished by the lean kernels (narrow + wide)
-  c->stats.bytes_in += P.arena_bytes; c->stats.bytes_out += m.payload_total();
+  c->stats.bytes_in += P.arena_bytes; c->stats.bytes_out += payload_total(m);
   fill_dev_result(c, extent, out);
-  out->payload_bytes = m.payload_total();
+  out->payload_bytes = payload_total(m);
   return YGM_OK;
 }
 
@@ -616,14 +477,15 @@ static int ask_plan(ygm_ctx* c, hipStream_t s, const uint64_t* d_doc_off, uint32
                                c->ask_bs.as<uint64_t>(), s) ? YGM_EDEVICE : YGM_OK;
 }
 
-// gather (mode 1 only): the batch is n_asks asks over n_docs shared documents, ask a answered from document
+enum { DOC_SV = 0, DOC_DIFF = 1 };   // the walker kernels' mode argument (ygm_k_launch_doc, ygm_k_launch_doc_lean)
+// gather (DOC_DIFF only): the batch is n_asks asks over n_docs shared documents, ask a answered from document
 // d_ask_doc[a] with state vector a; results are indexed by ask, slots placed from the asks' scanned state lengths
 static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off,
                           const uint8_t* d_sv, uint64_t sv_bytes, const uint64_t* d_sv_off, uint32_t n_docs, void* stream,
                           ygm_device_result* out, uint32_t extra_flags = 0, bool gather = false, const uint32_t* d_ask_doc = nullptr,
                           uint32_t n_asks = 0) {
   const uint32_t flags = c ? c->flags | extra_flags : 0;
-  if (!c || !out || (gather && mode != 1)) return YGM_EINVAL;
+  if (!c || !out || (gather && mode != DOC_DIFF)) return YGM_EINVAL;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   (void)hipSetDevice(c->device);
   int e = YGM_OK;
@@ -641,7 +503,7 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
   e = prep_outputs(c, n_docs, out_cap, s, true);
   if (e) return e;
   void* meta = c->meta_slot(2);
-  if (mode == 1 && (!c->sv_tbl.ensure(ygm_k_sv_table_bytes(n_docs)) || !c->sv_tn.ensure(4ull * n_docs + 4))) return YGM_ENOMEM;
+  if (mode == DOC_DIFF && (!c->sv_tbl.ensure(ygm_k_sv_table_bytes(n_docs)) || !c->sv_tn.ensure(4ull * n_docs + 4))) return YGM_ENOMEM;
   HIPCHK(hipEventRecord(c->e0, s));
   if (gather) {
     if (ygm_k_launch_doc_lean_gather(d_arena, d_doc_off, d_sv, d_sv_off, c->ask_ix.as<uint32_t>(), c->ask_base.as<uint64_t>(), n_asks,
@@ -679,7 +541,7 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
   // gather: an ask of a refused state id carries YGM_EINVAL (whatever the kernels left there)
   if (gather && ygm_k_launch_ask_status(c->ask_ix.as<uint32_t>(), n_asks, nullptr, c->status.as<int32_t>(), c->out_len.as<uint64_t>(), s))
     return YGM_EDEVICE;
-  const uint64_t payload = m.payload_total() + m.fast_total;
+  const uint64_t payload = payload_total(m) + m.fast_total;
   c->stats.calls++; c->stats.docs += n_docs; c->stats.docs_fast += m.lean_defer; c->stats.docs_lean += n_docs - m.lean_defer;
   c->stats.bytes_in += arena_bytes; c->stats.bytes_out += payload;
   fill_dev_result(c, slot_total + m.fast_total, out);
@@ -1102,12 +964,12 @@ int ygm_diff_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes,
   // (the state-vector arena's extent is the last offset; its 16-byte window reads stay inside its padding)
   uint64_t sv_end = 0;
   if (n_docs && hipMemcpy(&sv_end, d_sv_off + n_docs, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
-  return run_doc_kernel(c, 1, d_arena, arena_bytes, d_doc_off, d_sv_arena, sv_end, d_sv_off, n_docs, stream, out);
+  return run_doc_kernel(c, DOC_DIFF, d_arena, arena_bytes, d_doc_off, d_sv_arena, sv_end, d_sv_off, n_docs, stream, out);
 }
 
 int ygm_sv_from_update_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off, uint32_t n_docs,
                                  void* stream, ygm_device_result* out) {
-  return run_doc_kernel(c, 0, d_arena, arena_bytes, d_doc_off, nullptr, 0, nullptr, n_docs, stream, out);
+  return run_doc_kernel(c, DOC_SV, d_arena, arena_bytes, d_doc_off, nullptr, 0, nullptr, n_docs, stream, out);
 }
 
 // SyncStep2 of the documents the snapshot left pending (P of them, list c->sn_pend, PendHdr layouts in its output
@@ -1191,7 +1053,7 @@ int ygm_sync_step2_opts_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t 
   if (e || (e = pack_snapshots(c, s, r1, n_docs))) return e;
   uint64_t sv_end = 0;
   if (n_docs && hipMemcpy(&sv_end, d_sv_off + n_docs, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
-  e = run_doc_kernel(c, 1, c->s2_data.as<uint8_t>(), r1.payload_bytes, c->s2_off.as<uint64_t>(), d_sv_arena, sv_end, d_sv_off, n_docs, s,
+  e = run_doc_kernel(c, DOC_DIFF, c->s2_data.as<uint8_t>(), r1.payload_bytes, c->s2_off.as<uint64_t>(), d_sv_arena, sv_end, d_sv_off, n_docs, s,
                      out, YGM_F_KEEP_SUB);
   if (dbg) fprintf(stderr, "ygm step2: diff rc %d\n", e);
   if (e) return e;
@@ -1215,7 +1077,7 @@ int ygm_diff_shared_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena
   if (!c || !out || (n_asks && (!d_sv_off || !d_ask_doc))) return YGM_EINVAL;
   uint64_t sv_end = 0;
   if (n_asks && hipMemcpy(&sv_end, d_sv_off + n_asks, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
-  return run_doc_kernel(c, 1, d_arena, arena_bytes, d_doc_off, d_sv_arena, sv_end, d_sv_off, n_docs, stream, out, 0, true, d_ask_doc, n_asks);
+  return run_doc_kernel(c, DOC_DIFF, d_arena, arena_bytes, d_doc_off, d_sv_arena, sv_end, d_sv_off, n_docs, stream, out, 0, true, d_ask_doc, n_asks);
 }
 
 // SyncStep2 of a reconnect storm: the snapshot batch over the n_states states (each once), packed; the gather diff
@@ -1270,7 +1132,7 @@ int ygm_sync_step2_shared_opts_v1_device(ygm_ctx* c, const uint8_t* d_states, ui
   if ((e = pack_snapshots(c, s, r1, n_states))) return e;
   uint64_t sv_end = 0;
   if (n_asks && hipMemcpy(&sv_end, d_sv_off + n_asks, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
-  e = run_doc_kernel(c, 1, c->s2_data.as<uint8_t>(), r1.payload_bytes, c->s2_off.as<uint64_t>(), d_sv_arena, sv_end, d_sv_off, n_states, s,
+  e = run_doc_kernel(c, DOC_DIFF, c->s2_data.as<uint8_t>(), r1.payload_bytes, c->s2_off.as<uint64_t>(), d_sv_arena, sv_end, d_sv_off, n_states, s,
                      out, YGM_F_KEEP_SUB, true, d_ask_state, n_asks);
   if (e) return e;
   // the status carry from state to ask (the gather form of k_v2_status)
@@ -1456,10 +1318,11 @@ int ygm_convert_v2_to_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t are
 }
 
 // ------------------------------------------------------------------ host API
-// A batch is cut into chunks of whole documents (about YGM_CHUNK_BYTES of input each) that alternate
-// between two stage contexts, each with its own stream and device buffers:
-//   stage i+1: host arena -> pinned staging (CPU copy) -> H2D        (stream of stage (i+1) % 2)
-//   chunk i:   kernels -> device-side packing of the outputs -> D2H   (stream of stage i % 2)
+// A batch is cut into chunks (about YGM_CHUNK_BYTES of input each; the planners are in ygm_chunks.hpp) that alternate
+// between two stage contexts, each with its own stream and device buffers.  run_pipeline drives three parts:
+//   stage:  host arenas -> pinned staging (CPU copy) -> H2D               (chunk i + 1, stream of stage (i + 1) % 2)
+//   run:    the operation's device entry point on the staged chunk (OPS)  (chunk i, stream of stage i % 2)
+//   drain:  device-side packing of the outputs -> D2H                     (chunk i, same stream)
 // so the CPU copy and the H2D of one chunk overlap the kernels of the previous one, and the D2H moves
 // only the packed outputs (not the per-document slots).  h2d_ms / d2h_ms are the copies' HIP-event
 // times (summed over chunks); the results live in the parent context's pinned buffers.
@@ -1474,23 +1337,124 @@ static uint64_t chunk_bytes(uint64_t in_bytes) {
 }
 
 namespace {
-struct Chunk {   // documents [d0, d1): merge updates [u0, u1) / SV-diff documents
-  uint32_t d0, d1, u0, u1;
-  uint64_t pos = 0, payload = 0;   // packed output position in the parent's result, bytes
-  hipEvent_t h0 = nullptr, h1 = nullptr, o0 = nullptr, o1 = nullptr;
+// The host API's operations; OPS below holds one row per operation, in this order.
+enum class Op : uint8_t {
+  Sv, Diff, Merge, Snapshot, Contains, MergeV2, DiffV2, SvV2, V1ToV2, V2ToV1, Step2, DiffShared, Step2Shared, VersionTake,
+  VersionRestore, VersionRestoreShared, Text, Count
 };
+enum class Primary : uint8_t { Docs, Updates, States };   // what the first arena's offsets count
+enum class OptOf : uint8_t { None, Doc, State, Ask };     // whose option bytes travel with a chunk
+
 struct HostCall {
-  int mode;   // 0 sv, 1 diff, 2 merge, 3 snapshot, 4 contains (second arena in the sv slots); update V2: 5 merge, 6 diff,
-              // 7 sv, 8 V1 -> V2, 9 V2 -> V1; 10 sync step2 (states + state vectors); 11 / 12 the shared-state diff /
-              // step2 (host_shared_call: n_docs states, n_upd asks, upd_doc = the asks' states); 13 version take, 14 version
-              // restore (states + versions in the sv slots, restored_opt as opt); 15 the shared-state version restore
-              // (host_shared_call: versions in the sv slots, restored_opt per ask); 16 text (states + root names in the
-              // sv slots, text_mode)
-  const uint8_t* arena; const uint64_t* off; const uint32_t* upd_doc; const uint8_t* sv_arena; const uint64_t* sv_off;
-  uint32_t n_upd, n_docs;
-  const uint8_t* opt = nullptr;   // modes 3 / 10 / 14: n_docs option bytes, mode 12: one per state, mode 15: one per ask (null: none); each chunk stages its slice
-  uint32_t text_mode = 0;         // mode 16: YGM_TEXT_FLAT / YGM_TEXT_DEEP
+  Op op;
+  const uint8_t* arena; const uint64_t* off; uint32_t n_pri;   // primary inputs: documents, a merge's updates, shared states
+  uint32_t n_res;                                               // results: documents, or the asks of a shared call
+  const uint32_t* link = nullptr;   // merge: each update's document; shared: each ask's state
+  const uint8_t* arena2 = nullptr; const uint64_t* off2 = nullptr;   // the second arena, one entry per result (OpRow::second)
+  const uint8_t* opt = nullptr;     // option bytes (OpRow::opt says whose), null: none; each chunk stages its slice
+  uint32_t text_mode = 0;           // Op::Text: YGM_TEXT_FLAT / YGM_TEXT_DEEP
 };
+// a chunk's inputs on its stage context, as the device entry points take them
+struct Staged {
+  const uint8_t* arena; uint64_t bytes; const uint64_t* off; uint32_t n_pri, n_res;
+  const uint8_t* arena2; const uint64_t* off2;
+  const uint32_t* link;   // merge: the documents' update ranges (n_res + 1); shared: each ask's state, relative to the chunk
+  const uint8_t* opt;     // null: no options
+  uint32_t text_mode;
+};
+struct Chunk : ygm::ChunkRange {
+  Staged in{};                     // filled by stage
+  uint64_t pos = 0, payload = 0;   // packed output position in the parent's result, bytes
+  hipEvent_t h0 = nullptr, h1 = nullptr, o0 = nullptr, o1 = nullptr;   // around the H2D / the D2H copies
+};
+struct OpRow {
+  Op op;
+  Primary primary;
+  bool second;    // a second arena per result (diff: state vectors, contains: updates, restore: versions, text: root names)
+  OptOf opt;
+  int (*run)(ygm_ctx* k, const Staged& S, ygm_device_result* dr);   // the staged chunk on stage context k
+  int (*enqueue)(ygm_ctx* k, const Staged& S);   // device work enqueued before the next chunk is staged (null: none)
+};
+
+static int run_sv(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_sv_from_update_v1_device(k, S.arena, S.bytes, S.off, S.n_res, nullptr, dr);
+}
+static int run_diff(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_diff_v1_device(k, S.arena, S.bytes, S.off, S.arena2, S.off2, S.n_res, nullptr, dr);
+}
+// (the lean kernel of chunk i runs while chunk i + 1 is staged)
+static int enqueue_merge(ygm_ctx* k, const Staged& S) {
+  return ygm_merge_v1_device_async(k, S.arena, S.bytes, S.off, S.link, S.n_pri, S.n_res, nullptr);
+}
+static int run_merge(ygm_ctx* k, const Staged&, ygm_device_result* dr) { return ygm_merge_v1_device_finish(k, dr); }
+static int run_snapshot(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_snapshot_opts_v1_device(k, S.arena, S.bytes, S.off, S.opt, S.n_res, nullptr, dr);
+}
+static int run_contains(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_contains_v1_device(k, S.arena, S.off, S.arena2, S.off2, S.n_res, nullptr, dr);
+}
+static int run_merge_v2(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_merge_v2_device(k, S.arena, S.bytes, S.off, S.link, S.n_pri, S.n_res, nullptr, dr);
+}
+static int run_diff_v2(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_diff_v2_device(k, S.arena, S.bytes, S.off, S.arena2, S.off2, S.n_res, nullptr, dr);
+}
+static int run_sv_v2(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_sv_from_update_v2_device(k, S.arena, S.bytes, S.off, S.n_res, nullptr, dr);
+}
+static int run_v1_to_v2(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_convert_v1_to_v2_device(k, S.arena, S.bytes, S.off, S.n_res, nullptr, dr);
+}
+static int run_v2_to_v1(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_convert_v2_to_v1_device(k, S.arena, S.bytes, S.off, S.n_res, nullptr, dr);
+}
+static int run_step2(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_sync_step2_opts_v1_device(k, S.arena, S.bytes, S.off, S.opt, S.arena2, S.off2, S.n_res, nullptr, dr);
+}
+static int run_diff_shared(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_diff_shared_v1_device(k, S.arena, S.bytes, S.off, S.n_pri, S.arena2, S.off2, S.link, S.n_res, nullptr, dr);
+}
+static int run_step2_shared(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_sync_step2_shared_opts_v1_device(k, S.arena, S.bytes, S.off, S.opt, S.n_pri, S.arena2, S.off2, S.link, S.n_res, nullptr, dr);
+}
+static int run_version_take(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_version_take_v1_device(k, S.arena, S.bytes, S.off, S.n_res, nullptr, dr);
+}
+static int run_version_restore(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_version_restore_v1_device(k, S.arena, S.off, S.arena2, S.off2, S.opt, S.n_res, nullptr, dr);
+}
+static int run_version_restore_shared(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_version_restore_shared_v1_device(k, S.arena, S.bytes, S.off, S.n_pri, S.arena2, S.off2, S.link, S.opt, S.n_res, nullptr, dr);
+}
+static int run_text(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_text_v1_device(k, S.arena, S.bytes, S.off, S.arena2, S.off2, S.text_mode, S.n_res, nullptr, dr);
+}
+
+constexpr OpRow OPS[] = {
+    {Op::Sv, Primary::Docs, false, OptOf::None, run_sv, nullptr},
+    {Op::Diff, Primary::Docs, true, OptOf::None, run_diff, nullptr},
+    {Op::Merge, Primary::Updates, false, OptOf::None, run_merge, enqueue_merge},
+    {Op::Snapshot, Primary::Docs, false, OptOf::Doc, run_snapshot, nullptr},
+    {Op::Contains, Primary::Docs, true, OptOf::None, run_contains, nullptr},
+    {Op::MergeV2, Primary::Updates, false, OptOf::None, run_merge_v2, nullptr},
+    {Op::DiffV2, Primary::Docs, true, OptOf::None, run_diff_v2, nullptr},
+    {Op::SvV2, Primary::Docs, false, OptOf::None, run_sv_v2, nullptr},
+    {Op::V1ToV2, Primary::Docs, false, OptOf::None, run_v1_to_v2, nullptr},
+    {Op::V2ToV1, Primary::Docs, false, OptOf::None, run_v2_to_v1, nullptr},
+    {Op::Step2, Primary::Docs, true, OptOf::Doc, run_step2, nullptr},
+    {Op::DiffShared, Primary::States, true, OptOf::None, run_diff_shared, nullptr},
+    {Op::Step2Shared, Primary::States, true, OptOf::State, run_step2_shared, nullptr},
+    {Op::VersionTake, Primary::Docs, false, OptOf::None, run_version_take, nullptr},
+    {Op::VersionRestore, Primary::Docs, true, OptOf::Doc, run_version_restore, nullptr},
+    {Op::VersionRestoreShared, Primary::States, true, OptOf::Ask, run_version_restore_shared, nullptr},
+    {Op::Text, Primary::Docs, true, OptOf::None, run_text, nullptr},
+};
+constexpr bool ops_in_order() {
+  for (size_t i = 0; i < sizeof(OPS) / sizeof(OPS[0]); i++) if (OPS[i].op != (Op)i) return false;
+  return true;
+}
+static_assert(sizeof(OPS) / sizeof(OPS[0]) == (size_t)Op::Count && ops_in_order(), "one row per operation, in the enum's order");
+extern "C++" constexpr const OpRow& row(Op op) { return OPS[(size_t)op]; }
 }  // namespace
 
 static int stage_ctx(ygm_ctx* c, int i, ygm_ctx** out) {
@@ -1534,94 +1498,72 @@ static void par_for(size_t n, F f) {
   for (auto& x : th) x.join();
 }
 
-// CPU copy of a chunk's inputs into the stage's pinned buffer, then the async H2D copies
-static bool is_merge(int mode) { return mode == 2 || mode == 5; }
-static int chunk_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
-  const bool two = H.mode == 1 || H.mode == 4 || H.mode == 6 || H.mode == 10 || H.mode == 14 || H.mode == 16;   // a second arena per document (diff: state vectors, contains: updates, restore: versions, text: root names)
-  const uint32_t nd = C.d1 - C.d0;
-  const uint64_t a0 = is_merge(H.mode) ? H.off[C.u0] : H.off[C.d0], a1 = is_merge(H.mode) ? H.off[C.u1] : H.off[C.d1];
-  const uint64_t bytes = a1 - a0, ab = (bytes + 64 + 15) & ~15ull;
-  const uint32_t nu = is_merge(H.mode) ? C.u1 - C.u0 : nd;
-  uint64_t s0 = 0, s1 = 0, sb = 0;
-  if (two) { s0 = H.sv_off[C.d0]; s1 = H.sv_off[C.d1]; sb = ((s1 - s0) + 64 + 15) & ~15ull; }
-  const uint64_t n_off = (uint64_t)nu + 1, n_doc = is_merge(H.mode) ? (uint64_t)nd + 1 : 0, n_sv = two ? (uint64_t)nd + 1 : 0;
-  const uint64_t n_opt = H.opt ? (uint64_t)nd : 0;
-  const uint64_t need = ab + 8 * n_off + sb + 8 * n_sv + 4 * n_doc + n_opt + 64;
-  if (!k->h_in.ensure(need)) return YGM_ENOMEM;
+// a staged arena: its bytes, 64 readable zero bytes after them, a multiple of 16
+static uint64_t staged_bytes(uint64_t n) { return (n + 64 + 15) & ~15ull; }
+static void rebase(uint64_t* dst, const uint64_t* src, uint64_t n, uint64_t base) {
+  par_for(n, [=](size_t a, size_t b) { for (size_t j = a; j < b; j++) dst[j] = src[j] - base; });
+}
+
+// stage: CPU copy of a chunk's inputs into the stage's pinned buffer -- [arena | offsets | second arena | its offsets |
+// link table | option bytes] -- then one async H2D copy per part; C.in is what the run function reads
+static int stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
+  const OpRow& R = row(H.op);
+  const uint32_t n_res = C.r1 - C.r0, n_pri = C.p1 - C.p0;
+  const uint64_t a0 = H.off[C.p0], bytes = H.off[C.p1] - a0, ab = staged_bytes(bytes);
+  const uint64_t s0 = R.second ? H.off2[C.r0] : 0, sbytes = R.second ? H.off2[C.r1] - s0 : 0, sb = R.second ? staged_bytes(sbytes) : 0;
+  const uint64_t n_off = (uint64_t)n_pri + 1, n_off2 = R.second ? (uint64_t)n_res + 1 : 0;
+  const uint64_t n_link = R.primary == Primary::Updates ? (uint64_t)n_res + 1 : R.primary == Primary::States ? n_res : 0;
+  // a shared state's option byte travels in each of its chunks; the version restore's belong to the restored documents
+  const uint64_t n_opt = !H.opt || R.opt == OptOf::None ? 0 : R.opt == OptOf::State ? n_pri : n_res;
+  if (!k->h_in.ensure(ab + 8 * n_off + sb + 8 * n_off2 + 4 * n_link + n_opt + 64)) return YGM_ENOMEM;
   uint8_t* P = k->h_in.as<uint8_t>();
-  par_memcpy(P, H.arena + a0, bytes); memset(P + bytes, 0, ab - bytes);
   uint64_t* ro = (uint64_t*)(P + ab);
-  const uint64_t* src_off = is_merge(H.mode) ? H.off + C.u0 : H.off + C.d0;
-  par_for(n_off, [=](size_t a, size_t b) { for (size_t j = a; j < b; j++) ro[j] = src_off[j] - a0; });
-  uint8_t* q = P + ab + 8 * n_off;
-  if (two) {
-    memcpy(q, H.sv_arena + s0, s1 - s0); memset(q + (s1 - s0), 0, sb - (s1 - s0));
-    uint64_t* rs = (uint64_t*)(q + sb);
-    for (uint64_t j = 0; j < n_sv; j++) rs[j] = H.sv_off[C.d0 + j] - s0;
-    q += sb + 8 * n_sv;
+  uint8_t* q = (uint8_t*)(ro + n_off);
+  uint64_t* ro2 = (uint64_t*)(q + sb);
+  uint32_t* lk = (uint32_t*)(ro2 + n_off2);
+  uint8_t* po = (uint8_t*)(lk + n_link);
+  if (bytes) par_memcpy(P, H.arena + a0, bytes);
+  memset(P + bytes, 0, ab - bytes);
+  rebase(ro, H.off + C.p0, n_off, a0);
+  if (R.second) {
+    if (sbytes) memcpy(q, H.arena2 + s0, sbytes);
+    memset(q + sbytes, 0, sb - sbytes);
+    rebase(ro2, H.off2 + C.r0, n_off2, s0);
   }
-  if (is_merge(H.mode)) {   // per-document update ranges, relative to the chunk (one walk over its updates: a binary
-                            // search per document measured 2-3x slower end to end, tools/host_probe.py)
-    uint32_t* du = (uint32_t*)q;
-    du[0] = 0;
-    uint32_t u = C.u0;
-    for (uint32_t d = 0; d < nd; d++) { while (u < C.u1 && H.upd_doc[u] == C.d0 + d) u++; du[d + 1] = u - C.u0; }
+  if (R.primary == Primary::Updates) {   // per-document update ranges, relative to the chunk (one walk over its updates: a
+                                         // binary search per document measured 2-3x slower end to end, tools/host_probe.py)
+    lk[0] = 0;
+    uint32_t u = C.p0;
+    for (uint32_t d = 0; d < n_res; d++) { while (u < C.p1 && H.link[u] == C.r0 + d) u++; lk[d + 1] = u - C.p0; }
+  } else if (R.primary == Primary::States) {
+    for (uint32_t j = 0; j < n_res; j++) lk[j] = H.link[C.r0 + j] - C.p0;
   }
-  uint8_t* po = q + 4 * n_doc;   // the chunk's option bytes, after everything else
-  if (n_opt) memcpy(po, H.opt + C.d0, n_opt);
-  if (!k->arena.ensure(ab) || !k->offs.ensure(8 * n_off) || (two && (!k->sv_arena.ensure(sb) || !k->sv_offs.ensure(8 * n_sv))) ||
-      (is_merge(H.mode) && !k->docs.ensure(4 * n_doc)) || (n_opt && !k->opt.ensure(n_opt)))
+  if (n_opt) memcpy(po, H.opt + (R.opt == OptOf::State ? C.p0 : C.r0), n_opt);
+  if (!k->arena.ensure(ab) || !k->offs.ensure(8 * n_off) || (R.second && (!k->sv_arena.ensure(sb) || !k->sv_offs.ensure(8 * n_off2))) ||
+      (R.primary != Primary::Docs && !k->docs.ensure(4 * n_link + 4)) || (n_opt && !k->opt.ensure(n_opt)))
     return YGM_ENOMEM;
-  HIPCHK(hipEventRecord(C.h0, k->stream));
-  HIPCHK(hipMemcpyAsync(k->arena.p, P, ab, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(hipMemcpyAsync(k->offs.p, ro, 8 * n_off, hipMemcpyHostToDevice, k->stream));
-  if (two) {
-    HIPCHK(hipMemcpyAsync(k->sv_arena.p, P + ab + 8 * n_off, sb, hipMemcpyHostToDevice, k->stream));
-    HIPCHK(hipMemcpyAsync(k->sv_offs.p, P + ab + 8 * n_off + sb, 8 * n_sv, hipMemcpyHostToDevice, k->stream));
+  hipStream_t s = k->stream;
+  HIPCHK(hipEventRecord(C.h0, s));
+  HIPCHK(hipMemcpyAsync(k->arena.p, P, ab, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(k->offs.p, ro, 8 * n_off, hipMemcpyHostToDevice, s));
+  if (R.second) {
+    HIPCHK(hipMemcpyAsync(k->sv_arena.p, q, sb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(k->sv_offs.p, ro2, 8 * n_off2, hipMemcpyHostToDevice, s));
   }
-  if (is_merge(H.mode)) HIPCHK(hipMemcpyAsync(k->docs.p, q, 4 * n_doc, hipMemcpyHostToDevice, k->stream));
-  if (n_opt) HIPCHK(hipMemcpyAsync(k->opt.p, po, n_opt, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(hipEventRecord(C.h1, k->stream));
+  if (n_link) HIPCHK(hipMemcpyAsync(k->docs.p, lk, 4 * n_link, hipMemcpyHostToDevice, s));
+  if (n_opt) HIPCHK(hipMemcpyAsync(k->opt.p, po, n_opt, hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(C.h1, s));
+  C.in = Staged{k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), n_pri, n_res, k->sv_arena.as<uint8_t>(), k->sv_offs.as<uint64_t>(),
+                k->docs.as<uint32_t>(), n_opt ? k->opt.as<uint8_t>() : nullptr, H.text_mode};
   return YGM_OK;
 }
 
-// kernels of a staged chunk, packing, and the async D2H into the parent's pinned results
-static int chunk_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint64_t& pos, bool merge_enqueued) {
-  const uint32_t nd = C.d1 - C.d0;
-  const uint64_t bytes = (is_merge(H.mode) ? H.off[C.u1] - H.off[C.u0] : H.off[C.d1] - H.off[C.d0]);
-  ygm_device_result dr;
-  int e;
-  if (H.mode == 5) e = ygm_merge_v2_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->docs.as<uint32_t>(), C.u1 - C.u0, nd,
-                                           nullptr, &dr);
-  else if (H.mode == 6) e = ygm_diff_v2_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
-                                               k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 7) e = ygm_sv_from_update_v2_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 8) e = ygm_convert_v1_to_v2_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 9) e = ygm_convert_v2_to_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 2) e = merge_enqueued ? ygm_merge_v1_device_finish(k, &dr)
-                                      : ygm_merge_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->docs.as<uint32_t>(),
-                                                            C.u1 - C.u0, nd, nullptr, &dr);
-  else if (H.mode == 4) e = ygm_contains_v1_device(k, k->arena.as<uint8_t>(), k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
-                                                   k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 13) e = ygm_version_take_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 14) e = ygm_version_restore_v1_device(k, k->arena.as<uint8_t>(), k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
-                                                           k->sv_offs.as<uint64_t>(), H.opt && nd ? k->opt.as<uint8_t>() : nullptr, nd,
-                                                           nullptr, &dr);
-  else if (H.mode == 3) e = ygm_snapshot_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
-                                                        H.opt && nd ? k->opt.as<uint8_t>() : nullptr, nd, nullptr, &dr);
-  else if (H.mode == 10) e = ygm_sync_step2_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
-                                                           H.opt && nd ? k->opt.as<uint8_t>() : nullptr, k->sv_arena.as<uint8_t>(),
-                                                           k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
-  else if (H.mode == 16) e = ygm_text_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
-                                                k->sv_offs.as<uint64_t>(), H.text_mode, nd, nullptr, &dr);
-  else if (H.mode == 1) e = ygm_diff_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), k->sv_arena.as<uint8_t>(),
-                                               k->sv_offs.as<uint64_t>(), nd, nullptr, &dr);
-  else e = ygm_sv_from_update_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), nd, nullptr, &dr);
-  if (e) return e;
-  const uint32_t nb = (nd + 255) / 256;
-  if (!k->pk_data.ensure(dr.payload_bytes + 64) || !k->pk_off.ensure(8ull * nd + 8) || !k->pk_bsum.ensure(8ull * nb + 16)) return YGM_ENOMEM;
-  if (nd && ygm_k_launch_pack(dr.data, dr.off, dr.len, dr.status, nd, k->pk_bsum.as<uint64_t>(), k->pk_data.as<uint8_t>(),
-                              k->pk_off.as<uint64_t>(), k->stream))
+// drain: device-side packing of a chunk's results, and the async D2H into the parent's pinned results at `pos`
+static int drain(ygm_ctx* c, ygm_ctx* k, Chunk& C, const ygm_device_result& dr, uint64_t& pos) {
+  const uint32_t n = C.r1 - C.r0, nb = (n + 255) / 256;
+  if (!k->pk_data.ensure(dr.payload_bytes + 64) || !k->pk_off.ensure(8ull * n + 8) || !k->pk_bsum.ensure(8ull * nb + 16)) return YGM_ENOMEM;
+  if (n && ygm_k_launch_pack(dr.data, dr.off, dr.len, dr.status, n, k->pk_bsum.as<uint64_t>(), k->pk_data.as<uint8_t>(),
+                             k->pk_off.as<uint64_t>(), k->stream))
     return YGM_EDEVICE;
   C.pos = pos; C.payload = dr.payload_bytes;
   if (pos + dr.payload_bytes + 1 > c->h_data.cap) {   // regrowth moves the bytes copied so far: let those copies land first
@@ -1630,10 +1572,10 @@ static int chunk_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint64
   }
   HIPCHK(hipEventRecord(C.o0, k->stream));
   if (dr.payload_bytes) HIPCHK(hipMemcpyAsync(c->h_data.as<uint8_t>() + pos, k->pk_data.p, dr.payload_bytes, hipMemcpyDeviceToHost, k->stream));
-  if (nd) {
-    HIPCHK(hipMemcpyAsync(c->h_off.as<uint64_t>() + C.d0, k->pk_off.p, 8ull * nd, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(hipMemcpyAsync(c->h_len.as<uint64_t>() + C.d0, dr.len, 8ull * nd, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(hipMemcpyAsync(c->h_status.as<int32_t>() + C.d0, dr.status, 4ull * nd, hipMemcpyDeviceToHost, k->stream));
+  if (n) {
+    HIPCHK(hipMemcpyAsync(c->h_off.as<uint64_t>() + C.r0, k->pk_off.p, 8ull * n, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(hipMemcpyAsync(c->h_len.as<uint64_t>() + C.r0, dr.len, 8ull * n, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(hipMemcpyAsync(c->h_status.as<int32_t>() + C.r0, dr.status, 4ull * n, hipMemcpyDeviceToHost, k->stream));
   }
   HIPCHK(hipEventRecord(C.o1, k->stream));
   pos += dr.payload_bytes;
@@ -1653,222 +1595,35 @@ static void add_stage_stats(ygm_ctx* c, const ygm_stats_t& a, const ygm_stats_t&
   c->stats.docs_snapshot += a.docs_snapshot - b.docs_snapshot;
 }
 
-static int host_call(ygm_ctx* c, const HostCall& H, ygm_result* out) {
+// The driver: the planned chunks, double-buffered over the two stage contexts, into the parent's pinned results.
+// out_hint sizes the pinned result at first (outputs are usually no larger than the inputs; grown when a chunk needs more)
+static int run_pipeline(ygm_ctx* c, const HostCall& H, const std::vector<ygm::ChunkRange>& plan, uint64_t out_hint, ygm_result* out) {
   (void)hipSetDevice(c->device);
-  const uint32_t n = H.n_docs;
-  // chunks of whole documents
-  std::vector<Chunk> ch;
-  {
-    const uint64_t CB = chunk_bytes(n ? (is_merge(H.mode) ? H.off[H.n_upd] - H.off[0] : H.off[n] - H.off[0]) : 0);
-    uint32_t d = 0, u = 0;
-    while (d < n || ch.empty()) {
-      Chunk C{};
-      C.d0 = d; C.u0 = u;
-      const uint64_t base = is_merge(H.mode) ? H.off[u] : H.off[d];
-      // the input end of documents [C.d0, x): binary searches over the ascending upd_doc / offsets (a walk over every
-      // update took milliseconds per call on batches of millions of updates)
-      auto first_upd = [&](uint32_t x) { return (uint32_t)(std::lower_bound(H.upd_doc, H.upd_doc + H.n_upd, x) - H.upd_doc); };
-      auto end_of = [&](uint32_t x) { return is_merge(H.mode) ? H.off[first_upd(x)] : H.off[x]; };
-      uint32_t lo = d + 1, hi = n;   // the last x in [d + 1, n] whose documents fit in CB (at least one document)
-      if (n > d && end_of(n) - base <= CB) lo = n;
-      else if (n > d) {
-        while (lo < hi) { const uint32_t mid = lo + (hi - lo + 1) / 2; if (end_of(mid) - base <= CB) lo = mid; else hi = mid - 1; }
-      }
-      if (n > d) { d = lo; u = is_merge(H.mode) ? first_upd(d) : d; }
-      C.d1 = d; C.u1 = u;
-      ch.push_back(C);
-      if (n == 0) break;
-    }
-  }
-  // (outputs are usually no larger than the inputs: sized so, grown when a chunk needs more)
-  const uint64_t in_bytes = n ? (is_merge(H.mode) ? H.off[H.n_upd] - H.off[0] : H.off[n] - H.off[0]) : 0;
+  const OpRow& R = row(H.op);
+  const uint32_t n = H.n_res;
   if (!c->h_off.ensure(8ull * n + 8) || !c->h_len.ensure(8ull * n + 8) || !c->h_status.ensure(4ull * n + 4) ||
-      !c->h_data.ensure(in_bytes + 16ull * n + 4096))
+      !c->h_data.ensure(out_hint + 16ull * n + 4096))
     return YGM_ENOMEM;
+  std::vector<Chunk> ch(plan.size());
+  for (size_t i = 0; i < ch.size(); i++) static_cast<ygm::ChunkRange&>(ch[i]) = plan[i];
   int e = YGM_OK;
-  ygm_ctx* k[2];
-  if ((e = stage_ctx(c, 0, &k[0])) || (ch.size() > 1 && (e = stage_ctx(c, 1, &k[1])))) return e;
-  for (Chunk& C : ch)
-    if (hipEventCreate(&C.h0) != hipSuccess || hipEventCreate(&C.h1) != hipSuccess || hipEventCreate(&C.o0) != hipSuccess ||
-        hipEventCreate(&C.o1) != hipSuccess) { e = YGM_EDEVICE; break; }
-  ygm_stats_t s0[2] = {k[0]->stats, ch.size() > 1 ? k[1]->stats : ygm_stats_t{}};
-  uint64_t pos = 0;
-  if (!e) e = chunk_stage(k[0], H, ch[0]);
-  for (size_t i = 0; i < ch.size() && !e; i++) {
-    ygm_ctx* ki = k[i & 1];
-    bool enq = false;
-    if (H.mode == 2) {   // the lean kernel of chunk i runs while chunk i + 1 is staged
-      const uint64_t bytes = H.off[ch[i].u1] - H.off[ch[i].u0];
-      if ((e = ygm_merge_v1_device_async(ki, ki->arena.as<uint8_t>(), bytes, ki->offs.as<uint64_t>(), ki->docs.as<uint32_t>(),
-                                         ch[i].u1 - ch[i].u0, ch[i].d1 - ch[i].d0, nullptr)))
-        break;
-      enq = true;
-    }
-    if (i + 1 < ch.size()) {
-      ygm_ctx* kn = k[(i + 1) & 1];
-      // the stage's previous chunk (i - 1) has left its pinned staging (its kernels have run)
-      if ((e = chunk_stage(kn, H, ch[i + 1]))) break;
-    }
-    e = chunk_run(c, ki, H, ch[i], pos, enq);
-  }
-  for (int j = 0; j < (ch.size() > 1 ? 2 : 1); j++) if (hipStreamSynchronize(k[j]->stream) != hipSuccess && !e) e = YGM_EDEVICE;
-  if (!e) {
-    float ms = 0;
-    for (Chunk& C : ch) {
-      if (hipEventElapsedTime(&ms, C.h0, C.h1) == hipSuccess) c->stats.h2d_ms += ms;
-      if (hipEventElapsedTime(&ms, C.o0, C.o1) == hipSuccess) c->stats.d2h_ms += ms;
-      uint64_t* off = c->h_off.as<uint64_t>() + C.d0;
-      for (uint32_t d = 0; d < C.d1 - C.d0; d++) off[d] += C.pos;
-    }
-    for (int j = 0; j < (ch.size() > 1 ? 2 : 1); j++) add_stage_stats(c, k[j]->stats, s0[j]);
-    int32_t* st = c->h_status.as<int32_t>();
-    uint64_t* ln = c->h_len.as<uint64_t>();
-    for (uint32_t d = 0; d < n; d++) {
-      if (st[d] >= 100 || st[d] < 0) st[d] = YGM_EDEVICE;   // never leaves internal codes
-      if (st[d] != YGM_OK) ln[d] = 0;
-    }
-    out->data = c->h_data.as<uint8_t>(); out->off = c->h_off.as<uint64_t>(); out->len = ln; out->status = st;
-    out->n_docs = n; out->data_bytes = pos;
-  }
-  for (Chunk& C : ch) for (hipEvent_t ev : {C.h0, C.h1, C.o0, C.o1}) if (ev) (void)hipEventDestroy(ev);
-  return e;
-}
-
-// ---- shared states: n_docs states, n_asks asks (ask_doc non-decreasing).  A chunk is a range of states [u0, u1) with
-// its contiguous asks [d0, d1) (results and offsets are indexed by ask); its budget counts virtual bytes, the states'
-// bytes plus, over its asks, the ask's state length -- what bounds the slot region.  A state whose asks alone exceed
-// the budget is split: chunks of that one state, each staging (and, step2, snapshotting) it again.
-static void shared_chunks(const uint64_t* off, uint32_t n_docs, const uint32_t* ask_doc, uint32_t n_asks, uint64_t CB, std::vector<Chunk>& ch) {
-  uint32_t a = 0;   // the first ask not yet placed
-  Chunk C{};
-  uint64_t cur = 0;
-  bool open = false;
-  auto close = [&]() { if (open) { ch.push_back(C); open = false; cur = 0; } };
-  for (uint32_t sd = 0; sd < n_docs; sd++) {
-    const uint64_t L = off[sd + 1] - off[sd];
-    uint32_t a1 = a;
-    while (a1 < n_asks && ask_doc[a1] == sd) a1++;
-    const uint64_t v = L + (uint64_t)(a1 - a) * L;
-    if (open && cur + v > CB) close();
-    if (v <= CB || a1 - a <= 1) {
-      if (!open) { C = Chunk{}; C.u0 = sd; C.d0 = a; open = true; }
-      C.u1 = sd + 1; C.d1 = a1; cur += v;
-    } else {   // one state over several chunks
-      const uint64_t per = CB > L ? (CB - L) / L : 1;
-      const uint32_t m = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per, 1), a1 - a);
-      for (uint32_t x = a; x < a1; x += m) {
-        C = Chunk{}; C.u0 = sd; C.u1 = sd + 1; C.d0 = x; C.d1 = std::min(a1, x + m);
-        ch.push_back(C);
-      }
-    }
-    a = a1;
-  }
-  close();
-  if (ch.empty()) { C = Chunk{}; ch.push_back(C); }
-}
-static int shared_stage(ygm_ctx* k, const HostCall& H, Chunk& C) {
-  const uint32_t ns = C.u1 - C.u0, na = C.d1 - C.d0;
-  const uint64_t a0 = H.off[C.u0], bytes = H.off[C.u1] - a0, ab = (bytes + 64 + 15) & ~15ull;
-  const uint64_t s0 = H.sv_off[C.d0], svb = H.sv_off[C.d1] - s0, sb = (svb + 64 + 15) & ~15ull;
-  const uint64_t n_off = (uint64_t)ns + 1, n_sv = (uint64_t)na + 1;
-  // the chunk's states' option bytes (a split state's byte in each of its chunks); the version restore's belong to the
-  // restored documents: the chunk's asks' bytes
-  const bool ask_opt = H.mode == 15;
-  const uint64_t n_opt = H.opt ? (uint64_t)(ask_opt ? na : ns) : 0;
-  if (!k->h_in.ensure(ab + 8 * n_off + sb + 8 * n_sv + 4ull * na + n_opt + 64)) return YGM_ENOMEM;
-  uint8_t* P = k->h_in.as<uint8_t>();
-  if (bytes) par_memcpy(P, H.arena + a0, bytes);
-  memset(P + bytes, 0, ab - bytes);
-  uint64_t* ro = (uint64_t*)(P + ab);
-  for (uint64_t j = 0; j < n_off; j++) ro[j] = H.off[C.u0 + j] - a0;
-  uint8_t* q = P + ab + 8 * n_off;
-  if (svb) memcpy(q, H.sv_arena + s0, svb);
-  memset(q + svb, 0, sb - svb);
-  uint64_t* rs = (uint64_t*)(q + sb);
-  for (uint64_t j = 0; j < n_sv; j++) rs[j] = H.sv_off[C.d0 + j] - s0;
-  uint32_t* ra = (uint32_t*)(q + sb + 8 * n_sv);
-  for (uint32_t j = 0; j < na; j++) ra[j] = H.upd_doc[C.d0 + j] - C.u0;
-  uint8_t* po = (uint8_t*)(ra + na);
-  if (n_opt) memcpy(po, H.opt + (ask_opt ? C.d0 : C.u0), n_opt);
-  if (!k->arena.ensure(ab) || !k->offs.ensure(8 * n_off) || !k->sv_arena.ensure(sb) || !k->sv_offs.ensure(8 * n_sv) ||
-      !k->docs.ensure(4ull * na + 4) || (n_opt && !k->opt.ensure(n_opt)))
-    return YGM_ENOMEM;
-  HIPCHK(hipEventRecord(C.h0, k->stream));
-  HIPCHK(hipMemcpyAsync(k->arena.p, P, ab, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(hipMemcpyAsync(k->offs.p, ro, 8 * n_off, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(hipMemcpyAsync(k->sv_arena.p, q, sb, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(hipMemcpyAsync(k->sv_offs.p, rs, 8 * n_sv, hipMemcpyHostToDevice, k->stream));
-  if (na) HIPCHK(hipMemcpyAsync(k->docs.p, ra, 4ull * na, hipMemcpyHostToDevice, k->stream));
-  if (n_opt) HIPCHK(hipMemcpyAsync(k->opt.p, po, n_opt, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(hipEventRecord(C.h1, k->stream));
-  return YGM_OK;
-}
-static int shared_run(ygm_ctx* c, ygm_ctx* k, const HostCall& H, Chunk& C, uint64_t& pos) {
-  const uint32_t ns = C.u1 - C.u0, na = C.d1 - C.d0;
-  const uint64_t bytes = H.off[C.u1] - H.off[C.u0];
-  ygm_device_result dr;
-  int e;
-  if (H.mode == 12) e = ygm_sync_step2_shared_opts_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(),
-                                                             H.opt && ns ? k->opt.as<uint8_t>() : nullptr, ns, k->sv_arena.as<uint8_t>(),
-                                                             k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
-  else if (H.mode == 15) e = ygm_version_restore_shared_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), ns,
-                                                                  k->sv_arena.as<uint8_t>(), k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(),
-                                                                  H.opt && na ? k->opt.as<uint8_t>() : nullptr, na, nullptr, &dr);
-  else e = ygm_diff_shared_v1_device(k, k->arena.as<uint8_t>(), bytes, k->offs.as<uint64_t>(), ns, k->sv_arena.as<uint8_t>(),
-                                     k->sv_offs.as<uint64_t>(), k->docs.as<uint32_t>(), na, nullptr, &dr);
-  if (e) return e;
-  const uint32_t nb = (na + 255) / 256;
-  if (!k->pk_data.ensure(dr.payload_bytes + 64) || !k->pk_off.ensure(8ull * na + 8) || !k->pk_bsum.ensure(8ull * nb + 16)) return YGM_ENOMEM;
-  if (na && ygm_k_launch_pack(dr.data, dr.off, dr.len, dr.status, na, k->pk_bsum.as<uint64_t>(), k->pk_data.as<uint8_t>(),
-                              k->pk_off.as<uint64_t>(), k->stream))
-    return YGM_EDEVICE;
-  C.pos = pos; C.payload = dr.payload_bytes;
-  if (pos + dr.payload_bytes + 1 > c->h_data.cap) {   // regrowth moves the bytes copied so far: let those copies land first
-    for (ygm_ctx* x : c->kid) if (x) HIPCHK(hipStreamSynchronize(x->stream));
-    if (!c->h_data.ensure(pos + dr.payload_bytes + 1, pos)) return YGM_ENOMEM;
-  }
-  HIPCHK(hipEventRecord(C.o0, k->stream));
-  if (dr.payload_bytes) HIPCHK(hipMemcpyAsync(c->h_data.as<uint8_t>() + pos, k->pk_data.p, dr.payload_bytes, hipMemcpyDeviceToHost, k->stream));
-  if (na) {
-    HIPCHK(hipMemcpyAsync(c->h_off.as<uint64_t>() + C.d0, k->pk_off.p, 8ull * na, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(hipMemcpyAsync(c->h_len.as<uint64_t>() + C.d0, dr.len, 8ull * na, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(hipMemcpyAsync(c->h_status.as<int32_t>() + C.d0, dr.status, 4ull * na, hipMemcpyDeviceToHost, k->stream));
-  }
-  HIPCHK(hipEventRecord(C.o1, k->stream));
-  pos += dr.payload_bytes;
-  return YGM_OK;
-}
-static int host_shared_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, const uint8_t* sv_arena,
-                            const uint64_t* sv_off, const uint32_t* ask_doc, uint32_t n_asks, ygm_result* out, const uint8_t* opt = nullptr) {
-  if (!c || !out || (n_docs && !doc_off) || (n_asks && (!sv_off || !ask_doc))) return YGM_EINVAL;
-  for (uint32_t d = 0; d < n_docs; d++) if (doc_off[d + 1] < doc_off[d]) return YGM_EINVAL;
-  for (uint32_t a = 0; a < n_asks; a++)
-    if (ask_doc[a] >= n_docs || (a && ask_doc[a] < ask_doc[a - 1]) || sv_off[a + 1] < sv_off[a]) return YGM_EINVAL;
-  if ((n_docs && doc_off[n_docs] > doc_off[0] && !arena) || (n_asks && sv_off[n_asks] > sv_off[0] && !sv_arena)) return YGM_EINVAL;
-  static const uint64_t zero_off[1] = {0};
-  HostCall H{mode, arena, n_docs ? doc_off : zero_off, ask_doc, sv_arena, n_asks ? sv_off : zero_off, n_asks, n_docs, opt};
-  (void)hipSetDevice(c->device);
-  uint64_t in_bytes = n_docs ? doc_off[n_docs] - doc_off[0] : 0, vbytes = in_bytes;
-  for (uint32_t a = 0; a < n_asks; a++) vbytes += doc_off[ask_doc[a] + 1] - doc_off[ask_doc[a]];
-  std::vector<Chunk> ch;
-  shared_chunks(H.off, n_docs, ask_doc, n_asks, chunk_bytes(vbytes), ch);
-  const uint32_t n = n_asks;
-  if (!c->h_off.ensure(8ull * n + 8) || !c->h_len.ensure(8ull * n + 8) || !c->h_status.ensure(4ull * n + 4) ||
-      !c->h_data.ensure(std::min<uint64_t>(vbytes, 1ull << 30) + 16ull * n + 4096))
-    return YGM_ENOMEM;
-  int e = YGM_OK;
-  ygm_ctx* k[2];
-  if ((e = stage_ctx(c, 0, &k[0])) || (ch.size() > 1 && (e = stage_ctx(c, 1, &k[1])))) return e;
-  for (Chunk& C : ch)
-    if (hipEventCreate(&C.h0) != hipSuccess || hipEventCreate(&C.h1) != hipSuccess || hipEventCreate(&C.o0) != hipSuccess ||
-        hipEventCreate(&C.o1) != hipSuccess) { e = YGM_EDEVICE; break; }
   const int nk = ch.size() > 1 ? 2 : 1;
+  ygm_ctx* k[2] = {nullptr, nullptr};
+  for (int j = 0; j < nk; j++) if ((e = stage_ctx(c, j, &k[j]))) return e;
+  for (Chunk& C : ch)
+    if (hipEventCreate(&C.h0) != hipSuccess || hipEventCreate(&C.h1) != hipSuccess || hipEventCreate(&C.o0) != hipSuccess ||
+        hipEventCreate(&C.o1) != hipSuccess) { e = YGM_EDEVICE; break; }
   ygm_stats_t s0[2] = {k[0]->stats, nk > 1 ? k[1]->stats : ygm_stats_t{}};
   uint64_t pos = 0;
-  if (!e) e = shared_stage(k[0], H, ch[0]);
+  if (!e) e = stage(k[0], H, ch[0]);
   for (size_t i = 0; i < ch.size() && !e; i++) {
-    if (i + 1 < ch.size() && (e = shared_stage(k[(i + 1) & 1], H, ch[i + 1]))) break;
-    e = shared_run(c, k[i & 1], H, ch[i], pos);
+    ygm_ctx* ki = k[i & 1];
+    if (R.enqueue && (e = R.enqueue(ki, ch[i].in))) break;
+    // the next stage's previous chunk (i - 1) has left its pinned staging (its kernels have run)
+    if (i + 1 < ch.size() && (e = stage(k[(i + 1) & 1], H, ch[i + 1]))) break;
+    ygm_device_result dr;
+    if ((e = R.run(ki, ch[i].in, &dr))) break;
+    e = drain(c, ki, ch[i], dr, pos);
   }
   for (int j = 0; j < nk; j++) if (hipStreamSynchronize(k[j]->stream) != hipSuccess && !e) e = YGM_EDEVICE;
   if (!e) {
@@ -1876,8 +1631,8 @@ static int host_shared_call(ygm_ctx* c, int mode, const uint8_t* arena, const ui
     for (Chunk& C : ch) {
       if (hipEventElapsedTime(&ms, C.h0, C.h1) == hipSuccess) c->stats.h2d_ms += ms;
       if (hipEventElapsedTime(&ms, C.o0, C.o1) == hipSuccess) c->stats.d2h_ms += ms;
-      uint64_t* off = c->h_off.as<uint64_t>() + C.d0;
-      for (uint32_t d = 0; d < C.d1 - C.d0; d++) off[d] += C.pos;
+      uint64_t* off = c->h_off.as<uint64_t>() + C.r0;
+      for (uint32_t d = 0; d < C.r1 - C.r0; d++) off[d] += C.pos;
     }
     for (int j = 0; j < nk; j++) add_stage_stats(c, k[j]->stats, s0[j]);
     int32_t* st = c->h_status.as<int32_t>();
@@ -1893,22 +1648,32 @@ static int host_shared_call(ygm_ctx* c, int mode, const uint8_t* arena, const ui
   return e;
 }
 
-int ygm_diff_shared_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, const uint8_t* sv_arena,
-                       const uint64_t* sv_off, const uint32_t* ask_doc, uint32_t n_asks, ygm_result* out) {
-  return host_shared_call(c, 11, arena, doc_off, n_docs, sv_arena, sv_off, ask_doc, n_asks, out);
-}
-int ygm_sync_step2_shared_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, uint32_t n_states, const uint8_t* sv_arena,
-                             const uint64_t* sv_off, const uint32_t* ask_state, uint32_t n_asks, ygm_result* out) {
-  return host_shared_call(c, 12, states, state_off, n_states, sv_arena, sv_off, ask_state, n_asks, out);
-}
-int ygm_sync_step2_shared_opts_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* state_opt, uint32_t n_states,
-                                  const uint8_t* sv_arena, const uint64_t* sv_off, const uint32_t* ask_state, uint32_t n_asks,
-                                  ygm_result* out) {
-  return host_shared_call(c, 12, states, state_off, n_states, sv_arena, sv_off, ask_state, n_asks, out, state_opt);
+static const uint64_t ZERO_OFF[1] = {0};   // the offsets of an empty batch
+
+// chunks of whole documents (H.off: the documents', or a merge's updates' offsets)
+static int host_call(ygm_ctx* c, const HostCall& H, ygm_result* out) {
+  const uint64_t in_bytes = H.off[H.n_pri] - H.off[0];
+  return run_pipeline(c, H, ygm::plan_doc_chunks(H.off, H.n_res, row(H.op).primary == Primary::Updates, H.link, H.n_pri, chunk_bytes(in_bytes)),
+                      in_bytes, out);
 }
 
-int ygm_merge_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* upd_doc, uint32_t n_upd, uint32_t n_docs,
-                 ygm_result* out) {
+// shared states: n_docs states, n_asks asks (ask_doc non-decreasing), results and the second arena indexed by ask
+static int host_shared_call(ygm_ctx* c, Op op, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, const uint8_t* sv_arena,
+                            const uint64_t* sv_off, const uint32_t* ask_doc, uint32_t n_asks, ygm_result* out, const uint8_t* opt = nullptr) {
+  if (!c || !out || (n_docs && !doc_off) || (n_asks && (!sv_off || !ask_doc))) return YGM_EINVAL;
+  for (uint32_t d = 0; d < n_docs; d++) if (doc_off[d + 1] < doc_off[d]) return YGM_EINVAL;
+  for (uint32_t a = 0; a < n_asks; a++)
+    if (ask_doc[a] >= n_docs || (a && ask_doc[a] < ask_doc[a - 1]) || sv_off[a + 1] < sv_off[a]) return YGM_EINVAL;
+  if ((n_docs && doc_off[n_docs] > doc_off[0] && !arena) || (n_asks && sv_off[n_asks] > sv_off[0] && !sv_arena)) return YGM_EINVAL;
+  HostCall H{op, arena, n_docs ? doc_off : ZERO_OFF, n_docs, n_asks, ask_doc, sv_arena, n_asks ? sv_off : ZERO_OFF, opt};
+  uint64_t vbytes = H.off[n_docs] - H.off[0];   // virtual bytes: the states', plus each ask's state length
+  for (uint32_t a = 0; a < n_asks; a++) vbytes += doc_off[ask_doc[a] + 1] - doc_off[ask_doc[a]];
+  return run_pipeline(c, H, ygm::plan_shared_chunks(H.off, n_docs, ask_doc, n_asks, chunk_bytes(vbytes)), std::min<uint64_t>(vbytes, 1ull << 30),
+                      out);
+}
+
+static int host_merge_call(ygm_ctx* c, Op op, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* upd_doc, uint32_t n_upd,
+                           uint32_t n_docs, ygm_result* out) {
   if (!c || !out || (n_upd && (!arena || !upd_off || !upd_doc))) return YGM_EINVAL;
   // document ids non-decreasing, offsets non-decreasing
   std::atomic<int> bad{0};
@@ -1917,102 +1682,105 @@ int ygm_merge_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, cons
       if (upd_doc[i] >= n_docs || (i && upd_doc[i] < upd_doc[i - 1]) || upd_off[i + 1] < upd_off[i]) { bad = 1; return; }
   });
   if (bad) return YGM_EINVAL;
-  static const uint64_t zero_off[1] = {0};
-  HostCall H{2, arena, n_upd ? upd_off : zero_off, upd_doc, nullptr, nullptr, n_upd, n_docs};
+  HostCall H{op, arena, n_upd ? upd_off : ZERO_OFF, n_upd, n_docs, upd_doc};
   return host_call(c, H, out);
 }
 
-int ygm_merge_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* upd_doc, uint32_t n_upd, uint32_t n_docs,
-                 ygm_result* out) {
-  if (!c || !out || (n_upd && (!arena || !upd_off || !upd_doc))) return YGM_EINVAL;
-  for (uint32_t i = 0; i < n_upd; i++)
-    if (upd_doc[i] >= n_docs || (i && upd_doc[i] < upd_doc[i - 1]) || upd_off[i + 1] < upd_off[i]) return YGM_EINVAL;
-  static const uint64_t zero_off[1] = {0};
-  HostCall H{5, arena, n_upd ? upd_off : zero_off, upd_doc, nullptr, nullptr, n_upd, n_docs};
-  return host_call(c, H, out);
-}
-
-static int host_doc_call(ygm_ctx* c, int mode, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena,
-                         const uint64_t* sv_off, uint32_t n_docs, ygm_result* out, const uint8_t* opt = nullptr) {
+static int host_doc_call(ygm_ctx* c, Op op, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* arena2, const uint64_t* off2,
+                         uint32_t n_docs, ygm_result* out, const uint8_t* opt = nullptr) {
   if (!c || !out || (n_docs && (!arena || !doc_off))) return YGM_EINVAL;
-  const bool two = mode == 1 || mode == 4 || mode == 6 || mode == 10 || mode == 14 || mode == 16;
-  if (two && n_docs && (!sv_arena || !sv_off)) return YGM_EINVAL;
+  const bool two = row(op).second;
+  if (two && n_docs && (!arena2 || !off2)) return YGM_EINVAL;
   for (uint32_t d = 0; d < n_docs; d++) {
     if (doc_off[d + 1] < doc_off[d]) return YGM_EINVAL;
-    if (two && sv_off[d + 1] < sv_off[d]) return YGM_EINVAL;
+    if (two && off2[d + 1] < off2[d]) return YGM_EINVAL;
   }
-  static const uint64_t zero_off[1] = {0};
-  HostCall H{mode, arena, n_docs ? doc_off : zero_off, nullptr, sv_arena, n_docs ? sv_off : zero_off, 0, n_docs, opt};
+  HostCall H{op, arena, n_docs ? doc_off : ZERO_OFF, n_docs, n_docs, nullptr, arena2, n_docs ? off2 : ZERO_OFF, opt};
   return host_call(c, H, out);
 }
 
+int ygm_merge_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* upd_doc, uint32_t n_upd, uint32_t n_docs,
+                 ygm_result* out) {
+  return host_merge_call(c, Op::Merge, arena, upd_off, upd_doc, n_upd, n_docs, out);
+}
+int ygm_merge_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* upd_doc, uint32_t n_upd, uint32_t n_docs,
+                 ygm_result* out) {
+  return host_merge_call(c, Op::MergeV2, arena, upd_off, upd_doc, n_upd, n_docs, out);
+}
+int ygm_sv_from_update_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::Sv, arena, doc_off, nullptr, nullptr, n_docs, out);
+}
+int ygm_diff_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
+                uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::Diff, arena, doc_off, sv_arena, sv_off, n_docs, out);
+}
+int ygm_diff_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
+                uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::DiffV2, arena, doc_off, sv_arena, sv_off, n_docs, out);
+}
+int ygm_sv_from_update_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::SvV2, arena, doc_off, nullptr, nullptr, n_docs, out);
+}
+int ygm_convert_v1_to_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::V1ToV2, arena, doc_off, nullptr, nullptr, n_docs, out);
+}
+int ygm_convert_v2_to_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::V2ToV1, arena, doc_off, nullptr, nullptr, n_docs, out);
+}
 int ygm_contains_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* updates, const uint64_t* update_off,
                     uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 4, states, state_off, updates, update_off, n_docs, out);
+  return host_doc_call(c, Op::Contains, states, state_off, updates, update_off, n_docs, out);
 }
-
+int ygm_snapshot_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::Snapshot, arena, doc_off, nullptr, nullptr, n_docs, out);
+}
+int ygm_snapshot_opts_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* doc_opt, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::Snapshot, arena, doc_off, nullptr, nullptr, n_docs, out, doc_opt);
+}
+int ygm_sync_step2_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* sv_arena, const uint64_t* sv_off,
+                      uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::Step2, states, state_off, sv_arena, sv_off, n_docs, out);
+}
+int ygm_sync_step2_opts_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* state_opt, const uint8_t* sv_arena,
+                           const uint64_t* sv_off, uint32_t n_docs, ygm_result* out) {
+  return host_doc_call(c, Op::Step2, states, state_off, sv_arena, sv_off, n_docs, out, state_opt);
+}
 int ygm_version_take_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 13, states, state_off, nullptr, nullptr, n_docs, out);
+  return host_doc_call(c, Op::VersionTake, states, state_off, nullptr, nullptr, n_docs, out);
 }
 int ygm_version_restore_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* versions, const uint64_t* version_off,
                            const uint8_t* restored_opt, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 14, states, state_off, versions, version_off, n_docs, out, restored_opt);
-}
-
-int ygm_version_restore_shared_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, uint32_t n_states, const uint8_t* versions,
-                                  const uint64_t* version_off, const uint32_t* ask_state, const uint8_t* restored_opt, uint32_t n_asks,
-                                  ygm_result* out) {
-  return host_shared_call(c, 15, states, state_off, n_states, versions, version_off, ask_state, n_asks, out, restored_opt);
-}
-
-int ygm_snapshot_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 3, arena, doc_off, nullptr, nullptr, n_docs, out);
+  return host_doc_call(c, Op::VersionRestore, states, state_off, versions, version_off, n_docs, out, restored_opt);
 }
 int ygm_text_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* names, const uint64_t* name_off, uint32_t mode,
                 uint32_t n_docs, ygm_result* out) {
   if (!c || !out || mode > YGM_TEXT_DEEP || (n_docs && (!states || !state_off || !name_off))) return YGM_EINVAL;
   for (uint32_t d = 0; d < n_docs; d++) if (state_off[d + 1] < state_off[d] || name_off[d + 1] < name_off[d]) return YGM_EINVAL;
-  static const uint64_t zero_off[1] = {0};
   static const uint8_t no_names[1] = {0};   // (every name empty: the arena may be NULL)
   if (n_docs && !names) { if (name_off[n_docs] != name_off[0]) return YGM_EINVAL; names = no_names; }   // (no byte of it is read)
-  HostCall H{16, states, n_docs ? state_off : zero_off, nullptr, names, n_docs ? name_off : zero_off, 0, n_docs};
+  HostCall H{Op::Text, states, n_docs ? state_off : ZERO_OFF, n_docs, n_docs, nullptr, names, n_docs ? name_off : ZERO_OFF};
   H.text_mode = mode;
   return host_call(c, H, out);
 }
-int ygm_snapshot_opts_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* doc_opt, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 3, arena, doc_off, nullptr, nullptr, n_docs, out, doc_opt);
-}
 
-int ygm_sync_step2_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                      uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 10, states, state_off, sv_arena, sv_off, n_docs, out);
+int ygm_diff_shared_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, const uint8_t* sv_arena,
+                       const uint64_t* sv_off, const uint32_t* ask_doc, uint32_t n_asks, ygm_result* out) {
+  return host_shared_call(c, Op::DiffShared, arena, doc_off, n_docs, sv_arena, sv_off, ask_doc, n_asks, out);
 }
-int ygm_sync_step2_opts_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* state_opt, const uint8_t* sv_arena,
-                           const uint64_t* sv_off, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 10, states, state_off, sv_arena, sv_off, n_docs, out, state_opt);
+int ygm_sync_step2_shared_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, uint32_t n_states, const uint8_t* sv_arena,
+                             const uint64_t* sv_off, const uint32_t* ask_state, uint32_t n_asks, ygm_result* out) {
+  return host_shared_call(c, Op::Step2Shared, states, state_off, n_states, sv_arena, sv_off, ask_state, n_asks, out);
 }
-
-int ygm_diff_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 1, arena, doc_off, sv_arena, sv_off, n_docs, out);
+int ygm_sync_step2_shared_opts_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* state_opt, uint32_t n_states,
+                                  const uint8_t* sv_arena, const uint64_t* sv_off, const uint32_t* ask_state, uint32_t n_asks,
+                                  ygm_result* out) {
+  return host_shared_call(c, Op::Step2Shared, states, state_off, n_states, sv_arena, sv_off, ask_state, n_asks, out, state_opt);
 }
-
-int ygm_sv_from_update_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 0, arena, doc_off, nullptr, nullptr, n_docs, out);
-}
-
-int ygm_diff_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 6, arena, doc_off, sv_arena, sv_off, n_docs, out);
-}
-int ygm_sv_from_update_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 7, arena, doc_off, nullptr, nullptr, n_docs, out);
-}
-int ygm_convert_v1_to_v2(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 8, arena, doc_off, nullptr, nullptr, n_docs, out);
-}
-int ygm_convert_v2_to_v1(ygm_ctx* c, const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, ygm_result* out) {
-  return host_doc_call(c, 9, arena, doc_off, nullptr, nullptr, n_docs, out);
+int ygm_version_restore_shared_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, uint32_t n_states, const uint8_t* versions,
+                                  const uint64_t* version_off, const uint32_t* ask_state, const uint8_t* restored_opt, uint32_t n_asks,
+                                  ygm_result* out) {
+  return host_shared_call(c, Op::VersionRestoreShared, states, state_off, n_states, versions, version_off, ask_state, n_asks, out,
+                          restored_opt);
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include "ygm_merge_big.hpp"
 #include "ygm_seqdoc.hpp"
 #include "ygm_v1.hpp"
+#include "ygm_launch.hpp"
 
 #ifdef YGM_DIAG
 // diagnostic build only (libygm_diag.so): per-phase shader-clock sums of k_merge_fast
@@ -3661,11 +3662,6 @@ int ygm_k_launch_merge_big(int large, const uint8_t* arena, const uint64_t* upd_
   return launch_rc(__func__);
 }
 size_t ygm_k_meta_bytes() { return sizeof(DocMeta); }
-int ygm_k_meta_layout(size_t* sz, size_t* off_big_started, size_t* off_big_scur, size_t* off_payload_sh) {
-  *sz = sizeof(DocMeta); *off_big_started = offsetof(DocMeta, big_started); *off_big_scur = offsetof(DocMeta, big_scur);
-  *off_payload_sh = offsetof(DocMeta, payload_sh);
-  return 0;
-}
 size_t ygm_k_seq_reader_bytes() { return sizeof(Stream); }
 size_t ygm_k_drec_bytes() { return sizeof(DRec); }
 

@@ -19,6 +19,7 @@
 #include "ygm_common.hpp"
 #include "ygm_snapshot.hpp"
 #include "ygm_snap_text.hpp"
+#include "ygm_launch.hpp"
 
 namespace ygm {
 

@@ -12,6 +12,7 @@
 
 #include "ygm_common.hpp"
 #include "ygm_text.hpp"
+#include "ygm_launch.hpp"
 
 namespace ygm {
 

@@ -18,6 +18,7 @@
 #include "ygm_v2.hpp"
 #include "ygm_v2_fast.hpp"
 #include "ygm_v21_fast.hpp"
+#include "ygm_launch.hpp"
 
 namespace ygm {
 

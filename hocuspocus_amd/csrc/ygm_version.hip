@@ -16,6 +16,7 @@
 
 #include "ygm_common.hpp"
 #include "ygm_version.hpp"
+#include "ygm_launch.hpp"
 
 namespace ygm {
 

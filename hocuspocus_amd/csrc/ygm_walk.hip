@@ -8,6 +8,7 @@
 
 #include "ygm_docmeta.hpp"
 #include "ygm_doc_walk.hpp"
+#include "ygm_launch.hpp"
 
 #ifdef YGM_DIAG
 // diagnostic build only (libygm_diag.so): walker census [0, 8) and per-section wave clocks [8, 13)
@@ -894,7 +895,6 @@ int ygm_walk_diag_read(unsigned long long* out, int reset) {
 }
 #endif
 
-int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s);
 // ask_ix[n_asks], ask_base[n_asks + 1] (bs: scan scratch of (n_asks + 1 + 255) / 256 + 1 entries)
 int ygm_k_launch_ask_plan(const uint64_t* doc_off, uint32_t n_docs, const uint32_t* ask_doc, uint32_t n_asks, uint32_t* ask_ix,
                           uint64_t* ask_base, uint64_t* bs, hipStream_t s) {
