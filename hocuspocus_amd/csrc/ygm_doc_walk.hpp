@@ -32,6 +32,14 @@
 // 0x20 beside an origin, GC info bytes other than 0, values >= 2^32, blocks not strictly
 // client-descending or empty, delete sets not strictly client-descending or with empty clients,
 // state vectors of > 16 entries or with trailing bytes, outputs over the slot, documents >= 1 GB.
+// The kernel also defers, beyond what the rules need (tests/walker_docs.py restates all of it as a predicate):
+//   * a struct whose content starts at or past its byte 60 (the content's length is read inside the struct's
+//     64-byte window);
+//   * a y-key, parentSub or XmlElement / XmlHook name that is not ASCII or ends past the struct's 64-byte window;
+//   * a document with a run of >= 6 top-bit bytes or (diff only) a top-bit byte followed by 0x00 anywhere in its
+//     bytes -- dw_commit looks at bytes, not fields: the payload of a ContentBinary counts;
+//   * varuints of > 5 bytes in the fields it reads (counts, clients, clocks, lengths; not ids and delete ranges,
+//     which it copies), empty documents, GC / Deleted / String lengths of 0.
 #pragma once
 #include "ygm_merge_lean.hpp"
 
@@ -174,7 +182,7 @@ YDEV uint64_t dw_bytes_at(const DWLds& L, uint32_t l, uint32_t q, uint64_t lo, u
 // a varString at p of the unit at q (window win): returns the position after it; ASCII only, inside the window
 YDEV uint32_t dw_str(const DWLds& L, uint32_t l, uint32_t q, uint64_t win, uint64_t lo, uint64_t hi, uint32_t p, uint32_t& bad) {
   const uint32_t e = dw_ctz(dw_from(win, p));
-  const uint32_t n = dw_val(dw_bytes_at(L, l, q, lo, hi, p < 56u ? p : 56u), e - p + 1u, bad);
+  const uint32_t n = dw_val(dw_bytes_at(L, l, q, lo, hi, p), e - p + 1u, bad);   // (p <= 63: the ring read wraps inside the lane's ring)
   const uint32_t s = e + 1u, f = s + n;
   bad |= f > 64u ? 1u : 0u;
   bad |= (s < 64u && ((~win >> s) & dw_lowmask(n))) ? 1u : 0u;

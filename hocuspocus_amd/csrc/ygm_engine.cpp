@@ -521,6 +521,10 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
   if (m.fault) return YGM_EDEVICE;
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) { c->stats.kernel_ms += ms; c->stats.lean_ms += ms; c->stats.lean_launches++; }
+  // YGM_TIER_COUNTS (testing knob): who finished the call's documents, one stderr line (exact: the walker's deferred list)
+  if (getenv("YGM_TIER_COUNTS"))
+    fprintf(stderr, "ygm walk tiers: op %s docs %u walker %u exact %u\n", gather ? "diff_shared" : mode == DOC_DIFF ? "diff" : "sv", n_docs,
+            n_docs - m.lean_defer, m.lean_defer);
   if (m.lean_defer) {   // the exact per-document kernel over the deferred list, packed after the slots
     HIPCHK(hipEventRecord(c->e0, s));
     if (gather) {

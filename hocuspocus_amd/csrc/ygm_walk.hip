@@ -710,7 +710,7 @@ __device__ __forceinline__ void dw_walk(const uint8_t* __restrict__ arena, const
               cs = p;
             }
             bad |= cs >= 60u ? 1u : 0u;
-            const uint32_t csx = cs < 56u ? cs : 56u;
+            const uint32_t csx = cs < 59u ? cs : 59u;   // (the length is read where the content starts: cs <= 59 here, else bad)
             const uint32_t ce = dw_ctz(dw_from(win, csx));
             const uint32_t v = dw_val(dw_bytes_at(L, l, q, lo, hi, csx), ce - csx + 1u, bad);
             const uint32_t cend = ce + 1u;
