@@ -1,19 +1,31 @@
-// ygm_kernels.hip -- gfx950 kernels of the batched Yjs update engine.
+// ygm_kernels.hip -- gfx950 kernels of the batched Yjs update engine: every merge tier, the exact SV / diff kernel
+// and the host API's packer.  (The SV / diff ring walker, the snapshot, text, version and V2 kernels have files of
+// their own: ygm_walk.hip, ygm_snapshot.hip, ygm_text.hip, ygm_version.hip, ygm_v2.hip.)
 //
-//  k_doc         encodeStateVectorFromUpdate / diffUpdate, one lane per document (yjs Y@37728 / Y@40711):
+//  k_doc, k_doc_gather   encodeStateVectorFromUpdate / diffUpdate, one lane per document (yjs Y@37728 / Y@40711):
 //                the exact kernel for what the ring walker (ygm_walk.hip) defers
-//  k_merge_fast  mergeUpdates, one workgroup per document, all state in LDS:
-//                stage -> parse (lane per update) -> bitonic sort of struct
-//                keys (client desc, clock asc) -> provenance scan (Skip gaps,
-//                GC coalescing, rule R-M of SURVEY.md App. B.5) -> delete-set
-//                segmented max-scan union (rule R-DS) -> emit
-//  k_merge_seq   mergeUpdates, exact sequential replay (one lane per document)
-//                for documents the fast path cannot prove overlap-free
+//  k_merge_fast  mergeUpdates, one workgroup per document, all state in LDS: stage -> parse (lane per update) ->
+//                bitonic sort of struct keys (client desc, clock asc) -> provenance scan (Skip gaps, GC coalescing,
+//                rule R-M of SURVEY.md App. B.5) -> delete-set segmented max-scan union (rule R-DS) -> emit
+//  k_merge_wave  mergeUpdates, one wave per document (ygm_merge_wave.hpp): what the lean kernels defer
+//  k_route_big   the wave kernel's routing decision taken before it, a lane per document: large snapshots go to
+//                the large-document tier's list
+//  k_merge_lean  mergeUpdates for debounce logs, a persistent wave per document (ygm_merge_lean.hpp): the narrow
+//                kernel over every document, the wide one over what it defers; k_build_off: the update-offset
+//                table of the compact input form
+//  k_big_pick, k_big_scan, k_big_val, k_merge_big (4- and 16-wave workgroups), k_big_wait
+//                mergeUpdates for large [snapshot, ...log] documents (ygm_merge_big.hpp)
+//  k_merge_seq   mergeUpdates, exact sequential replay (one lane per document) for documents the fast paths cannot
+//                prove overlap-free
+//  k_pack_*      the host API's packed results: per-document output slots copied into one buffer in document order
 //
-// Output placement: every kernel writes a packed arena in document order using
-// decoupled look-back over tiles taken in ticket order (ygm_common.hpp), so a
-// batch is ONE pass over the input; the sequential kernel appends after the
-// fast region through an atomic cursor (offsets are reported per document).
+// One translation unit on purpose: k_merge_big and k_big_val share the non-inlined codec helpers of ygm_v1.hpp with
+// k_merge_fast and k_merge_wave, and the lean kernels share inlined helpers with k_merge_big; compiled apart, each
+// of them comes out with other registers or instructions (profiles/kernel_split/README.md).
+//
+// Output placement: the SV / diff kernels write a packed arena in document order using decoupled look-back over tiles
+// taken in ticket order (ygm_common.hpp), so a batch is ONE pass over the input; a merge kernel writes a document's
+// output into its own slot, or -- larger than the slot -- after the slots through an atomic cursor (merge_place).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -31,41 +43,7 @@
 #include "ygm_seqdoc.hpp"
 #include "ygm_v1.hpp"
 #include "ygm_launch.hpp"
-
-#ifdef YGM_DIAG
-// diagnostic build only (libygm_diag.so): per-phase shader-clock sums of k_merge_fast
-__device__ unsigned long long ygm_diag[32];
-#define DIAG_T0 unsigned long long _dt = __builtin_amdgcn_s_memtime();
-#define DIAG(i) do { if (threadIdx.x == 0) { unsigned long long _n = __builtin_amdgcn_s_memtime(); atomicAdd(&ygm_diag[i], _n - _dt); _dt = _n; } } while (0)
-#define DIAGW(i) do { if ((threadIdx.x & 63) == 0) { unsigned long long _n = __builtin_amdgcn_s_memtime(); atomicAdd(&ygm_diag[8 + (i)], _n - _dt); _dt = _n; } } while (0)
-// lean kernel: absolute shader-clock stamps per document (no atomics): ygm_diag_ts[(d % 16384) * 8 + slot]
-__device__ unsigned long long ygm_diag_ts[16384 * 8];
-// (s_memrealtime: the chip-wide 100 MHz clock, comparable across waves and XCDs)
-#define DIAGL_T0 if (threadIdx.x == 0) ygm_diag_ts[(blockIdx.x & 16383u) * 8] = __builtin_amdgcn_s_memrealtime();
-#define DIAGL(i) do { if (threadIdx.x == 0) ygm_diag_ts[(blockIdx.x & 16383u) * 8 + 1 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define DIAG_NOW() __builtin_amdgcn_s_memrealtime()
-#define DIAG_PUT(i, v) do { if (threadIdx.x == 0) ygm_diag_ts[(blockIdx.x & 16383u) * 8 + (i)] = (v); } while (0)
-#define DIAG_C(...) __VA_ARGS__
-// lean kernel, per wave: shader cycles spent at the vmcnt(0) a document's first staging write sits behind (the
-// prefetch chunks -- and, the counter being in order, the previous document's output stores), and in the whole
-// persistent loop: ygm_diag_sw[wave * 2 + {0, 1}]
-__device__ unsigned long long ygm_diag_sw[16384 * 2];
-#define DIAGSW_T0 unsigned long long _sw = 0; const unsigned long long _sl = __builtin_amdgcn_s_memtime();
-#define DIAGSW_WAIT do { const unsigned long long _a = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0x0F70); _sw += __builtin_amdgcn_s_memtime() - _a; } while (0)
-#define DIAGSW_END do { if (threadIdx.x == 0) { ygm_diag_sw[(blockIdx.x & 16383u) * 2] = _sw; ygm_diag_sw[(blockIdx.x & 16383u) * 2 + 1] = __builtin_amdgcn_s_memtime() - _sl; } } while (0)
-#else
-#define DIAGSW_T0
-#define DIAGSW_WAIT
-#define DIAGSW_END
-#define DIAGL_T0
-#define DIAGL(i)
-#define DIAG_NOW() 0ull
-#define DIAG_PUT(i, v)
-#define DIAG_C(...)
-#define DIAGW(i)
-#define DIAG_T0
-#define DIAG(i)
-#endif
+#include "ygm_diag.hpp"
 
 namespace ygm {
 
@@ -1142,10 +1120,6 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
     wave_sync();
     DIAGL(0);
-#if defined(YGM_LEAN_STOP) && YGM_LEAN_STOP == 1   // timing experiment: stage only
-    { hn = lean_hdr_of(du, lean_bo_load<LENS>(upd_off, doc_off, du, LN_AHEAD(1), n_docs)); du = lean_du_load(doc_upd, LN_AHEAD(2), n_docs);
-      gn = !force_seq && lean_stageable<WIDE>(hn); lean_prefetch<WIDE, LENS>(arena, upd_off, upd_len, hn, gn, v, rx); wave_sync(); dit++; d = LN_AHEAD(1); continue; }
-#endif
     // ---- header of the next document (its prefetch is issued after the parse) and doc_upd of the one after
     const uint64_t bo_next = lean_bo_load<LENS>(upd_off, doc_off, du, LN_AHEAD(1), n_docs);
     const uint32_t du_next = lean_du_load(doc_upd, LN_AHEAD(2), n_docs);
@@ -1187,7 +1161,7 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     bool allfast = false;   // (wave-uniform) every row was decided by the fast parse: the log-order placement's documents
 #pragma unroll
     for (int q = 0; q < LN_ROWS; q++) { hs[q] = false; hasd[q] = false; }
-    if (go && !WIDE && YGM_LN_FASTPARSE) {
+    if (go && !WIDE) {
       allfast = true;
       // phase-major: the windows, mask bits and tail bytes of YGM_LN_FASTGROUP rows are loaded (invalid lanes: the first
       // update, 0 bytes), then those rows' fast parses run, straight-line; a row with a valid lane that is not
@@ -1236,17 +1210,11 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
     DIAGL(1);
     // ---- prefetch the next document while this one is scanned and emitted (kept below the parse:
     //      hoisted above it, the parse waits on the prefetch's vmcnt)
-#ifdef YGM_LEAN_SB
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     hn = lean_hdr_of(du, bo_next); du = du_next;
     gn = !force_seq && lean_stageable<WIDE>(hn);
     lean_prefetch<WIDE, LENS>(arena, upd_off, upd_len, hn, gn, v, rx);
     defer = defer || __ballot(bad) != 0;
     if (single) { wave_sync(); dit++; d = LN_AHEAD(1); continue; }   // (dit: bit j of dmask is the run's j-th document)
-#if defined(YGM_LEAN_STOP) && YGM_LEAN_STOP == 2   // timing experiment: stage + parse
-    if (l == 0) status[d] = (int)bad; wave_sync(); dit++; d = LN_AHEAD(1); continue;
-#endif
     if (!defer) {
       // ---- clients: a record's block is its client's rank, descending; lane c of `ctl` holds block c's client.
       //      All-fast documents of the narrow kernel: by first sight (below); every other document: discovered in
@@ -1496,9 +1464,6 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         }
         DIAGL(2);
         defer = __ballot(bad) != 0;
-#if defined(YGM_LEAN_STOP) && YGM_LEAN_STOP == 3   // timing experiment: stage + parse + scan
-        if (l == 0) status[d] = (int)bad + (int)((oex[0] ^ osp[0]) & 1) + (int)((oex[1] ^ osp[1]) & 1) + (int)((oex[2] ^ osp[2]) & 1) + (int)((oex[3] ^ osp[3]) & 1) + (int)((hpos ^ hcnt ^ hfc) & 1); wave_sync(); dit++; d = LN_AHEAD(1); continue;
-#endif
         if (!defer) {
           const uint32_t at = vu_len(nC) + hdr_all;   // + the struct bytes: the delete set's position
           size = at + (carry & 0xFFFFu) + dsu.bytes;   // headers + struct bytes + the delete set
@@ -1560,27 +1525,9 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
 }
 
 // ======================================================================= merge: large documents
-// One wave per document the workgroup tier sent on (ygm_merge_big.hpp); documents outside its class
-// go on to the sequential kernel through fb2_list.
-template <class T>
-YDEV void big_bitonic(T* a, uint32_t n) {   // ascending by key; n <= 1024 (entries [n, pow2) padded)
-  uint32_t P = 1;
-  while (P < n) P <<= 1;
-  const uint32_t l = threadIdx.x % WAVE;   // (one wave sorts: the lane, whichever wave of the workgroup it is)
-  for (uint32_t i = n + l; i < P; i += WAVE) a[i].key = ~0ull;
-  wave_sync();
-  for (uint32_t k = 2; k <= P; k <<= 1)
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t i = l; i < P; i += WAVE) {
-        const uint32_t x = i ^ j;
-        if (x > i) {
-          const T A = a[i], B = a[x];
-          if ((A.key > B.key) == ((i & k) == 0)) { a[i] = B; a[x] = A; }
-        }
-      }
-      wave_sync();
-    }
-}
+// A 4- or 16-wave workgroup per document the routing pass or the workgroup tier sent on, after a scan of every
+// snapshot over the whole GPU (ygm_merge_big.hpp); documents outside its class go on to the sequential kernel
+// through fb2_list.
 // a workgroup sort of n <= NT * k entries by key: every entry's rank (the keys before it, ties by index: a stable
 // order) from a broadcast scan of the keys, then a scatter through tmp (LDS) and the copy back
 template <class T, uint32_t NT>
@@ -1595,12 +1542,6 @@ YDEV void big_rank_sort(T* a, uint32_t n, T* tmp, uint32_t t0) {
   __syncthreads();
   for (uint32_t i = t0; i < n; i += NT) a[i] = tmp[i];
   __syncthreads();
-}
-YDEV void big_copy(uint8_t* dst, const uint8_t* src, uint64_t n) {   // the wave copies n bytes, 16 per lane-step
-  for (uint64_t c = 16ull * (threadIdx.x % WAVE); c < n; c += 16ull * WAVE) {
-    if (c + 16 <= n) { uint4 v; __builtin_memcpy(&v, src + c, 16); __builtin_memcpy(dst + c, &v, 16); }
-    else for (uint64_t q = c; q < n; q++) dst[q] = src[q];
-  }
 }
 // A list of byte copies (LDS) run by the wave at once: every lane takes 16-byte chunks of the whole list (the entry
 // by binary search over the chunk prefix), four chunks in flight per lane, so the loads of many short copies overlap
@@ -1924,18 +1865,6 @@ __global__ __launch_bounds__(1024) void k_big_pick(const uint8_t* __restrict__ a
   if (ok)
     for (uint32_t t = l; t < nt; t += WAVE) S.task[tb + t] = make_uint2(w, t);
 }
-#ifndef YGM_SCAN_LDS
-#define YGM_SCAN_LDS 1
-#endif
-#ifndef YGM_SCAN_UTF
-#define YGM_SCAN_UTF 1   // a candidate string's verdict: 0 the UTF-8 decoder over the stage; 1 ASCII views first (see the scan)
-#endif
-#ifndef YGM_SCAN_PF
-#define YGM_SCAN_PF 1    // parent-form candidates whose parentInfo byte is past 1 are not parsed (see the scan's queue)
-#endif
-#ifndef YGM_SCAN_CLS
-#define YGM_SCAN_CLS 2   // candidate classes queued one after the other (1: position order)
-#endif
 __global__ __launch_bounds__(256) void k_big_scan(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ upd_off,
                                                   const uint32_t* __restrict__ doc_upd, const uint32_t* __restrict__ fb_list,
                                                   uint32_t flags, BigScan S) {
@@ -1968,20 +1897,17 @@ __global__ __launch_bounds__(256) void k_big_scan(const uint8_t* __restrict__ ar
     // queued by class -- GC and Items with an origin and deleted / string content (text's structs: the verdict from the
     // skip parse) first, then the rest -- so that a wave's lanes parse the same kind of struct more often (the parse
     // branches by kind)
-    constexpr uint32_t NCLS = YGM_SCAN_CLS < 1 ? 1u : (uint32_t)YGM_SCAN_CLS;
-    for (uint32_t cls = 0; cls < NCLS; cls++)
+    for (uint32_t cls = 0; cls < 2u; cls++)
       for (uint32_t b = 0; b < w1 - w0; b += WAVE) {
         const uint32_t i = b + l;
         const uint32_t ib = i < w1 - w0 ? lb[i] : 1u;
         const bool txt = ib == 0u || ((ib & 0xC0u) && ((ib & 31u) == 1u || (ib & 31u) == 4u));
-        const uint32_t k = NCLS == 1u ? 0u : txt ? 0u : (NCLS < 3u || (ib & 0xC0u)) ? 1u : 2u;   // (3: the rest split by origin)
+        const uint32_t k = txt ? 0u : 1u;
         bool cand = i < w1 - w0 && big_cand(ib) && k == cls;   // (other positions are never read: nothing written)
-#if YGM_SCAN_PF
         // a parent-form Item (no origins) whose parentInfo byte is not 0 / 1 is refused by the validation wherever it
         // stands, so it needs no end: its word is 0 (no parse -- the follow parses such a position from global memory
         // should the chain meet it) and the queue keeps the candidates that can be structs write_struct emits
         if (cand && ib != 0u && (ib & 0xC0u) == 0u && i + 1u < se - w0 && lb[i + 1u] > 1u) { cand = false; S.nv[P.pb + w0 + i] = 0u; }
-#endif
         const uint64_t m = __ballot(cand);
         if (cand) q[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)i;
         qn += (uint32_t)__builtin_popcountll(m);
@@ -1993,21 +1919,10 @@ __global__ __launch_bounds__(256) void k_big_scan(const uint8_t* __restrict__ ar
       uint32_t e = 0, v = 0;
       bool slow = false;
       if (j < qn) {
-#if YGM_SCAN_LDS
         LCur c; c.init((LU8*)lb, se - w0); c.pos = i;   // (LDS-typed reads of the stage)
-#else
-        GCur c; c.init(lb, se - w0); c.pos = i;
-#endif
         uint32_t kind;
         uint64_t cv = 0;
-#if YGM_SCAN_SKIP1   // experiment: candidates of the other kinds not parsed (no end: the follow parses them from global memory)
-        const uint32_t ib0 = lb[i];
-        const bool txt0 = ib0 == 0u || ((ib0 & 0xC0u) && ((ib0 & 31u) == 1u || (ib0 & 31u) == 4u));
-        bool ok = txt0 && big_skip(c, kind, 8, &cv) && !c.err;
-        if (!txt0) c.err = ST_FALLBACK;
-#else
         bool ok = big_skip(c, kind, 8, &cv) && !c.err;
-#endif
         const uint8_t* vb = lb;   // (the string's bytes: the stage, or U0 after a redo)
         uint32_t cp = c.pos + w0;
         if (!ok && c.err == ST_MALFORMED && se < n0) {   // ran into the stage's end: the parse again from global memory
@@ -2024,22 +1939,18 @@ __global__ __launch_bounds__(256) void k_big_scan(const uint8_t* __restrict__ ar
               // from the skip parse itself (its varuints minimal, the string strict UTF-8, a non-zero length)
               int64_t len = c.nm ? -1 : (int64_t)cv;
               if (!c.nm && ref == 4u) {
-#if YGM_SCAN_UTF == 0 || !YGM_SCAN_LDS
-                len = gutf8_u16(vb + (cv >> 32), (uint32_t)cv);
-#else
                 // the string's bytes from the stage by 8-byte views: all ASCII (the common case, and a cheap no for most
-                // of the speculative parses) counts its bytes; otherwise the UTF-8 decoder (1) or no verdict (2: the
-                // merge kernel validates it if the chain meets it; 3: experiment, no verdict for any string)
+                // of the speculative parses) counts its bytes; otherwise the UTF-8 decoder
                 const uint32_t s0 = (uint32_t)(cv >> 32), sl = (uint32_t)cv;
-                bool asc = vb == lb && YGM_SCAN_UTF != 3;
+                bool asc = vb == lb;
                 for (uint32_t k = 0; asc && k < sl; k += 8u) {
                   const uint64_t w = c.w8(s0 + k), m = sl - k >= 8u ? ~0ull : (1ull << (8u * (sl - k))) - 1ull;
                   asc = (w & m & 0x8080808080808080ull) == 0ull;
                 }
-                len = asc ? (int64_t)sl : YGM_SCAN_UTF == 1 ? gutf8_u16(vb + s0, sl) : -2;
-#endif
+                len = asc ? (int64_t)sl : gutf8_u16(vb + s0, sl);
               }
-              v = len == -2 ? 0u : big_v16((uint64_t)len, len > 0 && len < 0xFFFFFFFFll);
+              v = len == -2 ? 0u : big_v16((uint64_t)len, len > 0 && len < 0xFFFFFFFFll);   // (-2: never, a retired verdict;
+                                                                                             //  the test is kept: dropping it changes the code)
             } else {
               // the other kinds: big_struct in k_big_val (its registers would halve this kernel's waves), for a parse
               // whose end could start the next struct (most candidates are bytes inside other structs: their ends
@@ -2069,19 +1980,12 @@ __global__ __launch_bounds__(256) void k_big_scan(const uint8_t* __restrict__ ar
 // Each lane stages its candidate's bytes -- the aligned 16-byte chunks of [pos, pos + BIG_VCAP] (the queued structs
 // parse in at most BIG_VCAP bytes), loads issued together -- into its LDS slot and validates from there: one load
 // latency per candidate instead of a chain of dependent window loads through a global-memory cursor.
-#ifndef YGM_VAL_LDS
-#define YGM_VAL_LDS 1
-#endif
-#ifndef YGM_VAL_SORT
-#define YGM_VAL_SORT 1
-#endif
 __global__ __launch_bounds__(256) void k_big_val(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ upd_off,
                                                  const uint32_t* __restrict__ doc_upd, const uint32_t* __restrict__ fb_list,
                                                  uint32_t flags, BigScan S) {
   constexpr uint32_t VW = (BIG_VCAP + 16u + 15u) / 16u;   // 16-byte chunks staged per candidate
-  __shared__ uint4 s_w[YGM_VAL_LDS ? 256 : 1][VW];
+  __shared__ uint4 s_w[256][VW];
   const uint64_t nq = *(volatile unsigned long long*)&S.cnt[4], n = nq < S.vq_cap ? nq : S.vq_cap;
-#if YGM_VAL_SORT
   // the workgroup's 256 entries are regrouped by their struct's content ref (a counting sort in LDS) before each lane
   // takes one: big_struct branches by content kind, and a wave of mixed kinds runs every branch its lanes take
   __shared__ uint2 s_q[256];
@@ -2107,48 +2011,28 @@ __global__ __launch_bounds__(256) void k_big_val(const uint8_t* __restrict__ are
     const uint32_t src_t = s_ix[t];
     const uint64_t i = b0 + src_t;
     if (i < n) {
-    const uint2 Q = s_q[src_t];
-#else
-  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull) {
-    const uint2 Q = S.vq[i];
-#endif
-    const BigPick P = S.pick[Q.x];
-    const uint8_t* u0p = arena + upd_off[doc_upd[fb_list[Q.x]] + P.u0];
-    const uint32_t wd = S.nv[P.pb + Q.y], end = Q.y + (wd & 0x7FFFu);
-#if YGM_VAL_LDS
-    const uint8_t* src = u0p + Q.y;
-    const uint32_t sh = (uint32_t)((uintptr_t)src & 15u);
-    const uint4* g16 = (const uint4*)(src - sh);
-    const uint32_t lim = P.n0 - Q.y < VW * 16u - sh ? P.n0 - Q.y : VW * 16u - sh;   // bytes of U0 in the slot
-    uint4* slot = s_w[threadIdx.x];
+      const uint2 Q = s_q[src_t];
+      const BigPick P = S.pick[Q.x];
+      const uint8_t* u0p = arena + upd_off[doc_upd[fb_list[Q.x]] + P.u0];
+      const uint32_t wd = S.nv[P.pb + Q.y];
+      const uint8_t* src = u0p + Q.y;
+      const uint32_t sh = (uint32_t)((uintptr_t)src & 15u);
+      const uint4* g16 = (const uint4*)(src - sh);
+      const uint32_t lim = P.n0 - Q.y < VW * 16u - sh ? P.n0 - Q.y : VW * 16u - sh;   // bytes of U0 in the slot
+      uint4* slot = s_w[threadIdx.x];
 #pragma unroll
-    for (uint32_t k = 0; k < VW; k++) {   // (a chunk holding a byte of U0 is inside the arena: its tail padding)
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (16u * k < sh + lim) v = g16[k];
-      slot[k] = v;
-    }
-    LCur w; w.init((LU8*)slot + sh, lim);
-    const GStruct g = big_struct(w, flags);
-    const bool at_end = w.pos == (wd & 0x7FFFu);
-#else
-    (void)s_w;
-    GCur w; w.init(u0p, P.n0); w.pos = Q.y;
-    const GStruct g = big_struct(w, flags);
-    const bool at_end = w.pos == end;
-#endif
-    (void)end;
-    S.nv[P.pb + Q.y] = (wd & 0xFFFFu) | (big_v16(g.len, g.ok && !g.patch && at_end && g.len != 0 && g.len < 0xFFFFFFFFull) << 16);
-#if YGM_VAL_SORT
+      for (uint32_t k = 0; k < VW; k++) {   // (a chunk holding a byte of U0 is inside the arena: its tail padding)
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (16u * k < sh + lim) v = g16[k];
+        slot[k] = v;
+      }
+      LCur w; w.init((LU8*)slot + sh, lim);
+      const GStruct g = big_struct(w, flags);
+      const bool at_end = w.pos == (wd & 0x7FFFu);
+      S.nv[P.pb + Q.y] = (wd & 0xFFFFu) | (big_v16(g.len, g.ok && !g.patch && at_end && g.len != 0 && g.len < 0xFFFFFFFFull) << 16);
     }
     __syncthreads();   // (s_q / s_ix are rewritten by the next round)
-#endif
   }
-}
-// the struct start 2^(k+1) structs after tile position i < BT_CH (k = -1: the next one, from nx), or BJ_NONE
-template <class TL>
-YDEV uint32_t big_jump(const TL& T, int k, uint32_t i) {
-  if (k < 0) { const uint32_t e = T.nx[i]; return e ? (e & 0x7FFFu) : BJ_NONE; }
-  return T.jp[k][i];
 }
 // A client block header (struct count, client, clock: three varuints of <= 5 bytes ending inside the tile)
 // from one 16-byte view of the tile: terminators by the top bits, values by 7-bit compaction, nm = a
@@ -2178,9 +2062,6 @@ YDEV bool big_hdr_fast(const TL& T, uint32_t hp, uint32_t tn, uint64_t& nst, uin
   hend = hp + e2 + 1u;
   return true;
 }
-#ifndef YGM_BIG_BH
-#define YGM_BIG_BH 1
-#endif
 template <class CF>
 YDEV void big_spec(typename CF::Tile& T, const uint8_t* u0p, const uint32_t* nxg, uint32_t at, uint32_t mis, uint32_t n0, uint32_t t0,
                    uint16_t* bh, uint8_t* mk, uint16_t* lst, bool use_bh) {
@@ -2262,7 +2143,7 @@ YDEV void big_spec(typename CF::Tile& T, const uint8_t* u0p, const uint32_t* nxg
     }
     if (k == 0) dgs(0);
   }
-  if (!YGM_BIG_BH || !use_bh) { dgs(1); return; }   // (documents of large blocks: the table would not be used, C3)
+  if (!use_bh) { dgs(1); return; }   // (documents of large blocks: the table would not be used, C3)
   // the block table: bh[i] = the tile position right after the whole client block whose header would start at tile
   // position i (the header decoded from the tile, then its nst structs jumped through the tables along the bits of
   // nst), or BJ_NONE (no header parse, nst 0 or >= 64, a struct without a table entry or starting past the tile's CH
@@ -2837,17 +2718,10 @@ __global__ __launch_bounds__(CF::THREADS, CF::MID ? YGM_MID_OCC : 1) void k_merg
   constexpr uint32_t SBQ = CF::MID ? 24u : 64u;   // block records staged in LDS before a store (mid: room for s_bh)
   __shared__ BigBlk s_blk[SBQ];
   __shared__ uint32_t s_cpre[WAVE];
-  __shared__ uint16_t s_bh[YGM_BIG_BH ? CF::CH : 1];   // the tile's block table (big_spec)
-  __shared__ uint8_t s_mk[YGM_BIG_BH ? CF::CH : 1];    // ... computed at these positions only
+  __shared__ uint16_t s_bh[CF::CH];   // the tile's block table (big_spec)
+  __shared__ uint8_t s_mk[CF::CH];    // ... computed at these positions only
   __shared__ uint16_t s_hl[WAVE + 2];                  // a run of blocks found from it: their tile positions
-#ifndef YGM_BIG_ROT
-#define YGM_BIG_ROT 0
-#endif
-  // the logical thread index: the chain-follow wave (logical wave 0) is physical wave blockIdx.x % WAVES, so the
-  // followers of the mid size's workgroups sharing a CU do not all land on one SIMD (they are latency chains: four on
-  // one SIMD share its issue while the helpers' SIMDs idle)
-  const uint32_t tid = YGM_BIG_ROT && CF::MID ? (threadIdx.x + CF::THREADS - WAVE * (blockIdx.x % CF::WAVES)) % CF::THREADS
-                                              : threadIdx.x;
+  const uint32_t tid = threadIdx.x;   // (wave 0 follows the chain, in every workgroup)
   if (!CF::MID && threadIdx.x == 0) atomicAdd(&meta->big_started, 1u);   // (k_big_wait holds the mid size back until then)
   if (tid >= WAVE) {   // helper waves: wave 0's tile commands until it sends 0 (one barrier pair per command)
     for (;;) {
@@ -3021,7 +2895,7 @@ __global__ __launch_bounds__(CF::THREADS, CF::MID ? YGM_MID_OCC : 1) void k_merg
     GCur c; c.init(u0p, n0);
     bool bad = false;
     nb = c.vu();
-    use_bh = YGM_BIG_BH && nb * 256ull > (uint64_t)n0;   // (average block under 256 bytes)
+    use_bh = nb * 256ull > (uint64_t)n0;   // (average block under 256 bytes)
     if (l == 0) { s_base = atomicAdd(&meta->big_cursor, (unsigned long long)nb); s_sbase = atomicAdd(&meta->big_scur, (unsigned long long)ncap); }
     wave_sync();
     base = s_base; sbase = s_sbase;
@@ -3043,7 +2917,7 @@ __global__ __launch_bounds__(CF::THREADS, CF::MID ? YGM_MID_OCC : 1) void k_merg
       DIAG_C(const uint64_t dq0 = DIAG_NOW();)
       if (!have || pos >= tc0 + CF::CH) { if (have) validate(); load_tile(pos, true); have = true; }
       DIAG_C(const uint64_t dq1 = DIAG_NOW(); dt_tile += dq1 - dq0;)
-      if (YGM_BIG_BH && use_bh) {
+      if (use_bh) {
         // ---- a run of whole blocks from the tile's block table (big_spec): lane 0 chains their header positions, one
         //      LDS lookup per block; the lanes then decode the headers and record the structs, a block each
         const uint32_t cap = SBQ - bq < (uint32_t)WAVE ? SBQ - bq : (uint32_t)WAVE;
@@ -3557,7 +3431,7 @@ extern "C" {
 using namespace ygm;
 
 #ifdef YGM_DIAG
-int ygm_diag_ts_read(unsigned long long* out, int reset) {  // 16384 x 8 stamps of the lean kernel
+int ygm_diag_ts_read(unsigned long long* out, int reset) {  // 16384 x 8 stamps of the lean kernel (and of k_merge_big)
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ygm_diag_ts), sizeof(unsigned long long) * 16384 * 8) != hipSuccess) return -1;
   (void)reset;
   return 0;
@@ -3572,7 +3446,7 @@ int ygm_diag_ds_read(unsigned long long* out, int reset) {   // 4 delete-set uni
   if (reset) { unsigned long long z[4] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(ygm_diag_ds), z, sizeof z); }
   return 0;
 }
-int ygm_diag_read(unsigned long long* out, int reset) {
+int ygm_diag_read(unsigned long long* out, int reset) {   // 32 sums: k_merge_fast's, k_merge_wave's, k_merge_big's (ygm_diag.hpp)
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ygm_diag), sizeof(unsigned long long) * 32) != hipSuccess) return -1;
   if (reset) { unsigned long long z[32] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(ygm_diag), z, sizeof z); }
   return 0;
@@ -3787,6 +3661,7 @@ static uint32_t resident_blocks(K kernel, int threads, uint32_t fallback) {
     return fallback;
   return (uint32_t)(cus * per);
 }
+
 
 uint32_t ygm_k_lean_stage_bytes() { return (uint32_t)LN_IN; }   // input bytes the narrow lean kernel stages per document
 // doc_off / upd_len non-null: the compact input form (ygm_merge_v1_device_lens); upd_off is then unused

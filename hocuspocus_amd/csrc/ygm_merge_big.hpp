@@ -1,5 +1,7 @@
 // ygm_merge_big.hpp -- mergeUpdates for LARGE [snapshot, ...log] documents:
-// ONE WAVE PER DOCUMENT, global memory, no per-struct records for the snapshot.
+// a workgroup per document -- 4 waves (the mid size, four workgroups per CU) or 16 waves (a whole CU) -- after a
+// speculative scan of every snapshot over the whole GPU; global memory, no per-struct copies of the snapshot.  The
+// kernels and launchers are in ygm_kernels.hip; this file holds the cursors, parsers and records they use.
 //
 // Shape it takes (what Hocuspocus stores: the engine's previous output plus the onChange updates
 // since, row a4): the largest update U0 (the snapshot) has its client blocks in strictly
@@ -13,13 +15,21 @@
 // GC-GC junctions between sources, re-encoded structs, ContentDoc in U0, 13.5
 // multi-client delete sets, malformed input) is deferred to the exact sequential kernel.
 //
-//   walk   lane 0 walks U0 with a 16-byte register-window cursor (GCur): every struct is validated
-//          as read_struct does (UTF-8 by 16-byte chunks with an ASCII fast path) and must be
-//          byte-for-byte what write_struct would emit; one table entry per block in global scratch
-//   log    lanes walk the log updates in parallel (Cur over global memory; they are small) into
-//          LDS records; bitonic sorts by (client descending, clock)
-//   emit   lane 0 merges the block table with the sorted log pieces twice (sizes, then bytes);
-//          the wave copies each U0 block range with 16-byte loads / stores
+//   scan   before k_merge_big (k_big_pick, k_big_scan, k_big_val): every byte of every U0 that could be an info byte
+//          is parsed as a struct start from an LDS stage, a lane per candidate; a word per position keeps the
+//          struct's end and, for structs of at most BIG_VCAP bytes, the verdict "byte for byte what write_struct
+//          would emit" with its clock length
+//   walk   wave 0 follows U0's struct chain a tile (1 KB mid / 4 KB) at a time through the scan's words; the helper
+//          waves serve its commands (BigCmd, a barrier pair each): 1 the tile's jump tables by doubling and, for
+//          documents of small blocks, its block table (big_spec), 2 the verdicts of the structs the scan left open
+//          (big_validate, from global memory), 3 the blocks' clock ranges, 4 U0's delete set checked canonical for
+//          the splice, 6 the log's rank sorts; while wave 0 follows a tile they prefetch the next.  One table entry
+//          per client block in global scratch
+//   log    lanes walk the log updates in parallel, staged in the tile's LDS when they fit, into LDS records sorted
+//          by (client descending, clock); a log past the mid size's LDS sends the document to the 16-wave size
+//   emit   wave 0 merges the block table with the sorted log pieces twice (sizes, then a copy list); the whole
+//          workgroup copies the list's ranges of U0 with 16-byte loads / stores (command 5), clearing the info-byte
+//          bits the validation marked; U0's delete set is spliced with the log's ranges, or streamed
 #pragma once
 #include <type_traits>
 #include "ygm_seqdoc.hpp"
@@ -307,9 +317,6 @@ YDEV_NI bool gany_skip(GCur& c, uint64_t n) {
 // the stage and its terminator mask, instead of a dependent read per varuint: the cursor ends where the vu() calls
 // would leave it, with nm set the same way (a varuint's last byte zero past its first).  Returns false (cursor
 // untouched) when the ids do not end inside the view and the update or a varuint runs past 7 bytes: the vu() path.
-#ifndef YGM_SKIP_MASK
-#define YGM_SKIP_MASK 1
-#endif
 YDEV uint32_t top_bits8(uint64_t h) { return (uint32_t)((((h >> 7) & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56); }
 YDEV uint64_t zero_bytes8(uint64_t x) {   // 0x80 in each zero byte of x, exactly (no borrow between bytes)
   const uint64_t t = (x & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full;
@@ -346,9 +353,7 @@ YDEV bool big_skip(CUR& c, uint32_t& kind, uint64_t jcap = ~0ull, uint64_t* cv =
   if ((info & 31u) == 0u) { kind = 0; const uint64_t n = c.vu(); if (cv) *cv = n; return !c.err; }
   uint32_t l;
   bool skipped = false;
-#if YGM_SKIP_MASK
   if constexpr (std::is_same<CUR, LCur>::value) skipped = (info & 0xC0u) == 0u || lcur_skip_ids(c, ((info >> 7) & 1u) + ((info >> 6) & 1u));
-#endif
   if (!skipped) {
     if (info & 0x80u) { c.vu(); c.vu(); }
     if (info & 0x40u) { c.vu(); c.vu(); }

@@ -87,13 +87,10 @@ template <int WIDE> struct LnCfg {
 #ifndef YGM_LN_INSLACK
 #define YGM_LN_INSLACK 96
 #endif
-#ifndef YGM_LN_PAD
-#define YGM_LN_PAD 0   // experiment only: LDS bytes added per wave (occupancy A/B, profiles/r06_lean)
-#endif
 template <int WIDE>
 struct alignas(16) LeanLdsT {
   uint8_t in[LnCfg<WIDE>::IN + (WIDE ? 96 : YGM_LN_INSLACK)];   // + slack: window / copy reads reach up to 76 bytes past an update's start
-  uint8_t out[LnCfg<WIDE>::OUT + 80 + (WIDE ? 0 : YGM_LN_PAD)];   // + slack: lds_or_copy ORs zero into up to 68 bytes past a range
+  uint8_t out[LnCfg<WIDE>::OUT + 80];   // + slack: lds_or_copy ORs zero into up to 68 bytes past a range
   // (narrow kernel: from the staging to the end of the parse its first 2 LN_MASKB bytes hold the staged bytes' two mask arrays)
 };
 static_assert(LN_IN % 16 == 0 && YGM_LN_INSLACK >= 80 && YGM_LN_INSLACK % 16 == 0, "staging granules and slack");
@@ -342,14 +339,8 @@ YDEV LRec lean_parse(LB8* in, uint32_t s, uint32_t n) {
 // Such an update's string length, character and delete-set count are its last three bytes, so their
 // address is known from (s, n) alone: the loads of every row are issued before the first is used.  A
 // lane that is not fast proves nothing: its row runs lean_parse.  A fast lane's record is lean_parse's.
-#ifndef YGM_LN_FASTPARSE
-#define YGM_LN_FASTPARSE 1    // 0 (experiment): row-major lean_parse only, as before the fast parse
-#endif
 #ifndef YGM_LN_FASTGROUP
 #define YGM_LN_FASTGROUP 4    // rows whose loads are issued together (1, 2 or 4)
-#endif
-#ifndef YGM_LN_FASTPARENT
-#define YGM_LN_FASTPARENT 1   // 0 (experiment): the parent-ykey first insert is left to lean_parse
 #endif
 // The fast parse's two byte masks -- H: top bit set, Z: zero byte ("haszero": may also flag a 0x01 right above a zero byte) -- are
 // properties of the staged bytes, not of an update, so they are made once per staged 16-byte chunk, from the prefetch
@@ -386,9 +377,6 @@ YDEV void lean_fast_load(LB8* in, LB8* masks, uint32_t s, uint32_t n, LFastIn& F
   const uint32_t t = s + (n > 3u ? n : 3u);
   F.tl = in[t - 3u]; F.td = in[t - 1u];
 }
-#ifndef YGM_LN_KEYGATE
-#define YGM_LN_KEYGATE 1      // 0 (experiment): the parent-ykey shape is evaluated for every row
-#endif
 // true: R is the update's record (R.ok) and hasd whether its delete set is non-empty.
 // Called by the whole wave, one row at a time (valid: the lane's slot of this row holds an update).  The parent-ykey
 // shape is evaluated only for a row that has a valid lane with neither origin -- one ballot and one scalar branch
@@ -430,8 +418,7 @@ YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, 
   const uint32_t pl = nsk == 2u ? pp + lnctz(t3) + 1u : pp + lnctz(t1) + 1u;   // the string length's position
   bool fits = pl + 3u == n;
   bool shape = nsk != 0u && (info & 0x3Fu) == 4u;
-#if YGM_LN_FASTPARENT
-  if (KEYROW || !YGM_LN_KEYGATE || __ballot(valid && nsk == 0u) != 0) {
+  if (KEYROW || __ballot(valid && nsk == 0u) != 0) {
     // parent ykey: info 0x04, parentInfo 1, key length, ASCII key
     const uint32_t lk = (x3 >> 16) & 0xFFu;
     const uint32_t kp = ip + 3u < 31u ? ip + 3u : 31u;
@@ -439,7 +426,6 @@ YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, 
     fits = nsk == 0u ? ip + 6u + lk == n : fits;
     shape = shape || (nsk == 0u && par);
   }
-#endif
   // the length byte, one ASCII character and the delete set's count end the update
   const bool item = bad == 0u && shape && fits && n <= 32u && F.tl == 1u && ((HV >> ((n - 2u) & 31u)) & 1u) == 0u;
   const bool dsonly = b0 == 0u && n >= 2u && n <= 32u;
@@ -546,19 +532,16 @@ YDEV void lds_or_copy(LB8* out, LB8* in, uint32_t t, uint32_t s, uint32_t n) {
 // else 9, else (the wide kernel's runs of up to 63 bytes) 17 -- one decision per document (cw: the lane's
 // widest head + bytes), wave-uniform.  Narrow kernel: 5 when every run fits that (class 3; a debounce log's structs
 // are <= 17 bytes)
-#ifndef YGM_LN_COPY5
-#define YGM_LN_COPY5 1        // 0 (experiment): no 5-dword class
-#endif
 template <int WIDE>
 YDEV uint32_t lean_copy_class(uint32_t cw) {
-  if (!WIDE && YGM_LN_COPY5 && __ballot(cw > 20u) == 0) return 3u;
+  if (!WIDE && __ballot(cw > 20u) == 0) return 3u;
   if (__ballot(cw > 24u) == 0) return 0u;
   return (!WIDE || __ballot(cw > 36u) == 0) ? 1u : 2u;
 }
 template <int WIDE>
 YDEV void lean_copy(LB8* out, LB8* in, uint32_t cls, bool go, uint32_t t, uint32_t s, uint32_t n) {
   if (!go) return;
-  if (!WIDE && YGM_LN_COPY5 && cls == 3u) lds_or_copy<5>(out, in, t, s, n);
+  if (!WIDE && cls == 3u) lds_or_copy<5>(out, in, t, s, n);
   else if (cls == 0u) lds_or_copy<6>(out, in, t, s, n);
   else if (!WIDE || cls == 1u) lds_or_copy<9>(out, in, t, s, n);
   else lds_or_copy<17>(out, in, t, s, n);

@@ -11,7 +11,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hocuspocus_amd", "csrc")
-SRC = ("ygm_kernels.hip", "ygm_walk.hip", "ygm_snapshot.hip", "ygm_text.hip", "ygm_version.hip", "ygm_v2.hip")
+with open(os.path.join(CSRC, "Makefile")) as _mk:   # the HIP sources the Makefile builds (its SRC line)
+    SRC = tuple(s for s in re.search(r"^SRC\s*=(.*)$", _mk.read(), re.M).group(1).split() if s.endswith(".hip"))
 
 
 def remarks(src):
