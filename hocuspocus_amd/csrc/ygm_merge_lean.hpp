@@ -170,14 +170,22 @@ struct LRec {
   bool ok;
 };
 
+// the low 28 bits of a varuint's value: the 7-bit groups of the first min(n, 4) bytes of x, packed.  The length cut is
+// one bit-field extract (31 bits at n >= 4: bit 31 goes with the 0x7f mask), the packing two dot products of the masked
+// bytes with the weights 1 and 128 -- bytes 0, 1 and bytes 2, 3 -- joined by one shift-or: no shift ladder, no select.
+// (n < 2^29, or a small negative number wrapped: what an invalid lane brings.  tools/pext32_check.cpp holds the check
+// against the ladder, every x at every length)
+YDEV uint32_t pext28(uint32_t x, uint32_t n) {
+  const uint32_t m = __builtin_amdgcn_ubfe(x, 0u, min(8u * n, 31u)) & 0x7f7f7f7fu;
+  const uint32_t lo = __builtin_amdgcn_udot4(m, 0x00008001u, 0u, false), hi = __builtin_amdgcn_udot4(m, 0x80010000u, 0u, false);
+  return lo | (hi << 14);
+}
 // value of the <= 5-byte varuint whose first 4 bytes are x and 5th byte is y (n = length)
 YDEV uint32_t pext32(uint32_t x, uint32_t y, uint32_t n) {
-  x &= n >= 4u ? 0xFFFFFFFFu : ((1u << (8u * n)) - 1u);
-  x &= 0x7f7f7f7fu;
-  x = ((x >> 1) & 0x3f803f80u) | (x & 0x007f007fu);
-  x = ((x >> 2) & 0x0fffc000u) | (x & 0x00003fffu);
-  return x | (n >= 5u ? (y & 0x7Fu) << 28 : 0u);
+  return pext28(x, n) | (n >= 5u ? (y & 0x7Fu) << 28 : 0u);
 }
+// (n > 5) != 0 for a varuint length n = 1 .. 32 (what the terminator masks give: lnctz <= 31), without a compare
+YDEV uint32_t lean_vu_over5(uint32_t n) { return (n + 2u) >> 3; }
 
 // Parses the update at staged position s (n bytes).  ok == false: the document is deferred.
 // Failure conditions are OR-ed into one integer (no per-condition lane masks); bytes the
@@ -386,7 +394,10 @@ template <bool KEYROW>
 YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, LRec& R, bool& hasd) {
   const uint32_t (&d)[4] = F.d;
   const uint32_t H = F.H, Z = F.Z;
-  const uint32_t V = n >= 32u ? 0xFFFFFFFFu : ((1u << n) - 1u);
+  // the valid bytes' mask by one right shift (n = 1 .. 32: the kernel defers longer updates before the parse; the
+  // count is taken modulo 32, so n = 32 keeps every bit.  n = 0 -- a lane without an update -- keeps every bit too:
+  // no shape fits its length, whatever its bytes)
+  const uint32_t V = 0xFFFFFFFFu >> ((32u - n) & 31u);
   const uint32_t T = ~H & V, HV = H & V;
   // lean_parse's whole-window checks (a varuint of >= 8 bytes, a zero byte after a top-bit byte)
   const uint32_t h2 = HV & (HV >> 1), h4 = h2 & (h2 >> 2), h7 = h4 & (h4 >> 3);
@@ -397,16 +408,21 @@ YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, 
   // of the window ends at >= 31, which the length test below (the structs end at n - 1 <= 31) refuses
   uint32_t e = 2u + lnctz(T >> 2);
   const uint32_t cl_n = e - 1u;
-  const uint32_t client = pext32(__builtin_amdgcn_alignbyte(d[1], d[0], 2u), (d[1] >> 16) & 0xFFu, cl_n);
-  bad |= (cl_n > 5u ? 1u : 0u) | (cl_n == 5u ? ((d[1] >> 16) & 0x70u) : 0u);
+  // the fifth byte, taken once where the varuint has one: its low four bits are the value's top bits, a bit of 0x70
+  // is past a uint32; six bytes and more are refused by arithmetic on the length (1 .. 32 here; a clock length that
+  // wraps has p > 31: a client of thirty bytes, refused already)
+  const uint32_t cl_y = cl_n >= 5u ? (d[1] >> 16) & 0xFFu : 0u;
+  const uint32_t client = pext28(__builtin_amdgcn_alignbyte(d[1], d[0], 2u), cl_n) | (cl_y << 28);
+  bad |= lean_vu_over5(cl_n) | (cl_y & 0x70u);
   const uint32_t p = e + 1u;                   // 3..7 when the client is good
   const uint32_t pc = p < 31u ? p : 31u;
   e = pc + lnctz(T >> pc);
   const uint32_t ck_n = e - p + 1u;
   const uint64_t U01 = ((uint64_t)d[1] << 32) | d[0], U23 = ((uint64_t)d[3] << 32) | d[2];
   const uint64_t cw = (U01 >> (8u * (p & 7u))) | (p & 7u ? (U23 << (64u - 8u * (p & 7u))) : 0ull);   // bytes p..p+7
-  const uint32_t clock = pext32((uint32_t)cw, (uint32_t)(cw >> 32) & 0xFFu, ck_n);
-  bad |= (ck_n > 5u ? 1u : 0u) | (ck_n == 5u ? ((uint32_t)(cw >> 32) & 0x70u) : 0u);
+  const uint32_t ck_y = ck_n >= 5u ? (uint32_t)(cw >> 32) & 0xFFu : 0u;
+  const uint32_t clock = pext28((uint32_t)cw, ck_n) | (ck_y << 28);
+  bad |= lean_vu_over5(ck_n) | (ck_y & 0x70u);
   bad |= clock == 0xFFFFFFFFu ? 1u : 0u;       // clock + 1 stays a uint32
   const uint32_t ip = e + 1u;                  // the info byte: byte ck_n of cw (ck_n <= 5), the two bytes after it too
   const uint32_t x3 = (uint32_t)(cw >> (8u * (ck_n & 7u)));
@@ -430,8 +446,11 @@ YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, 
   const bool item = bad == 0u && shape && fits && n <= 32u && F.tl == 1u && ((HV >> ((n - 2u) & 31u)) & 1u) == 0u;
   const bool dsonly = b0 == 0u && n >= 2u && n <= 32u;
   R.ok = true;
-  R.client = item ? client : 0u; R.clock = item ? clock : 0u; R.clen = item ? 1u : 0u;
-  R.span = item ? ((s + ip) << 16) | (1u << 8) | ((n - 1u - ip) & 0xFFu) : 0u;
+  // one mask, made once, and four `and`: a select costs what the mask costs, an `and` half of it
+  uint32_t im = item ? 0xFFFFFFFFu : 0u;
+  asm("" : "+v"(im));   // (kept a mask: the compiler turns `x & im` back into a select)
+  R.client = client & im; R.clock = clock & im; R.clen = 1u & im;
+  R.span = (((s + ip) << 16) | (1u << 8) | ((n - 1u - ip) & 0xFFu)) & im;
   hasd = item ? F.td != 0u : b1 != 0u;
   return item || dsonly;
 }

@@ -22,9 +22,16 @@
 
 constexpr int CHAINS = 8, UNROLL = 16, ITERS = 1024;   // 131 072 instructions per wave
 
-enum Op { AND, ADD, CNDMASK, BITOP3, ALIGNBYTE, DOT4, LSHLREV, MOV_DPP, FMA, N_OPS };
+enum Op { AND, ADD, CNDMASK, BITOP3, ALIGNBYTE, DOT4, LSHLREV, MOV_DPP, FMA,
+          CMP_VCC, CMP_SGPR, BFE, LSHRREV, OR, OR3, LSHL_OR, AND_OR, MOV, READLANE, PERM, BFM, MED3, MIN, MUL24, MAD24,
+          LSHL_CONST, SUB, BFI, ALIGNBIT, N_OPS };
 static const char* const OP_NAME[N_OPS] = {"v_and_b32", "v_add_u32", "v_cndmask_b32", "v_bitop3_b32", "v_alignbyte_b32",
-                                           "v_dot4_u32_u8", "v_lshlrev_b32", "v_mov_b32 dpp row_shr:1", "v_fma_f32"};
+                                           "v_dot4_u32_u8", "v_lshlrev_b32", "v_mov_b32 dpp row_shr:1", "v_fma_f32",
+                                           "v_cmp_lt_u32 vcc", "v_cmp_lt_u32 sgpr pair", "v_bfe_u32", "v_lshrrev_b32", "v_or_b32",
+                                           "v_or3_b32", "v_lshl_or_b32", "v_and_or_b32", "v_mov_b32", "v_readlane_b32",
+                                           "v_perm_b32", "v_bfm_b32", "v_med3_u32", "v_min_u32", "v_mul_u32_u24",
+                                           "v_mad_u32_u24", "v_lshlrev_b32 (constant count)", "v_sub_u32", "v_bfi_b32",
+                                           "v_alignbit_b32"};
 
 // one round: the instruction once on each of the eight chains (a, b: loop-invariant operands; m: a lane mask)
 #define ROUND8(INS, TAIL)                                                                                       \
@@ -32,11 +39,22 @@ static const char* const OP_NAME[N_OPS] = {"v_and_b32", "v_add_u32", "v_cndmask_
                INS " %4, " TAIL(4) "\n\t" INS " %5, " TAIL(5) "\n\t" INS " %6, " TAIL(6) "\n\t" INS " %7, " TAIL(7)          \
                : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])  \
                : "v"(a), "v"(b), "s"(m))
+// the same for an instruction without a vector destination (a compare, a lane read): its result goes to vcc or s[20:21]
+#define ROUND8S(INS, TAIL)                                                                                      \
+  asm volatile(INS " " TAIL(0) "\n\t" INS " " TAIL(1) "\n\t" INS " " TAIL(2) "\n\t" INS " " TAIL(3) "\n\t"            \
+               INS " " TAIL(4) "\n\t" INS " " TAIL(5) "\n\t" INS " " TAIL(6) "\n\t" INS " " TAIL(7)                     \
+               : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])  \
+               : "v"(a), "v"(b), "s"(m) : "vcc", "s20", "s21")
 #define T_AB(i) "%8, %" #i                       // dst = a op dst
 #define T_CND(i) "%" #i ", %8, %10"              // dst = mask ? a : dst
 #define T_3(i) "%" #i ", %8, %9"                 // dst = f(dst, a, b)
 #define T_BITOP(i) "%" #i ", %8, %9 bitop3:0x96" // dst = dst ^ a ^ b
 #define T_DOT(i) "%8, %9, %" #i                  // dst = dot4(a, b) + dst
+#define T_MOV(i) "%8"                            // dst = a
+#define T_K3(i) "3, %" #i                        // dst = dst << 3
+#define T_VCC(i) "vcc, %8, %" #i                 // vcc = a < x
+#define T_SP(i) "s[20:21], %8, %" #i             // s[20:21] = a < x
+#define T_RL(i) "s20, %" #i ", 5"                // s20 = lane 5 of x
 #define T_DPP(i) "%" #i " row_shr:1 row_mask:0xf bank_mask:0xf"
 
 template <int OP>
@@ -62,6 +80,26 @@ __global__ __launch_bounds__(1024) void k_rate(uint64_t* __restrict__ stamps, ui
       if constexpr (OP == LSHLREV) ROUND8("v_lshlrev_b32", T_AB);
       if constexpr (OP == MOV_DPP) ROUND8("v_mov_b32_dpp", T_DPP);
       if constexpr (OP == FMA) ROUND8("v_fma_f32", T_3);
+      if constexpr (OP == CMP_VCC) ROUND8S("v_cmp_lt_u32_e32", T_VCC);
+      if constexpr (OP == CMP_SGPR) ROUND8S("v_cmp_lt_u32_e64", T_SP);
+      if constexpr (OP == BFE) ROUND8("v_bfe_u32", T_3);
+      if constexpr (OP == LSHRREV) ROUND8("v_lshrrev_b32", T_AB);
+      if constexpr (OP == OR) ROUND8("v_or_b32", T_AB);
+      if constexpr (OP == OR3) ROUND8("v_or3_b32", T_3);
+      if constexpr (OP == LSHL_OR) ROUND8("v_lshl_or_b32", T_3);
+      if constexpr (OP == AND_OR) ROUND8("v_and_or_b32", T_3);
+      if constexpr (OP == MOV) ROUND8("v_mov_b32", T_MOV);
+      if constexpr (OP == READLANE) ROUND8S("v_readlane_b32", T_RL);
+      if constexpr (OP == PERM) ROUND8("v_perm_b32", T_3);
+      if constexpr (OP == BFM) ROUND8("v_bfm_b32", T_AB);
+      if constexpr (OP == MED3) ROUND8("v_med3_u32", T_3);
+      if constexpr (OP == MIN) ROUND8("v_min_u32", T_AB);
+      if constexpr (OP == MUL24) ROUND8("v_mul_u32_u24", T_AB);
+      if constexpr (OP == MAD24) ROUND8("v_mad_u32_u24", T_3);
+      if constexpr (OP == LSHL_CONST) ROUND8("v_lshlrev_b32", T_K3);
+      if constexpr (OP == SUB) ROUND8("v_sub_u32", T_AB);
+      if constexpr (OP == BFI) ROUND8("v_bfi_b32", T_3);
+      if constexpr (OP == ALIGNBIT) ROUND8("v_alignbit_b32", T_3);
     }
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -78,8 +116,11 @@ __global__ __launch_bounds__(1024) void k_rate(uint64_t* __restrict__ stamps, ui
 
 typedef void (*Kern)(uint64_t*, uint32_t*);
 template <int OP> static Kern kern_of() { return k_rate<OP>; }
-static Kern KERN[N_OPS] = {kern_of<AND>(), kern_of<ADD>(), kern_of<CNDMASK>(), kern_of<BITOP3>(), kern_of<ALIGNBYTE>(),
-                           kern_of<DOT4>(), kern_of<LSHLREV>(), kern_of<MOV_DPP>(), kern_of<FMA>()};
+template <int... OPS> struct KernTable { Kern k[sizeof...(OPS)] = {kern_of<OPS>()...}; };
+template <int N, int... OPS> struct KernSeq : KernSeq<N - 1, N - 1, OPS...> {};
+template <int... OPS> struct KernSeq<0, OPS...> { typedef KernTable<OPS...> T; };
+static KernSeq<N_OPS>::T KERNS;
+static Kern* const KERN = KERNS.k;
 
 static double median(std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; }
 
