@@ -758,6 +758,61 @@ int ygm_text_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_byte
   out->status = c->status.as<int32_t>(); out->data_bytes = slot_total + total; out->payload_bytes = m.payload;
   return YGM_OK;
 }
+// ---- stored documents as ProseMirror JSON: the count / scan launches and k_json over the workspaces (no flat tier:
+// its envelope holds no nested types).  A JSON is not bounded by its workspace's output region: k_json lists the
+// documents whose JSON did not fit, with the lengths they need and their places in an overflow region claimed from
+// the launch's cursor; only then the buffer grows by that region (the workspaces, which hold the other documents'
+// outputs, are kept) and k_json runs again for the listed documents alone -- one more host wait.
+int ygm_json_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, const uint8_t* d_names,
+                       const uint64_t* d_name_off, uint32_t kind, uint32_t n_docs, void* stream, ygm_device_result* out) {
+  if (!c || !out || kind != YGM_JSON_PROSEMIRROR || (n_docs && (!d_state_off || !d_name_off))) return YGM_EINVAL;
+  (void)hipSetDevice(c->device);
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  const uint32_t fl = c->flags;
+  const uint32_t nb = (n_docs + 1 + 255) / 256;
+  if (!c->sn_cnt.ensure(16ull * n_docs + 16) || !c->sn_off.ensure(8ull * n_docs + 16) || !c->sn_bs.ensure(8ull * nb + 16) ||
+      !c->out_off.ensure(8ull * n_docs + 8) || !c->out_len.ensure(8ull * n_docs + 8) || !c->status.ensure(4ull * n_docs + 4) ||
+      !c->sn_pend.ensure(4ull * n_docs + 16))
+    return YGM_ENOMEM;
+  void* meta = c->meta_slot(2);
+  HIPCHK(hipMemsetAsync(meta, 0, sizeof(Meta), s));
+  HIPCHK(hipEventRecord(c->e0, s));
+  uint64_t total = 0, ovf = 0;
+  uint32_t reran = 0;
+  Meta m;
+  memset(&m, 0, sizeof(m));
+  if (n_docs) {
+    if (ygm_k_launch_snap_plan(d_states, d_state_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), nullptr, s))
+      return YGM_EDEVICE;
+    int e = 0;
+    total = read_u64(c, s, c->sn_off.as<uint64_t>() + n_docs, e);
+    if (e) return e;
+    if (!c->sn_ws.ensure(total + 64)) return YGM_ENOMEM;
+    auto launch = [&](uint32_t n_list, int again) {
+      return ygm_k_launch_json(d_states, d_state_off, d_names, d_name_off, n_docs, fl, kind, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
+                               c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), meta, 0,
+                               total, c->sn_pend.as<uint32_t>(), n_list, again, s);
+    };
+    if (launch(0, 0)) return YGM_EDEVICE;
+    if ((e = read_meta(c, s, m, meta))) return e;
+    if (m.fb_count) {   // the documents whose JSON did not fit: sized from the recorded lengths, run again
+      reran = m.fb_count; ovf = m.cursor;
+      if (!c->sn_ws.ensure(total + ovf + 64, total, s)) return YGM_ENOMEM;
+      if (launch(reran, 1)) return YGM_EDEVICE;
+      if ((e = read_meta(c, s, m, meta))) return e;
+    }
+  }
+  HIPCHK(hipEventRecord(c->e1, s));
+  HIPCHK(hipEventSynchronize(c->e1));
+  if (getenv("YGM_TIER_COUNTS"))   // (testing knob, as the text's line)
+    fprintf(stderr, "ygm json tiers: docs %u general %u overflow %u overflow_bytes %llu\n", n_docs, n_docs, reran, (unsigned long long)ovf);
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
+  c->stats.calls++; c->stats.docs += n_docs; c->stats.bytes_in += states_bytes; c->stats.bytes_out += m.payload;
+  out->data = c->sn_ws.as<uint8_t>(); out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
+  out->status = c->status.as<int32_t>(); out->data_bytes = total + ovf; out->payload_bytes = m.payload;
+  return YGM_OK;
+}
 // a snapshot batch's outputs packed into one arena on the device (k_pack_*: offsets n + 1, the total at [n]) with its
 // statuses, for kernels that read documents by offsets (step2's diff, contains)
 static int pack_snapshots(ygm_ctx* c, hipStream_t s, const ygm_device_result& r1, uint32_t n_docs) {
@@ -1344,7 +1399,7 @@ namespace {
 // The host API's operations; OPS below holds one row per operation, in this order.
 enum class Op : uint8_t {
   Sv, Diff, Merge, Snapshot, Contains, MergeV2, DiffV2, SvV2, V1ToV2, V2ToV1, Step2, DiffShared, Step2Shared, VersionTake,
-  VersionRestore, VersionRestoreShared, Text, Count
+  VersionRestore, VersionRestoreShared, Text, Json, Count
 };
 enum class Primary : uint8_t { Docs, Updates, States };   // what the first arena's offsets count
 enum class OptOf : uint8_t { None, Doc, State, Ask };     // whose option bytes travel with a chunk
@@ -1356,7 +1411,7 @@ struct HostCall {
   const uint32_t* link = nullptr;   // merge: each update's document; shared: each ask's state
   const uint8_t* arena2 = nullptr; const uint64_t* off2 = nullptr;   // the second arena, one entry per result (OpRow::second)
   const uint8_t* opt = nullptr;     // option bytes (OpRow::opt says whose), null: none; each chunk stages its slice
-  uint32_t text_mode = 0;           // Op::Text: YGM_TEXT_FLAT / YGM_TEXT_DEEP
+  uint32_t text_mode = 0;           // Op::Text: YGM_TEXT_FLAT / YGM_TEXT_DEEP; Op::Json: the kind (YGM_JSON_PROSEMIRROR)
 };
 // a chunk's inputs on its stage context, as the device entry points take them
 struct Staged {
@@ -1374,7 +1429,7 @@ struct Chunk : ygm::ChunkRange {
 struct OpRow {
   Op op;
   Primary primary;
-  bool second;    // a second arena per result (diff: state vectors, contains: updates, restore: versions, text: root names)
+  bool second;    // a second arena per result (diff: state vectors, contains: updates, restore: versions, text / json: root names)
   OptOf opt;
   int (*run)(ygm_ctx* k, const Staged& S, ygm_device_result* dr);   // the staged chunk on stage context k
   int (*enqueue)(ygm_ctx* k, const Staged& S);   // device work enqueued before the next chunk is staged (null: none)
@@ -1434,6 +1489,10 @@ static int run_text(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
   return ygm_text_v1_device(k, S.arena, S.bytes, S.off, S.arena2, S.off2, S.text_mode, S.n_res, nullptr, dr);
 }
 
+static int run_json(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_json_v1_device(k, S.arena, S.bytes, S.off, S.arena2, S.off2, S.text_mode, S.n_res, nullptr, dr);
+}
+
 constexpr OpRow OPS[] = {
     {Op::Sv, Primary::Docs, false, OptOf::None, run_sv, nullptr},
     {Op::Diff, Primary::Docs, true, OptOf::None, run_diff, nullptr},
@@ -1452,6 +1511,7 @@ constexpr OpRow OPS[] = {
     {Op::VersionRestore, Primary::Docs, true, OptOf::Doc, run_version_restore, nullptr},
     {Op::VersionRestoreShared, Primary::States, true, OptOf::Ask, run_version_restore_shared, nullptr},
     {Op::Text, Primary::Docs, true, OptOf::None, run_text, nullptr},
+    {Op::Json, Primary::Docs, true, OptOf::None, run_json, nullptr},
 };
 constexpr bool ops_in_order() {
   for (size_t i = 0; i < sizeof(OPS) / sizeof(OPS[0]); i++) if (OPS[i].op != (Op)i) return false;
@@ -1764,6 +1824,17 @@ int ygm_text_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, co
   if (n_docs && !names) { if (name_off[n_docs] != name_off[0]) return YGM_EINVAL; names = no_names; }   // (no byte of it is read)
   HostCall H{Op::Text, states, n_docs ? state_off : ZERO_OFF, n_docs, n_docs, nullptr, names, n_docs ? name_off : ZERO_OFF};
   H.text_mode = mode;
+  return host_call(c, H, out);
+}
+
+int ygm_json_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* names, const uint64_t* name_off, uint32_t kind,
+                uint32_t n_docs, ygm_result* out) {
+  if (!c || !out || kind != YGM_JSON_PROSEMIRROR || (n_docs && (!states || !state_off || !name_off))) return YGM_EINVAL;
+  for (uint32_t d = 0; d < n_docs; d++) if (state_off[d + 1] < state_off[d] || name_off[d + 1] < name_off[d]) return YGM_EINVAL;
+  static const uint8_t no_names[1] = {0};   // (every name empty: the arena may be NULL)
+  if (n_docs && !names) { if (name_off[n_docs] != name_off[0]) return YGM_EINVAL; names = no_names; }   // (no byte of it is read)
+  HostCall H{Op::Json, states, n_docs ? state_off : ZERO_OFF, n_docs, n_docs, nullptr, names, n_docs ? name_off : ZERO_OFF};
+  H.text_mode = kind;
   return host_call(c, H, out);
 }
 

@@ -157,7 +157,8 @@ YDEV uint32_t dec_digits(uint64_t v, uint8_t* t) {   // decimal, most significan
 }
 
 // ---------------------------------------------------------------- Any -> JSON.stringify (public V2 -> V1)
-YDEV void js_quote(Out& o, const uint8_t* s, uint32_t n) {
+template <class O>
+YDEV void js_quote(O& o, const uint8_t* s, uint32_t n) {
   const char* hx = "0123456789abcdef";
   o.b('"');
   for (uint32_t i = 0; i < n; i++) {
@@ -171,8 +172,10 @@ YDEV void js_quote(Out& o, const uint8_t* s, uint32_t n) {
   o.b('"');
 }
 // one canonical Any (validated) as JSON.stringify writes it; numbers other than varInt integers, undefined and
-// Uint8Array are refused (ST_NONCANON), a BigInt throws in JSON.stringify (ST_MALFORMED)
-YDEV_NI int any_json(Cur& c, Out& o) {
+// Uint8Array are refused (ST_NONCANON), a BigInt throws in JSON.stringify (ST_MALFORMED).  O: the writer (Out here,
+// snap::OutCap for ygm_json_v1)
+template <class O>
+YDEV_NI int any_json(Cur& c, O& o) {
   uint32_t rem[MAX_DEPTH + 1]; uint8_t obj[MAX_DEPTH + 1]; uint8_t first[MAX_DEPTH + 1];
   int d = 0; rem[0] = 1; obj[0] = 2; first[0] = 1;
   while (!c.err) {

@@ -30,6 +30,7 @@ F_COMPAT_135 = 1
 F_FORCE_SEQ = 2
 DOC_NO_GC = 1   # YGM_DOC_NO_GC: a document's option byte, the document is a Y.Doc({gc: false})
 TEXT_FLAT, TEXT_DEEP = 0, 1   # YGM_TEXT_FLAT / YGM_TEXT_DEEP: the modes of ygm_text_v1
+JSON_PROSEMIRROR = 0          # YGM_JSON_PROSEMIRROR: the one kind of ygm_json_v1
 
 
 class YjsError(Exception):
@@ -79,7 +80,7 @@ EXPORTS = ("ygm_open", "ygm_close", "ygm_merge_v1", "ygm_diff_v1", "ygm_sv_from_
            "ygm_snapshot_opts_v1_device", "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device",
            "ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device",
            "ygm_version_restore_shared_v1", "ygm_version_restore_shared_v1_device",
-           "ygm_text_v1", "ygm_text_v1_device")
+           "ygm_text_v1", "ygm_text_v1_device", "ygm_json_v1", "ygm_json_v1_device")
 
 
 def lib():
@@ -144,7 +145,9 @@ def lib():
             getattr(L, f).restype = i32
         L.ygm_text_v1.argtypes = [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
         L.ygm_text_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
-        for f in ("ygm_text_v1", "ygm_text_v1_device"):
+        L.ygm_json_v1.argtypes = [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
+        L.ygm_json_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
+        for f in ("ygm_text_v1", "ygm_text_v1_device", "ygm_json_v1", "ygm_json_v1_device"):
             getattr(L, f).restype = i32
         L.ygm_merge_v2.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
         L.ygm_diff_v2.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
@@ -521,6 +524,32 @@ class Engine:
         m = (TEXT_DEEP if deep else TEXT_FLAT) if mode is None else int(mode)
         st = lib().ygm_text_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off), _dptr(d_names),
                                       _dptr(d_name_off), m, n_docs, stream or None, ctypes.byref(r))
+        if st != OK:
+            raise YjsError(st)
+        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+
+    # ------------------------------------------------------------ ProseMirror JSON
+    def json_batch(self, states, names, kind=JSON_PROSEMIRROR):
+        """Stored documents as ProseMirror / Tiptap JSON (ygm_json_v1): for doc = Y.applyUpdate(new Y.Doc(), state),
+        the UTF-8 of JSON.stringify(yXmlFragmentToProsemirrorJSON(doc.getXmlFragment(name))) -- what
+        TiptapTransformer.fromYdoc(doc, name) returns -> list of bytes, or a YjsError for a refused document (the
+        caller keeps its yjs path for it).  names: one root name per state (str or bytes).  A name the state has no
+        root for gives b'{"type":"doc","content":[]}'."""
+        if len(states) != len(names):
+            raise ValueError("one root name per state")
+        sa, so = _pack([bytes(s) for s in states])
+        na, no = _pack([n.encode() if isinstance(n, str) else bytes(n) for n in names])
+        res = _Result()
+        st = lib().ygm_json_v1(self._ctx, sa or None, _ptr(so), na or None, _ptr(no), int(kind), len(states), ctypes.byref(res))
+        if st != OK:
+            raise YjsError(st)
+        return [b if s == OK else YjsError(s) for s, b in self._unpack(res)]
+
+    def json_device(self, d_states, states_bytes, d_state_off, d_names, d_name_off, n_docs, kind=JSON_PROSEMIRROR, stream=0) -> "DeviceResult":
+        """Device-resident JSON batch (ygm_json_v1_device): the states arena followed by TAIL_PAD readable bytes."""
+        r = _DevResult()
+        st = lib().ygm_json_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off), _dptr(d_names),
+                                      _dptr(d_name_off), int(kind), n_docs, stream or None, ctypes.byref(r))
         if st != OK:
             raise YjsError(st)
         return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)

@@ -189,6 +189,51 @@ int ygm_contains_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_o
 #define YGM_TEXT_DEEP 1u
 int ygm_text_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *names,
                 const uint64_t *name_off, uint32_t mode, uint32_t n_docs, ygm_result *out);
+/* ---- stored documents as ProseMirror / Tiptap JSON ---------------------------
+ * What a stored document is, without loading it into a Y.Doc: for doc = Y.applyUpdate(new Y.Doc(), state) and a root
+ * name (UTF-8 bytes, compared bytewise, as in ygm_text_v1), document d's output for kind YGM_JSON_PROSEMIRROR is the
+ * UTF-8 of
+ *     JSON.stringify(yXmlFragmentToProsemirrorJSON(doc.getXmlFragment(name)))
+ * that is JSON.stringify(TiptapTransformer.fromYdoc(doc, name)) -- y-prosemirror's function (the reference pins
+ * 1.3.4), restated over yjs 13.5.16's toArray / toDelta / getAttributes / nodeName:
+ *     serialize(XmlText)    = toDelta().map(d => { type:'text', text:d.insert,
+ *                               marks?: Object.keys(d.attributes).map(k => ({ type:k, attrs:d.attributes[k] })) })
+ *     serialize(XmlElement) = { type:nodeName, attrs?: getAttributes() (when it has a key),
+ *                               content?: toArray().map(serialize).flat() (when toArray() is not empty) }
+ *     result                = { type:'doc', content: fragment.toArray().map(serialize) }   (top level not flattened)
+ * with the keys in exactly that order.  toArray keeps a list's live countable items.  toDelta: a live ContentFormat
+ * flushes the pending string, then a null value deletes its key from currentAttributes (a Map) and any other sets it
+ * (an existing key keeps its place; delete then set moves it to the end); live ContentStrings append to the pending
+ * string (U+FFFD on both sides of a cut surrogate pair); a live ContentEmbed flushes and gives one op whose text is
+ * the embed's JSON value; the end of the list flushes; deleted items are ignored; ops with equal marks are not
+ * merged, strings across deleted items are.  getAttributes: the type's map entries whose current item is not
+ * deleted, the value the last element of its ContentAny.  attrs and marks follow JavaScript's own-property order:
+ * canonical array-index keys ascending, then insertion order.  Any values are written as the V2 -> V1 conversion
+ * writes them, format and embed values (canonical JSON text in V1) are copied, strings are escaped as JSON.stringify
+ * escapes them (\" \\ \b \f \n \r \t, other bytes below 0x20 as \u00xx, everything else verbatim).
+ * A name the update has no root for gives {"type":"doc","content":[]} with YGM_OK; a state with pending structs / a
+ * pending delete set is read through its integrated part with YGM_OK.  Refusals affect only their own document
+ * (length 0); in the asked root's subtree:
+ *   a live list child of a fragment or element that is not a type; a child type that is neither XmlElement nor
+ *   XmlText; a live type inside an XmlText; a live attribute that is not a ContentAny, or whose value is undefined or
+ *   a Uint8Array; a mark key ending in "--" plus 8 characters of [A-Za-z0-9+/=] (newer y-prosemirror versions
+ *   rewrite such names)                                                                   YGM_EUNSUPPORTED
+ *   a number in an attribute, mark or embed that is not an integer JSON.stringify writes without an exponent
+ *   (as ygm_convert_v2_to_v1 refuses it)                                                  YGM_ENONCANON
+ *   a BigInt (JSON.stringify throws)                                                      YGM_EMALFORMED
+ *   a JSON of 2^31 bytes or more                                                          YGM_ENOMEM
+ * Any other status is the one the state's parse and integration give in ygm_snapshot_v1.  The caller keeps its yjs
+ * path for refused documents.  A JSON has no bound in its state's size (every op repeats the current marks): one
+ * that does not fit its workspace is neither cut nor refused -- the documents concerned run a second time into a
+ * region sized from their recorded lengths, at the cost of one more host wait (ygm_stats_t.host_syncs).
+ * states / state_off / names / name_off, tail padding, packing and the other statuses as ygm_text_v1.  A kind other
+ * than YGM_JSON_PROSEMIRROR is YGM_EINVAL for the call (room for toJSON of Map and Array roots).  No options form:
+ * the JSON depends neither on YGM_F_COMPAT_135 nor on garbage collection.
+ * (Replaces packages/extension-webhook/src/index.ts:119, packages/transformer/src/Prosemirror.ts:26: the document a
+ * change webhook or a REST read sends, transformer.fromYdoc(document, fieldName).) */
+#define YGM_JSON_PROSEMIRROR 0u
+int ygm_json_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *names,
+                const uint64_t *name_off, uint32_t kind, uint32_t n_docs, ygm_result *out);
 /* SyncStep2 payload of a stored document: Y.encodeStateAsUpdate(doc, sv) for doc = Y.applyUpdate(new Y.Doc(), state)
  * -- what the reference sends in reply to a SyncStep1 (packages/server/src/MessageReceiver.ts:137-138) for a
  * document loaded from stored bytes (extension-database Database.ts:44-50).  Computed as the doc-normalized
@@ -387,6 +432,13 @@ int ygm_contains_v1_device(ygm_ctx *ctx, const uint8_t *d_states, const uint64_t
  * (Replaces no single reference interface, as ygm_text_v1.) */
 int ygm_text_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                        const uint8_t *d_names, const uint64_t *d_name_off, uint32_t mode, uint32_t n_docs, void *stream,
+                       ygm_device_result *out);
+/* ygm_json_v1, device-resident, as ygm_text_v1_device: 64 readable bytes must follow both arenas, results are not
+ * packed (a document's JSON lies in its workspace's output region, or in the overflow region after the workspaces
+ * when it ran a second time), payload_bytes is the sum of the lengths.
+ * (Replaces packages/extension-webhook/src/index.ts:119, packages/transformer/src/Prosemirror.ts:26, as ygm_json_v1.) */
+int ygm_json_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
+                       const uint8_t *d_names, const uint64_t *d_name_off, uint32_t kind, uint32_t n_docs, void *stream,
                        ygm_device_result *out);
 int ygm_sync_step2_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                              const uint8_t *d_sv_arena, const uint64_t *d_sv_off, uint32_t n_docs, void *stream,

@@ -49,6 +49,9 @@ export declare class GpuEngine {
   /** plain text of stored documents: doc.getText(names[i]).toString() of doc = Y.applyUpdate(new Y.Doc(), states[i]); deep:
    *  also descends into nested types (XmlFragment / Tiptap), one '\n' after each; an absent root name gives '' */
   textMany (states: Uint8Array[], names: (string | Uint8Array)[], opts?: { deep?: boolean }): Promise<(string | YgmError)[]>
+  /** stored documents as ProseMirror / Tiptap JSON: JSON.stringify(TiptapTransformer.fromYdoc(doc, names[i])) of
+   *  doc = Y.applyUpdate(new Y.Doc(), states[i]); a document outside the envelope gives a YgmError in its place */
+  jsonMany (states: Uint8Array[], names: (string | Uint8Array)[]): Promise<(string | YgmError)[]>
   /** Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), new Y.Doc(opts))) of doc =
    *  Y.applyUpdate(new Y.Doc({ gc: false }), state); several versions of one document: restoreVersionShared */
   restoreVersion (state: Uint8Array, version: Uint8Array, opts?: DocOptions): Promise<Uint8Array>
@@ -88,6 +91,7 @@ export declare class GpuEnginePool {
   takeVersionMany (names: string[], states: Uint8Array[]): Promise<(Uint8Array | YgmError)[]>
   /** docNames[i] routes states[i]; names[i] is its root name */
   textMany (docNames: string[], states: Uint8Array[], names: (string | Uint8Array)[], opts?: { deep?: boolean }): Promise<(string | YgmError)[]>
+  jsonMany (docNames: string[], states: Uint8Array[], names: (string | Uint8Array)[]): Promise<(string | YgmError)[]>
   restoreVersionMany (names: string[], states: Uint8Array[], versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** names[i] naming states[i], routed as step2Shared; opts: one option per ask */
   restoreVersionShared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
@@ -168,6 +172,13 @@ export declare class GpuMerge implements Extension {
   textOf (names: string[], opts?: { field?: string, deep?: boolean }): Promise<Map<string, string>>
   /** restoreVersions followed by one text batch over the fulfilled results, settled per entry */
   versionTexts (entries: { documentName: string, version: Uint8Array, gc?: boolean }[], opts?: { field?: string, deep?: boolean }): Promise<({ status: 'fulfilled', value: string } | { status: 'rejected', reason: Error })[]>
+  /** what each loaded document is: JSON.stringify(TiptapTransformer.fromYdoc(document, field)) (field 'default'), or the
+   *  parsed object with parse: true, one GPU batch; unloaded documents are left out, refused ones left out and named in `unserialized` */
+  jsonOf (names: string[], opts?: { field?: string, parse?: boolean }): Promise<Map<string, string | object>>
+  /** restoreVersions followed by one JSON batch over the fulfilled results, settled per entry */
+  versionJson (entries: { documentName: string, version: Uint8Array, gc?: boolean }[], opts?: { field?: string, parse?: boolean }): Promise<({ status: 'fulfilled', value: string | object } | { status: 'rejected', reason: Error })[]>
+  /** documents whose JSON the engine refused in jsonOf / versionJson: the caller keeps its yjs path (transformer.fromYdoc) for them */
+  unserialized: { documentName: string, code: string }[]
   /** batched SyncStep1 responder over the captured state (snapshot + updates since) */
   syncResponder (): SyncResponder
   /** batched extension-redis fan-out over the same captured state */

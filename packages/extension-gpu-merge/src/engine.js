@@ -118,6 +118,8 @@ function packBlobs (blobs) {
 const DOC_NO_GC = 1
 /** YGM_TEXT_FLAT / YGM_TEXT_DEEP: the modes of ygm_text_v1 */
 const TEXT_FLAT = 0; const TEXT_DEEP = 1
+/** YGM_JSON_PROSEMIRROR: the one kind of ygm_json_v1 */
+const JSON_PROSEMIRROR = 0
 // per-document options -> option bytes, or undefined when none is set (the plain native entry points): an entry is an
 // option byte, `true` (no-GC), or { gc: boolean } as in yDocOptions; a Uint8Array is taken as it is
 function optBytes (opts, n) {
@@ -170,6 +172,10 @@ class GpuEngine {
       if (op === 'text' || op === 'textDeep') {   // a job is [state, root name bytes]
         const u = packBlobs(jobs.map(j => j[0])); const n = packBlobs(jobs.map(j => j[1]))
         return a.text(this.handle, u.arena, u.lens, n.arena, n.lens, op === 'textDeep' ? TEXT_DEEP : TEXT_FLAT)
+      }
+      if (op === 'json') {   // a job is [state, root name bytes]
+        const u = packBlobs(jobs.map(j => j[0])); const n = packBlobs(jobs.map(j => j[1]))
+        return a.json(this.handle, u.arena, u.lens, n.arena, n.lens, JSON_PROSEMIRROR)
       }
       if (op === 'restoreVersion') {   // a job is [state, version, option byte]
         const u = packBlobs(jobs.map(j => j[0])); const v = packBlobs(jobs.map(j => j[1]))
@@ -299,6 +305,20 @@ class GpuEngine {
     return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
   }
 
+  /**
+   * Stored documents as ProseMirror / Tiptap JSON, as an explicit batch: for doc = Y.applyUpdate(new Y.Doc(), states[i])
+   * the string JSON.stringify(yXmlFragmentToProsemirrorJSON(doc.getXmlFragment(names[i]))) -- what
+   * TiptapTransformer.fromYdoc(doc, names[i]) returns, stringified (ygm_json_v1).  names: strings or UTF-8 bytes.  A
+   * name the state has no root for gives '{"type":"doc","content":[]}'; a document outside the envelope (a root that
+   * is no XmlFragment of elements and texts, a float, ...) gives a YgmError in its place.
+   */
+  async jsonMany (states, names) {
+    if (names.length !== states.length) throw new YgmError(8, 'one root name per state')
+    const jobs = states.map((s, i) => [s, names[i] instanceof Uint8Array ? names[i] : Buffer.from(String(names[i]), 'utf8')])
+    const r = await this._run('json', jobs)
+    return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
+  }
+
   /** update format V2 (yjs providers other than Hocuspocus's V1 path): Y.mergeUpdatesV2 / Y.diffUpdateV2 /
    *  Y.encodeStateVectorFromUpdateV2 / yjs 13.6 Y.convertUpdateFormatV1ToV2 / V2ToV1, as explicit batches */
   async mergeManyV2 (docs) { const r = await this._run('mergeV2', docs); return unpack(r) }
@@ -413,6 +433,8 @@ class GpuEnginePool {
   }
   /** textMany with one document name per state (the shard), beside its root name */
   textMany (docNames, states, names, opts) { return this._many(docNames, [states, names], (e, a, b) => e.textMany(a, b, opts)) }
+  /** jsonMany with one document name per state (the shard), beside its root name */
+  jsonMany (docNames, states, names) { return this._many(docNames, [states, names], (e, a, b) => e.jsonMany(a, b)) }
   stats () { return this.engines.map(e => e.stats()) }
   /**
    * Node-wide totals (the reference's server-wide counters, Hocuspocus.ts:138-160): every numeric field of the

@@ -96,6 +96,9 @@ class GpuMerge {
     this.refused = []
     /** normalize: stores that kept the merged bytes (snapshot outside the kernel's envelope) */
     this.unnormalized = []
+    /** jsonOf / versionJson: documents whose JSON the engine refused (outside ygm_json_v1's envelope: the caller keeps
+     *  its yjs path, transformer.fromYdoc, for them) */
+    this.unserialized = []
   }
 
   _Y () { if (!this.Y) this.Y = require('yjs'); return this.Y }
@@ -249,6 +252,53 @@ class GpuMerge {
       ? await eng.textMany(ok.map(i => entries[i].documentName), ok.map(i => out[i].value), fields, { deep })
       : await eng.textMany(ok.map(i => out[i].value), fields, { deep })
     ok.forEach((i, k) => { out[i] = res[k] instanceof Error ? { status: 'rejected', reason: res[k] } : { status: 'fulfilled', value: res[k] } })
+    return out
+  }
+
+  /**
+   * Document JSON (INTEGRATION.md "Document JSON / webhook bodies").  jsonOf(names, { field, parse }): what each loaded
+   * document is -- JSON.stringify(TiptapTransformer.fromYdoc(document, field)), the body the reference's webhook sends
+   * -- in one GPU batch over the captured states -> Map name -> JSON string, or the parsed object with parse: true.  A
+   * document that is not loaded is left out; one the engine refuses (a root that is no XmlFragment of elements and
+   * texts, a float attribute, ...) is left out and named in `unserialized`: the caller keeps its yjs path for it.
+   */
+  async jsonOf (names, { field = 'default', parse = false } = {}) {
+    const eng = this._engine()
+    const states = await this._statesOf(names)
+    const idx = names.map((_, i) => i).filter(i => states[i] && !(states[i] instanceof Error))
+    const fields = idx.map(() => field)
+    const res = !idx.length ? [] : typeof eng.shardOf === 'function'
+      ? await eng.jsonMany(idx.map(i => names[i]), idx.map(i => states[i]), fields)
+      : await eng.jsonMany(idx.map(i => states[i]), fields)
+    const out = new Map()
+    idx.forEach((i, k) => {
+      if (res[k] instanceof Error) this.unserialized.push({ documentName: names[i], code: res[k].code || String(res[k]) })
+      else out.set(names[i], parse ? JSON.parse(res[k]) : res[k])
+    })
+    return out
+  }
+
+  /**
+   * versionJson(entries, { field, parse }): restoreVersions(entries) followed by one JSON batch over the fulfilled
+   * results -- a saved version shown as a document, without a Y.Doc per version.  Settled per entry as restoreVersions
+   * is: { status: 'fulfilled', value: string | object } or { status: 'rejected', reason } (a refused version is
+   * rejected with the engine's error and named in `unserialized`).
+   */
+  async versionJson (entries, { field = 'default', parse = false } = {}) {
+    const eng = this._engine()
+    const out = await this.restoreVersions(entries)
+    const ok = out.map((r, i) => r.status === 'fulfilled' ? i : -1).filter(i => i >= 0)
+    if (!ok.length) return out
+    const fields = ok.map(() => field)
+    const res = typeof eng.shardOf === 'function'
+      ? await eng.jsonMany(ok.map(i => entries[i].documentName), ok.map(i => out[i].value), fields)
+      : await eng.jsonMany(ok.map(i => out[i].value), fields)
+    ok.forEach((i, k) => {
+      if (res[k] instanceof Error) {
+        this.unserialized.push({ documentName: entries[i].documentName, code: res[k].code || String(res[k]) })
+        out[i] = { status: 'rejected', reason: res[k] }
+      } else out[i] = { status: 'fulfilled', value: parse ? JSON.parse(res[k]) : res[k] }
+    })
     return out
   }
 
