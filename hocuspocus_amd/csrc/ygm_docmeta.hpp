@@ -1,5 +1,5 @@
 // ygm_docmeta.hpp -- what the kernel files share: the per-launch device counters, merge output slots, and the
-// launch glue's device-size cache and error report.
+// launch glue's device-size cache (the launch-error report is ygm_launch_rc, ygm_launch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -69,12 +69,6 @@ static uint32_t device_cus() {
     (void)hipGetDevice(&dev);
     return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? (uint32_t)n : 256u;
   });
-}
-
-static int launch_rc(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) fprintf(stderr, "ygm: %s: %s\n", fn, hipGetErrorString(e));
-  return (int)e;
 }
 
 }  // namespace ygm

@@ -4,6 +4,9 @@
 // buffers and HIP-event timers.  A batch call = H2D of the packed inputs, one
 // fast-path launch (look-back placed, packed output), an 8-byte-class meta
 // read, the sequential kernel only when some document needed it, D2H.
+// The stored-document operations (snapshot, text, JSON, contains) are one
+// workspace batch: ws_begin / ws_flat / ws_plan / ws_finish.  Every read-back
+// goes through read_meta, read_u64s or read_u64_pair, which count the call's host waits.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -12,6 +15,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <thread>
 #include <vector>
 
@@ -103,12 +107,13 @@ struct ygm_ctx {
   // shared-state diff / step2: per ask the checked state id, the scanned state lengths (slot bases, n_asks + 1), scan
   // scratch; step2: the asks of pending states and their count
   DevBuf ask_ix, ask_base, ask_bs, ask_pl, ask_pn;
+  // the workspace batch (snapshot, text, JSON, contains): per-document counts, workspace offsets, scan scratch,
+  // [flat-tier output slots | workspaces], flat-tier claims, its payload / claimed counters
   DevBuf sn_cnt, sn_off, sn_bs, sn_ws, sn_claim, sn_pay;
   DevBuf sn_pend, pn_off, pn_du, pn_arena;   // snapshot: documents left pending, their three-update batch for the merge
   DevBuf pq_off, pq_a, pq_b, pq_c, pq_s, pq_st;   // step2 of pending documents: their parts and state vectors, statuses
   ygm_ctx* pend_ctx = nullptr;               // ... merged on this child context (its own buffers and counters)
-  ygm_ctx* pend_dx[2] = {nullptr, nullptr};  // ... and the step2 diffs of their parts on these  // snapshot: per-document counts, workspace offsets, scan scratch,
-  // [LDS-tier output slots | workspaces], LDS-tier claims, its payload / claimed counters
+  ygm_ctx* pend_dx[2] = {nullptr, nullptr};  // ... and the step2 diffs of their parts on these
   // update V2: per-update V1 sizes -> offsets, transcoding statuses, scan scratch, the V1 arena, per-document column
   // lengths, the V2 outputs (packed), their offsets / lengths / statuses
   DevBuf v2_len, v2_st, v2_bs, v2_v1, v2_L, v2_out, v2_off, v2_olen, v2_ost, v2_fo, v2_claim, v2_pay, v2_scr, v21_cl;
@@ -228,6 +233,32 @@ static int read_meta(ygm_ctx* c, hipStream_t s, Meta& m, const void* slot) {
   HIPCHK(hipStreamSynchronize(s));
   m = *c->h_meta;
   return YGM_OK;
+}
+// Every read-back smaller than a Meta goes through the three helpers below (through the pinned h_meta), so
+// ygm_stats_t.host_syncs counts each of the calls' waits.
+static_assert(sizeof(Meta) >= 4 * sizeof(uint64_t), "h_meta holds read_u64s' four values");
+// one 8-byte value from each of up to four device places, read with one wait
+static int read_u64s(ygm_ctx* c, hipStream_t s, std::initializer_list<const uint64_t*> src, uint64_t* v) {
+  if (src.size() > 4) return YGM_EINVAL;
+  c->stats.host_syncs++;
+  uint64_t* h = (uint64_t*)c->h_meta;
+  for (const uint64_t* p : src) HIPCHK(hipMemcpyAsync(h++, p, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  memcpy(v, c->h_meta, 8 * src.size());
+  return YGM_OK;
+}
+// the two consecutive values at d_p (a tier's byte and document counters), one 16-byte copy
+static int read_u64_pair(ygm_ctx* c, hipStream_t s, const uint64_t* d_p, uint64_t (&v)[2]) {
+  c->stats.host_syncs++;
+  HIPCHK(hipMemcpyAsync(c->h_meta, d_p, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  memcpy(v, c->h_meta, 16);
+  return YGM_OK;
+}
+static uint64_t read_u64(ygm_ctx* c, hipStream_t s, const uint64_t* d_p, int& e) {
+  uint64_t v = 0;
+  e = read_u64s(c, s, {d_p}, &v);
+  return v;
 }
 
 static void fill_dev_result(ygm_ctx* c, uint64_t data_bytes, ygm_device_result* out) {
@@ -467,7 +498,6 @@ int ygm_merge_v1_device_lens(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_
   return ygm_merge_v1_device_finish(c, out);
 }
 
-static uint64_t read_u64(ygm_ctx* c, hipStream_t s, const uint64_t* d_p, int& e);
 // the plan of a shared-state call: c->ask_ix (checked state id per ask) and c->ask_base (exclusive scan of the asks'
 // state lengths, the total at [n_asks])
 static int ask_plan(ygm_ctx* c, hipStream_t s, const uint64_t* d_doc_off, uint32_t n_docs, const uint32_t* d_ask_doc, uint32_t n_asks) {
@@ -553,20 +583,9 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
   return YGM_OK;
 }
 
-// Documents k_snap left pending (ST_PEND: PendHdr, then [state, pendingDs, pending structs]): encodeStateAsUpdate
-// returns mergeUpdates of the three (Y@23300).  They are packed into one arena as three-update documents (k_pend_plan /
-// k_pend_copy) and merged by the merge kernels on the child context c->pend_ctx; the merged bytes are appended to the
-// snapshot's output region at `used` and the documents' offsets, lengths and statuses rewritten (k_pend_fix).
-// the pending documents' three-update batch (c->pn_arena / pn_off / pn_du, `total` bytes) merged on the child context
+// The pending documents' three-update batch (c->pn_arena / pn_off / pn_du, `total` bytes) merged on the child context
 // c->pend_ctx; the merged bytes appended to `dst` at `used` and the documents' places, lengths and statuses written
-// (pst: statuses decided before the merge, nullable)
-static uint64_t read_u64(ygm_ctx* c, hipStream_t s, const uint64_t* d_p, int& e) {
-  uint64_t v = 0;
-  c->stats.host_syncs++;
-  e = hipMemcpyAsync(c->h_meta, d_p, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ? YGM_EDEVICE : 0;
-  memcpy(&v, c->h_meta, 8);
-  return v;
-}
+// (k_pend_fix; pst: statuses decided before the merge, nullable)
 static int pend_merge_place(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t total, const int32_t* pst, DevBuf& dst, uint64_t used,
                             uint64_t& data_bytes, unsigned long long& payload, const uint32_t* list = nullptr) {
   if (!list) list = c->sn_pend.as<uint32_t>();   // (the shared-state step2: its list of asks)
@@ -585,6 +604,9 @@ static int pend_merge_place(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t tota
   c->stats.docs_pending += P;
   return YGM_OK;
 }
+// Documents k_snap left pending (ST_PEND: PendHdr, then [state, pendingDs, pending structs]): encodeStateAsUpdate
+// returns mergeUpdates of the three (Y@23300).  They are packed into one arena as three-update documents (k_pend_plan /
+// k_pend_copy) and merged by pend_merge_place, which appends the merged bytes to the snapshot's output region at `used`.
 static int snap_resolve_pending(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t used, uint64_t& data_bytes, unsigned long long& payload) {
   if (!c->pn_off.ensure(8ull * (3ull * P + 1) + 16) || !c->pn_du.ensure(4ull * (P + 1) + 16)) return YGM_ENOMEM;
   if (ygm_k_launch_pend_plan(c->sn_pend.as<uint32_t>(), P, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->pn_off.as<uint64_t>(),
@@ -601,6 +623,78 @@ static int snap_resolve_pending(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t 
   return pend_merge_place(c, s, P, total, nullptr, c->sn_ws, used, data_bytes, payload);
 }
 
+// ---- the workspace batch: the steps the stored-document operations share (snapshot, text, JSON, contains).  A batch
+// writes per-document places, lengths and statuses (c->out_off, out_len, status) and its bytes into c->sn_ws:
+// [the flat tier's per-document slots | the general path's workspaces], the workspaces sized by a count and scan
+// launch into c->sn_off.  An operation names only what differs: its launches, its tier line, what it does with the
+// counters.  The context's snapshot buffers serve every operation (one batch in flight per context).
+struct WsBatch {
+  ygm_ctx* c; hipStream_t s; uint32_t n_docs;
+  void* meta;               // counter slot 2, reset by ws_begin
+  uint64_t slot_total = 0;  // bytes of the flat tier's slot region (0: the tier did not run)
+  uint64_t total = 0;       // bytes of the workspaces after it (ws_plan)
+  uint64_t flat_pay = 0, flat_docs = 0, flat_first = 0;   // flat tier: payload bytes, documents claimed, by launch 0
+  const uint8_t* claim() const { return slot_total ? c->sn_claim.as<uint8_t>() : nullptr; }
+  unsigned long long* payload() const { return (unsigned long long*)((uint8_t*)meta + offsetof(Meta, payload)); }
+  unsigned int* fb_count() const { return (unsigned int*)((uint8_t*)meta + offsetof(Meta, fb_count)); }
+};
+// begin: the per-document buffers, the counters reset, event e0
+static int ws_begin(ygm_ctx* c, hipStream_t s, uint32_t n_docs, WsBatch& B) {
+  const uint32_t nb = (n_docs + 1 + 255) / 256;
+  if (!c->sn_cnt.ensure(16ull * n_docs + 16) || !c->sn_off.ensure(8ull * n_docs + 16) || !c->sn_bs.ensure(8ull * nb + 16) ||
+      !c->out_off.ensure(8ull * n_docs + 8) || !c->out_len.ensure(8ull * n_docs + 8) || !c->status.ensure(4ull * n_docs + 4))
+    return YGM_ENOMEM;
+  B.c = c; B.s = s; B.n_docs = n_docs; B.meta = c->meta_slot(2);
+  HIPCHK(hipMemsetAsync(B.meta, 0, sizeof(Meta), s));
+  HIPCHK(hipEventRecord(c->e0, s));
+  return YGM_OK;
+}
+// the flat tier: launch(again) writes flat documents (input + workspace in LDS) into per-document slots of c->sn_ws
+// and claims them -- 6 KiB of LDS per document, then 24 KiB for what that left; one read of the tier's counters after
+// each.  The documents it leaves take the general path, whose workspaces follow the slot region.  YGM_SNAP_NOLDS
+// (testing knob) turns the tier off.
+extern "C++" template <class L>
+static int ws_flat(WsBatch& B, uint64_t in_bytes, L launch) {
+  ygm_ctx* c = B.c;
+  if (!B.n_docs || getenv("YGM_SNAP_NOLDS")) return YGM_OK;
+  B.slot_total = 2 * in_bytes + 64ull * B.n_docs + 64;
+  if (!c->sn_ws.ensure(B.slot_total + 64) || !c->sn_claim.ensure((size_t)B.n_docs + 16) || !c->sn_pay.ensure(16)) return YGM_ENOMEM;
+  HIPCHK(hipMemsetAsync(c->sn_pay.p, 0, 16, B.s));
+  uint64_t pay[2] = {0, 0};
+  for (int again = 0; again < 2 && pay[1] < B.n_docs; again++) {
+    if (launch(again)) return YGM_EDEVICE;
+    const int e = read_u64_pair(c, B.s, c->sn_pay.as<uint64_t>(), pay);
+    if (e) return e;
+    if (again == 0) B.flat_first = pay[1];
+  }
+  B.flat_pay = pay[0]; B.flat_docs = pay[1];
+  return YGM_OK;
+}
+// plan: the count and scan launches (cont: the containment's), one read of the scanned total, c->sn_ws grown to hold
+// the workspaces after the slot region, which is kept
+static int ws_plan(WsBatch& B, const uint8_t* d_arena, const uint64_t* d_off, uint32_t flags, bool cont = false) {
+  ygm_ctx* c = B.c;
+  if (cont ? ygm_k_launch_cont_plan(d_arena, d_off, B.n_docs, flags, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), B.s)
+           : ygm_k_launch_snap_plan(d_arena, d_off, B.n_docs, flags, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), B.claim(), B.s))
+    return YGM_EDEVICE;
+  int e = 0;
+  if (B.n_docs) B.total = read_u64(c, B.s, c->sn_off.as<uint64_t>() + B.n_docs, e);
+  if (e) return e;
+  return c->sn_ws.ensure(B.slot_total + B.total + 64, B.slot_total, B.s) ? YGM_OK : YGM_ENOMEM;
+}
+// finish: event e1 and the wait for it, the call's statistics, the result over `data`
+static int ws_finish(WsBatch& B, uint64_t in_bytes, uint8_t* data, uint64_t data_bytes, uint64_t payload, ygm_device_result* out) {
+  ygm_ctx* c = B.c;
+  HIPCHK(hipEventRecord(c->e1, B.s));
+  HIPCHK(hipEventSynchronize(c->e1));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
+  c->stats.calls++; c->stats.docs += B.n_docs; c->stats.bytes_in += in_bytes; c->stats.bytes_out += payload;
+  out->data = data; out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
+  out->status = c->status.as<int32_t>(); out->data_bytes = data_bytes; out->payload_bytes = payload;
+  return YGM_OK;
+}
+
 // the snapshot batch; xf: YGM_F_SNAP_STATE (contains) for states that leave pending parts
 // leave: when non-null, documents left pending are not resolved: their count goes there (list c->sn_pend, statuses
 // ST_PEND, their PendHdr layouts at out_off)
@@ -611,76 +705,39 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
                         const uint8_t* d_opt = nullptr) {
   if (leave) *leave = 0;
   const uint32_t fl = c->flags | xf;
-  const uint32_t nb = (n_docs + 1 + 255) / 256;
-  if (!c->sn_cnt.ensure(16ull * n_docs + 16) || !c->sn_off.ensure(8ull * n_docs + 16) || !c->sn_bs.ensure(8ull * nb + 16) ||
-      !c->out_off.ensure(8ull * n_docs + 8) || !c->out_len.ensure(8ull * n_docs + 8) || !c->status.ensure(4ull * n_docs + 4))
-    return YGM_ENOMEM;
-  void* meta = c->meta_slot(2);
-  HIPCHK(hipMemsetAsync(meta, 0, sizeof(Meta), s));
-  HIPCHK(hipEventRecord(c->e0, s));
-  // tier 1: k_snap_text (flat text; input + workspace in LDS) into per-document slots; the documents it leaves go to
-  // the count / scan / k_snap path, whose workspaces follow the slot region
-  // (the flat-text tier writes updates only: a take batch, YGM_F_SNAP_VERSION, goes to k_snap whole)
-  const bool lds = n_docs && !(xf & YGM_F_SNAP_VERSION) && getenv("YGM_SNAP_NOLDS") == nullptr;
-  const uint64_t slot_total = lds ? 2 * arena_bytes + 64ull * n_docs + 64 : 0;
-  uint64_t lds_pay[2] = {0, 0};
-  uint64_t text_first = 0;   // (YGM_TIER_COUNTS: what launch 0 took)
-  if (lds) {
-    if (!c->sn_ws.ensure(slot_total + 64) || !c->sn_claim.ensure((size_t)n_docs + 16) || !c->sn_pay.ensure(16)) return YGM_ENOMEM;
-    HIPCHK(hipMemsetAsync(c->sn_pay.p, 0, 16, s));
-    for (int again = 0; again < 2 && lds_pay[1] < n_docs; again++) {   // 6 KiB per document, then 24 KiB for what it left
-      if (ygm_k_launch_snap_text(d_arena, d_doc_off, n_docs, fl, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
-                                 c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(), c->sn_pay.as<unsigned long long>(), again, slot_total, d_opt, s))
-        return YGM_EDEVICE;
-      HIPCHK(hipMemcpyAsync(c->h_meta, c->sn_pay.p, 16, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      memcpy(lds_pay, c->h_meta, 16);
-      if (again == 0) text_first = lds_pay[1];
-    }
-  }
-  uint64_t total = 0;   // workspace bytes: one read of the scanned total
+  WsBatch B;
+  int e = ws_begin(c, s, n_docs, B);
+  if (e) return e;
+  // tier 1: k_snap_text (the flat-text tier writes updates only: a take batch, YGM_F_SNAP_VERSION, goes to k_snap whole)
+  if (!(xf & YGM_F_SNAP_VERSION) && (e = ws_flat(B, arena_bytes, [&](int again) {
+        return ygm_k_launch_snap_text(d_arena, d_doc_off, n_docs, fl, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
+                                      c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(), c->sn_pay.as<unsigned long long>(), again,
+                                      B.slot_total, d_opt, s);
+      })))
+    return e;
   uint64_t total_out = 0;   // the output region's extent when pending documents' merged bytes follow the workspaces
   Meta m;
   memset(&m, 0, sizeof(m));
-  if (!lds || lds_pay[1] < n_docs) {
-    const uint8_t* claim = lds ? c->sn_claim.as<uint8_t>() : nullptr;
-    if (ygm_k_launch_snap_plan(d_arena, d_doc_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), claim, s))
-      return YGM_EDEVICE;
-    if (n_docs) {
-      HIPCHK(hipMemcpyAsync(c->h_meta, c->sn_off.as<uint64_t>() + n_docs, 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      memcpy(&total, c->h_meta, 8);
-    }
-    if (!c->sn_ws.ensure(slot_total + total + 64, slot_total, s) || !c->sn_pend.ensure(4ull * n_docs + 16)) return YGM_ENOMEM;
+  if (!B.slot_total || B.flat_docs < n_docs) {   // the count / scan / k_snap path
+    if ((e = ws_plan(B, d_arena, d_doc_off, fl))) return e;
+    if (!c->sn_pend.ensure(4ull * n_docs + 16)) return YGM_ENOMEM;
     if (ygm_k_launch_snap_w(d_arena, d_doc_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_ws.as<uint8_t>(),
-                            c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                            (unsigned long long*)((uint8_t*)meta + offsetof(Meta, payload)), claim, slot_total, c->sn_pend.as<uint32_t>(),
-                            (unsigned int*)((uint8_t*)meta + offsetof(Meta, fb_count)), dpw, d_opt, s))
+                            c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.payload(), B.claim(), B.slot_total,
+                            c->sn_pend.as<uint32_t>(), B.fb_count(), dpw, d_opt, s))
       return YGM_EDEVICE;
-    int e = read_meta(c, s, m, meta);
-    if (e) return e;
+    if ((e = read_meta(c, s, m, B.meta))) return e;
     if (m.fb_count && leave) *leave = m.fb_count;
-    else if (m.fb_count && (e = snap_resolve_pending(c, s, m.fb_count, slot_total + total, total_out, m.payload))) return e;
-    HIPCHK(hipEventRecord(c->e1, s));
-    HIPCHK(hipEventSynchronize(c->e1));
-  } else {
-    HIPCHK(hipEventRecord(c->e1, s));
-    HIPCHK(hipEventSynchronize(c->e1));
+    else if (m.fb_count && (e = snap_resolve_pending(c, s, m.fb_count, B.slot_total + B.total, total_out, m.payload))) return e;
   }
-  m.payload += lds_pay[0];
+  m.payload += B.flat_pay;
   // YGM_TIER_COUNTS (testing knob): the tier that finished the call's documents, one stderr line (general: the count /
   // scan / k_snap path, the documents it left pending among them)
   if (getenv("YGM_TIER_COUNTS"))
     fprintf(stderr, "ygm snapshot tiers: docs %u text_first %llu text_second %llu general %llu pending %u\n", n_docs,
-            (unsigned long long)text_first, (unsigned long long)(lds_pay[1] - text_first), (unsigned long long)(n_docs - lds_pay[1]),
+            (unsigned long long)B.flat_first, (unsigned long long)(B.flat_docs - B.flat_first), (unsigned long long)(n_docs - B.flat_docs),
             m.fb_count);
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
-  c->stats.calls++; c->stats.docs += n_docs; c->stats.bytes_in += arena_bytes; c->stats.bytes_out += m.payload;
   c->stats.docs_snapshot += n_docs;
-  out->data = c->sn_ws.as<uint8_t>(); out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
-  out->status = c->status.as<int32_t>(); out->data_bytes = total_out ? total_out : slot_total + total; out->payload_bytes = m.payload;
-  return YGM_OK;
+  return ws_finish(B, arena_bytes, c->sn_ws.as<uint8_t>(), total_out ? total_out : B.slot_total + B.total, m.payload, out);
 }
 int ygm_snapshot_opts_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off,
                                 const uint8_t* d_doc_opt, uint32_t n_docs, void* stream, ygm_device_result* out) {
@@ -692,126 +749,76 @@ int ygm_snapshot_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_by
                            void* stream, ygm_device_result* out) {
   return ygm_snapshot_opts_v1_device(c, d_arena, arena_bytes, d_doc_off, nullptr, n_docs, stream, out);
 }
-// ---- plain text of stored documents: the snapshot batch's tiers with another last stage.  k_text_flat at k_snap_text's
-// two LDS sizes into the per-document slots, then the count / scan launches and k_text over the workspaces that follow
-// the slot region, for the documents the flat tier left.  Nothing is left pending: a state with pending parts is read
-// through its integrated part.  The context's snapshot buffers serve (one batch in flight per context).
+// ---- plain text of stored documents: the snapshot batch's tiers with another last stage.  k_text_flat as the flat
+// tier, then k_text over the workspaces for the documents it left.  Nothing is left pending: a state with pending
+// parts is read through its integrated part.
 int ygm_text_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, const uint8_t* d_names,
                        const uint64_t* d_name_off, uint32_t mode, uint32_t n_docs, void* stream, ygm_device_result* out) {
   if (!c || !out || mode > YGM_TEXT_DEEP || (n_docs && (!d_state_off || !d_name_off))) return YGM_EINVAL;
   (void)hipSetDevice(c->device);
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const uint32_t fl = c->flags;
-  const uint32_t nb = (n_docs + 1 + 255) / 256;
-  if (!c->sn_cnt.ensure(16ull * n_docs + 16) || !c->sn_off.ensure(8ull * n_docs + 16) || !c->sn_bs.ensure(8ull * nb + 16) ||
-      !c->out_off.ensure(8ull * n_docs + 8) || !c->out_len.ensure(8ull * n_docs + 8) || !c->status.ensure(4ull * n_docs + 4))
-    return YGM_ENOMEM;
-  void* meta = c->meta_slot(2);
-  HIPCHK(hipMemsetAsync(meta, 0, sizeof(Meta), s));
-  HIPCHK(hipEventRecord(c->e0, s));
-  const bool lds = n_docs && getenv("YGM_SNAP_NOLDS") == nullptr;
-  const uint64_t slot_total = lds ? 2 * states_bytes + 64ull * n_docs + 64 : 0;
-  uint64_t lds_pay[2] = {0, 0};
-  uint64_t flat_first = 0;
-  if (lds) {
-    if (!c->sn_ws.ensure(slot_total + 64) || !c->sn_claim.ensure((size_t)n_docs + 16) || !c->sn_pay.ensure(16)) return YGM_ENOMEM;
-    HIPCHK(hipMemsetAsync(c->sn_pay.p, 0, 16, s));
-    for (int again = 0; again < 2 && lds_pay[1] < n_docs; again++) {
-      if (ygm_k_launch_text_flat(d_states, d_state_off, d_names, d_name_off, n_docs, fl, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(),
-                                 c->out_len.as<uint64_t>(), c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(),
-                                 c->sn_pay.as<unsigned long long>(), again, slot_total, s))
-        return YGM_EDEVICE;
-      c->stats.host_syncs++;
-      HIPCHK(hipMemcpyAsync(c->h_meta, c->sn_pay.p, 16, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      memcpy(lds_pay, c->h_meta, 16);
-      if (again == 0) flat_first = lds_pay[1];
-    }
-  }
-  uint64_t total = 0;
+  WsBatch B;
+  int e = ws_begin(c, s, n_docs, B);
+  if (e || (e = ws_flat(B, states_bytes, [&](int again) {
+        return ygm_k_launch_text_flat(d_states, d_state_off, d_names, d_name_off, n_docs, fl, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(),
+                                      c->out_len.as<uint64_t>(), c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(),
+                                      c->sn_pay.as<unsigned long long>(), again, B.slot_total, s);
+      })))
+    return e;
   Meta m;
   memset(&m, 0, sizeof(m));
-  if (n_docs && (!lds || lds_pay[1] < n_docs)) {
-    const uint8_t* claim = lds ? c->sn_claim.as<uint8_t>() : nullptr;
-    if (ygm_k_launch_snap_plan(d_states, d_state_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), claim, s))
-      return YGM_EDEVICE;
-    int e = 0;
-    total = read_u64(c, s, c->sn_off.as<uint64_t>() + n_docs, e);
-    if (e) return e;
-    if (!c->sn_ws.ensure(slot_total + total + 64, slot_total, s)) return YGM_ENOMEM;
+  if (n_docs && (!B.slot_total || B.flat_docs < n_docs)) {
+    if ((e = ws_plan(B, d_states, d_state_off, fl))) return e;
     if (ygm_k_launch_text(d_states, d_state_off, d_names, d_name_off, n_docs, fl, mode, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
-                          c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                          (unsigned long long*)((uint8_t*)meta + offsetof(Meta, payload)), claim, slot_total, s))
+                          c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.payload(),
+                          B.claim(), B.slot_total, s))
       return YGM_EDEVICE;
-    if ((e = read_meta(c, s, m, meta))) return e;
+    if ((e = read_meta(c, s, m, B.meta))) return e;
   }
-  HIPCHK(hipEventRecord(c->e1, s));
-  HIPCHK(hipEventSynchronize(c->e1));
-  m.payload += lds_pay[0];
   if (getenv("YGM_TIER_COUNTS"))   // (testing knob, as the snapshot's line: the tier that finished the call's documents)
-    fprintf(stderr, "ygm text tiers: docs %u flat_first %llu flat_second %llu general %llu\n", n_docs, (unsigned long long)flat_first,
-            (unsigned long long)(lds_pay[1] - flat_first), (unsigned long long)(n_docs - lds_pay[1]));
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
-  c->stats.calls++; c->stats.docs += n_docs; c->stats.bytes_in += states_bytes; c->stats.bytes_out += m.payload;
-  out->data = c->sn_ws.as<uint8_t>(); out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
-  out->status = c->status.as<int32_t>(); out->data_bytes = slot_total + total; out->payload_bytes = m.payload;
-  return YGM_OK;
+    fprintf(stderr, "ygm text tiers: docs %u flat_first %llu flat_second %llu general %llu\n", n_docs, (unsigned long long)B.flat_first,
+            (unsigned long long)(B.flat_docs - B.flat_first), (unsigned long long)(n_docs - B.flat_docs));
+  return ws_finish(B, states_bytes, c->sn_ws.as<uint8_t>(), B.slot_total + B.total, m.payload + B.flat_pay, out);
 }
-// ---- stored documents as ProseMirror JSON: the count / scan launches and k_json over the workspaces (no flat tier:
-// its envelope holds no nested types).  A JSON is not bounded by its workspace's output region: k_json lists the
-// documents whose JSON did not fit, with the lengths they need and their places in an overflow region claimed from
-// the launch's cursor; only then the buffer grows by that region (the workspaces, which hold the other documents'
-// outputs, are kept) and k_json runs again for the listed documents alone -- one more host wait.
+// ---- stored documents as ProseMirror JSON: k_json over the workspaces (no flat tier: its envelope holds no nested
+// types).  A JSON is not bounded by its workspace's output region: k_json lists the documents whose JSON did not fit,
+// with the lengths they need and their places in an overflow region claimed from the launch's cursor; only then the
+// buffer grows by that region (the workspaces, which hold the other documents' outputs, are kept) and k_json runs
+// again for the listed documents alone -- one more host wait.
 int ygm_json_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, const uint8_t* d_names,
                        const uint64_t* d_name_off, uint32_t kind, uint32_t n_docs, void* stream, ygm_device_result* out) {
   if (!c || !out || kind != YGM_JSON_PROSEMIRROR || (n_docs && (!d_state_off || !d_name_off))) return YGM_EINVAL;
   (void)hipSetDevice(c->device);
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const uint32_t fl = c->flags;
-  const uint32_t nb = (n_docs + 1 + 255) / 256;
-  if (!c->sn_cnt.ensure(16ull * n_docs + 16) || !c->sn_off.ensure(8ull * n_docs + 16) || !c->sn_bs.ensure(8ull * nb + 16) ||
-      !c->out_off.ensure(8ull * n_docs + 8) || !c->out_len.ensure(8ull * n_docs + 8) || !c->status.ensure(4ull * n_docs + 4) ||
-      !c->sn_pend.ensure(4ull * n_docs + 16))
-    return YGM_ENOMEM;
-  void* meta = c->meta_slot(2);
-  HIPCHK(hipMemsetAsync(meta, 0, sizeof(Meta), s));
-  HIPCHK(hipEventRecord(c->e0, s));
-  uint64_t total = 0, ovf = 0;
+  WsBatch B;
+  int e = ws_begin(c, s, n_docs, B);
+  if (e) return e;
+  if (!c->sn_pend.ensure(4ull * n_docs + 16)) return YGM_ENOMEM;
+  uint64_t ovf = 0;
   uint32_t reran = 0;
   Meta m;
   memset(&m, 0, sizeof(m));
   if (n_docs) {
-    if (ygm_k_launch_snap_plan(d_states, d_state_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), nullptr, s))
-      return YGM_EDEVICE;
-    int e = 0;
-    total = read_u64(c, s, c->sn_off.as<uint64_t>() + n_docs, e);
-    if (e) return e;
-    if (!c->sn_ws.ensure(total + 64)) return YGM_ENOMEM;
+    if ((e = ws_plan(B, d_states, d_state_off, fl))) return e;
     auto launch = [&](uint32_t n_list, int again) {
       return ygm_k_launch_json(d_states, d_state_off, d_names, d_name_off, n_docs, fl, kind, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
-                               c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), meta, 0,
-                               total, c->sn_pend.as<uint32_t>(), n_list, again, s);
+                               c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.meta, 0,
+                               B.total, c->sn_pend.as<uint32_t>(), n_list, again, s);
     };
     if (launch(0, 0)) return YGM_EDEVICE;
-    if ((e = read_meta(c, s, m, meta))) return e;
+    if ((e = read_meta(c, s, m, B.meta))) return e;
     if (m.fb_count) {   // the documents whose JSON did not fit: sized from the recorded lengths, run again
       reran = m.fb_count; ovf = m.cursor;
-      if (!c->sn_ws.ensure(total + ovf + 64, total, s)) return YGM_ENOMEM;
+      if (!c->sn_ws.ensure(B.total + ovf + 64, B.total, s)) return YGM_ENOMEM;
       if (launch(reran, 1)) return YGM_EDEVICE;
-      if ((e = read_meta(c, s, m, meta))) return e;
+      if ((e = read_meta(c, s, m, B.meta))) return e;
     }
   }
-  HIPCHK(hipEventRecord(c->e1, s));
-  HIPCHK(hipEventSynchronize(c->e1));
   if (getenv("YGM_TIER_COUNTS"))   // (testing knob, as the text's line)
     fprintf(stderr, "ygm json tiers: docs %u general %u overflow %u overflow_bytes %llu\n", n_docs, n_docs, reran, (unsigned long long)ovf);
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
-  c->stats.calls++; c->stats.docs += n_docs; c->stats.bytes_in += states_bytes; c->stats.bytes_out += m.payload;
-  out->data = c->sn_ws.as<uint8_t>(); out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
-  out->status = c->status.as<int32_t>(); out->data_bytes = total + ovf; out->payload_bytes = m.payload;
-  return YGM_OK;
+  return ws_finish(B, states_bytes, c->sn_ws.as<uint8_t>(), B.total + ovf, m.payload, out);
 }
 // a snapshot batch's outputs packed into one arena on the device (k_pack_*: offsets n + 1, the total at [n]) with its
 // statuses, for kernels that read documents by offsets (step2's diff, contains)
@@ -839,55 +846,61 @@ int ygm_version_take_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t sta
   return snapshot_dev(c, d_states, states_bytes, d_state_off, n_docs, stream ? (hipStream_t)stream : c->stream, out,
                       YGM_F_SNAP_STATE | YGM_F_SNAP_VERSION);
 }
-// restore: (1) the states' no-GC snapshots in their Y.snapshot view, (2) packed, (3) cut at the versions' clocks with
-// the versions' delete sets appended (k_ver_cut, per-document slots), (4) packed again, (5) snapshotted into the new
-// documents (restored_opt); the statuses of (1) and (3) carried into the result
+// the restores' tail over n cut units (documents, or asks): (3) the cut, launched by `cut` into per-unit slots of
+// c->vr_out (`total` bytes), (4) packed, padded, (5) snapshotted into the new documents (restored_opt); the cut's
+// statuses carried into the result.  cut_ms: the cut's HIP-event time
+extern "C++" template <class C>
+static int restore_tail(ygm_ctx* c, hipStream_t s, uint32_t n, uint64_t total, C cut, const uint8_t* d_restored_opt, ygm_device_result* out,
+                        float& cut_ms) {
+  const uint32_t nb = (n + 255) / 256;
+  if (!c->vr_out.ensure(total + 64) || !c->vr_off.ensure(8ull * n + 8) || !c->vr_len.ensure(8ull * n + 8) || !c->vr_st.ensure(4ull * n + 4) ||
+      !c->vr_pk.ensure(total + 64) || !c->vr_pkoff.ensure(8ull * n + 16) || !c->s2_bsum.ensure(8ull * nb + 16))
+    return YGM_ENOMEM;
+  HIPCHK(hipEventRecord(c->e2, s));
+  if (cut()) return YGM_EDEVICE;
+  HIPCHK(hipEventRecord(c->e3, s));
+  uint64_t xb = 0;
+  int e = 0;
+  if (n) {
+    if (ygm_k_launch_pack(c->vr_out.as<uint8_t>(), c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), n,
+                          c->s2_bsum.as<uint64_t>(), c->vr_pk.as<uint8_t>(), c->vr_pkoff.as<uint64_t>(), s))
+      return YGM_EDEVICE;
+    HIPCHK(hipMemcpyAsync(c->vr_pkoff.as<uint64_t>() + n, c->s2_bsum.as<uint64_t>() + nb, 8, hipMemcpyDeviceToDevice, s));
+    xb = read_u64(c, s, c->vr_pkoff.as<uint64_t>() + n, e);
+    if (e) return e;
+    if (xb > total) return YGM_EDEVICE;
+  } else HIPCHK(hipMemsetAsync(c->vr_pkoff.p, 0, 8, s));
+  HIPCHK(hipMemsetAsync(c->vr_pk.as<uint8_t>() + xb, 0, 64, s));   // (the snapshot kernels' tail padding)
+  cut_ms = 0;
+  if (hipEventElapsedTime(&cut_ms, c->e2, c->e3) == hipSuccess) c->stats.kernel_ms += cut_ms;
+  if ((e = snapshot_dev(c, c->vr_pk.as<uint8_t>(), xb, c->vr_pkoff.as<uint64_t>(), n, s, out, 0, nullptr, 0, d_restored_opt))) return e;
+  if (n && ygm_k_launch_v2_status(c->vr_st.as<int32_t>(), n, out->status, out->len, s)) return YGM_EDEVICE;
+  return YGM_OK;
+}
+// restore: (1) the states' no-GC snapshots in their Y.snapshot view, (2) packed, then restore_tail over the documents
+// (k_ver_cut at the versions' clocks with the versions' delete sets appended); the statuses of (1) and (3) carried
 int ygm_version_restore_v1_device(ygm_ctx* c, const uint8_t* d_states, const uint64_t* d_state_off, const uint8_t* d_versions,
                                   const uint64_t* d_version_off, const uint8_t* d_restored_opt, uint32_t n_docs, void* stream,
                                   ygm_device_result* out) {
   if (!c || !out || ((uintptr_t)d_versions & 15u)) return YGM_EINVAL;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   (void)hipSetDevice(c->device);
-  uint64_t sb = 0, vb = 0;
-  if (n_docs) {
-    c->stats.host_syncs++;
-    HIPCHK(hipMemcpyAsync(c->h_meta, d_state_off + n_docs, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync((uint64_t*)c->h_meta + 1, d_version_off + n_docs, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(&sb, c->h_meta, 8); memcpy(&vb, (uint64_t*)c->h_meta + 1, 8);
-  }
+  uint64_t sv[2] = {0, 0};   // the states' bytes, the versions' bytes
+  int e = n_docs ? read_u64s(c, s, {d_state_off + n_docs, d_version_off + n_docs}, sv) : 0;
+  if (e) return e;
   ygm_device_result r1;
   const double k0 = c->stats.kernel_ms;
-  int e = snapshot_dev(c, d_states, sb, d_state_off, n_docs, s, &r1, YGM_F_SNAP_STATE | YGM_F_SNAP_NOGC);
+  e = snapshot_dev(c, d_states, sv[0], d_state_off, n_docs, s, &r1, YGM_F_SNAP_STATE | YGM_F_SNAP_NOGC);
   if (e || (e = pack_snapshots(c, s, r1, n_docs))) return e;
   const double k1 = c->stats.kernel_ms;
-  const uint64_t total = r1.payload_bytes + vb + 32ull * n_docs + 64;
-  const uint32_t nb = (n_docs + 255) / 256;
-  if (!c->vr_out.ensure(total + 64) || !c->vr_off.ensure(8ull * n_docs + 8) || !c->vr_len.ensure(8ull * n_docs + 8) ||
-      !c->vr_st.ensure(4ull * n_docs + 4) || !c->vr_pk.ensure(total + 64) || !c->vr_pkoff.ensure(8ull * n_docs + 16) ||
-      !c->s2_bsum.ensure(8ull * nb + 16))
-    return YGM_ENOMEM;
-  HIPCHK(hipEventRecord(c->e2, s));
-  if (ygm_k_launch_ver_cut(c->s2_data.as<uint8_t>(), c->s2_off.as<uint64_t>(), c->s2_st.as<int32_t>(), d_versions, d_version_off, n_docs,
-                           c->flags, c->vr_out.as<uint8_t>(), total, c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(),
-                           c->vr_st.as<int32_t>(), s))
-    return YGM_EDEVICE;
-  HIPCHK(hipEventRecord(c->e3, s));
-  uint64_t xb = 0;
-  if (n_docs) {
-    if (ygm_k_launch_pack(c->vr_out.as<uint8_t>(), c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), n_docs,
-                          c->s2_bsum.as<uint64_t>(), c->vr_pk.as<uint8_t>(), c->vr_pkoff.as<uint64_t>(), s))
-      return YGM_EDEVICE;
-    HIPCHK(hipMemcpyAsync(c->vr_pkoff.as<uint64_t>() + n_docs, c->s2_bsum.as<uint64_t>() + nb, 8, hipMemcpyDeviceToDevice, s));
-    xb = read_u64(c, s, c->vr_pkoff.as<uint64_t>() + n_docs, e);
-    if (e) return e;
-    if (xb > total) return YGM_EDEVICE;
-  } else HIPCHK(hipMemsetAsync(c->vr_pkoff.p, 0, 8, s));
-  HIPCHK(hipMemsetAsync(c->vr_pk.as<uint8_t>() + xb, 0, 64, s));   // (the snapshot kernels' tail padding)
+  const uint64_t total = r1.payload_bytes + sv[1] + 32ull * n_docs + 64;
   float ms = 0;
-  if (hipEventElapsedTime(&ms, c->e2, c->e3) == hipSuccess) c->stats.kernel_ms += ms;
-  if ((e = snapshot_dev(c, c->vr_pk.as<uint8_t>(), xb, c->vr_pkoff.as<uint64_t>(), n_docs, s, out, 0, nullptr, 0, d_restored_opt))) return e;
-  if (n_docs && ygm_k_launch_v2_status(c->vr_st.as<int32_t>(), n_docs, out->status, out->len, s)) return YGM_EDEVICE;
+  e = restore_tail(c, s, n_docs, total, [&] {
+    return ygm_k_launch_ver_cut(c->s2_data.as<uint8_t>(), c->s2_off.as<uint64_t>(), c->s2_st.as<int32_t>(), d_versions, d_version_off, n_docs,
+                                c->flags, c->vr_out.as<uint8_t>(), total, c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(),
+                                c->vr_st.as<int32_t>(), s);
+  }, d_restored_opt, out, ms);
+  if (e) return e;
   HIPCHK(hipStreamSynchronize(s));
   if (getenv("YGM_VERSION_TIMES"))   // (tools/version_probe.py: the three stages' HIP-event times)
     fprintf(stderr, "ygm version restore: docs %u snapshot_nogc_ms %.3f cut_ms %.3f snapshot_restored_ms %.3f\n", n_docs, k1 - k0, (double)ms,
@@ -908,8 +921,8 @@ static uint32_t shared_snap_dpw(uint32_t n_states, uint32_t n_asks) {
 }
 // restore of many versions per state: (1) and (2) over the n_states states, each snapshotted once; the ask plan over the
 // packed snapshots' offsets (the checked state id per ask and the scan of the asks' snapshot lengths, what sizes the
-// cut's slots); (3) the gather cut over the n_asks asks, reading the packed snapshots in place; (4), (5) over the asks
-// with their option bytes.  The cut carries a refused id's YGM_EINVAL and a state's refusal to the ask
+// cut's slots); restore_tail over the n_asks asks with the gather cut, which reads the packed snapshots in place, and
+// the asks' option bytes.  The cut carries a refused id's YGM_EINVAL and a state's refusal to the ask
 int ygm_version_restore_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off,
                                          uint32_t n_states, const uint8_t* d_versions, const uint64_t* d_version_off,
                                          const uint32_t* d_ask_state, const uint8_t* d_restored_opt, uint32_t n_asks, void* stream,
@@ -925,44 +938,18 @@ int ygm_version_restore_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, ui
   if (e || (e = pack_snapshots(c, s, r1, n_states))) return e;
   const double k1 = c->stats.kernel_ms;
   if ((e = ask_plan(c, s, c->s2_off.as<uint64_t>(), n_states, d_ask_state, n_asks))) return e;
-  uint64_t ab = 0, vb = 0;   // the asks' snapshot bytes, the versions' bytes: the one read that sizes the cut's slots
-  if (n_asks) {
-    c->stats.host_syncs++;
-    HIPCHK(hipMemcpyAsync(c->h_meta, c->ask_base.as<uint64_t>() + n_asks, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync((uint64_t*)c->h_meta + 1, d_version_off + n_asks, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(&ab, c->h_meta, 8); memcpy(&vb, (uint64_t*)c->h_meta + 1, 8);
-  }
-  const uint64_t total = ab + vb + 32ull * n_asks + 64;
-  const uint32_t nb = (n_asks + 255) / 256;
-  if (!c->vr_out.ensure(total + 64) || !c->vr_off.ensure(8ull * n_asks + 8) || !c->vr_len.ensure(8ull * n_asks + 8) ||
-      !c->vr_st.ensure(4ull * n_asks + 4) || !c->vr_pk.ensure(total + 64) || !c->vr_pkoff.ensure(8ull * n_asks + 16) ||
-      !c->s2_bsum.ensure(8ull * nb + 16))
-    return YGM_ENOMEM;
-  HIPCHK(hipEventRecord(c->e2, s));
-  if (ygm_k_launch_ver_cut_gather(c->s2_data.as<uint8_t>(), c->s2_off.as<uint64_t>(), c->s2_st.as<int32_t>(), c->ask_ix.as<uint32_t>(),
-                                  c->ask_base.as<uint64_t>(), d_versions, d_version_off, n_asks, c->flags, c->vr_out.as<uint8_t>(), total,
-                                  c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), s))
-    return YGM_EDEVICE;
-  HIPCHK(hipEventRecord(c->e3, s));
-  uint64_t xb = 0;
-  if (n_asks) {
-    if (ygm_k_launch_pack(c->vr_out.as<uint8_t>(), c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), n_asks,
-                          c->s2_bsum.as<uint64_t>(), c->vr_pk.as<uint8_t>(), c->vr_pkoff.as<uint64_t>(), s))
-      return YGM_EDEVICE;
-    HIPCHK(hipMemcpyAsync(c->vr_pkoff.as<uint64_t>() + n_asks, c->s2_bsum.as<uint64_t>() + nb, 8, hipMemcpyDeviceToDevice, s));
-    xb = read_u64(c, s, c->vr_pkoff.as<uint64_t>() + n_asks, e);
-    if (e) return e;
-    if (xb > total) return YGM_EDEVICE;
-  } else HIPCHK(hipMemsetAsync(c->vr_pkoff.p, 0, 8, s));
-  HIPCHK(hipMemsetAsync(c->vr_pk.as<uint8_t>() + xb, 0, 64, s));   // (the snapshot kernels' tail padding)
+  uint64_t av[2] = {0, 0};   // the asks' snapshot bytes, the versions' bytes: the one read that sizes the cut's slots
+  if (n_asks && (e = read_u64s(c, s, {c->ask_base.as<uint64_t>() + n_asks, d_version_off + n_asks}, av))) return e;
+  const uint64_t total = av[0] + av[1] + 32ull * n_asks + 64;
   float ms = 0;
-  if (hipEventElapsedTime(&ms, c->e2, c->e3) == hipSuccess) c->stats.kernel_ms += ms;
-  if ((e = snapshot_dev(c, c->vr_pk.as<uint8_t>(), xb, c->vr_pkoff.as<uint64_t>(), n_asks, s, out, 0, nullptr, 0, d_restored_opt))) return e;
-  // the carries: the cut's status over the restored document's, then (as the other shared forms) id and state to ask
-  if (n_asks && (ygm_k_launch_v2_status(c->vr_st.as<int32_t>(), n_asks, out->status, out->len, s) ||
-                 ygm_k_launch_ask_status(c->ask_ix.as<uint32_t>(), n_asks, c->s2_st.as<int32_t>(), out->status, out->len, s)))
-    return YGM_EDEVICE;
+  e = restore_tail(c, s, n_asks, total, [&] {
+    return ygm_k_launch_ver_cut_gather(c->s2_data.as<uint8_t>(), c->s2_off.as<uint64_t>(), c->s2_st.as<int32_t>(), c->ask_ix.as<uint32_t>(),
+                                       c->ask_base.as<uint64_t>(), d_versions, d_version_off, n_asks, c->flags, c->vr_out.as<uint8_t>(), total,
+                                       c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), s);
+  }, d_restored_opt, out, ms);
+  if (e) return e;
+  // the carries: after the cut's status (restore_tail), as the other shared forms, id and state to ask
+  if (n_asks && ygm_k_launch_ask_status(c->ask_ix.as<uint32_t>(), n_asks, c->s2_st.as<int32_t>(), out->status, out->len, s)) return YGM_EDEVICE;
   HIPCHK(hipStreamSynchronize(s));
   if (getenv("YGM_VERSION_TIMES"))   // (tools/version_probe.py: the three stages' HIP-event times)
     fprintf(stderr, "ygm version restore shared: states %u asks %u snapshot_nogc_ms %.3f cut_ms %.3f snapshot_restored_ms %.3f\n", n_states,
@@ -978,51 +965,37 @@ int ygm_contains_v1_device(ygm_ctx* c, const uint8_t* d_states_in, const uint64_
   if (!c || !out) return YGM_EINVAL;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   (void)hipSetDevice(c->device);
-  uint64_t states_bytes = 0;
-  if (n_docs) {
-    c->stats.host_syncs++;
-    HIPCHK(hipMemcpyAsync(c->h_meta, d_state_off_in + n_docs, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(&states_bytes, c->h_meta, 8);
-  }
+  int e = 0;
+  const uint64_t states_bytes = n_docs ? read_u64(c, s, d_state_off_in + n_docs, e) : 0;
+  if (e) return e;
   ygm_device_result r1;
-  int e0 = snapshot_dev(c, d_states_in, states_bytes, d_state_off_in, n_docs, s, &r1, YGM_F_SNAP_STATE);
-  if (e0 || (e0 = pack_snapshots(c, s, r1, n_docs))) return e0;
+  e = snapshot_dev(c, d_states_in, states_bytes, d_state_off_in, n_docs, s, &r1, YGM_F_SNAP_STATE);
+  if (e || (e = pack_snapshots(c, s, r1, n_docs))) return e;
   const uint8_t* d_states = c->s2_data.as<uint8_t>();
   const uint64_t* d_state_off = c->s2_off.as<uint64_t>();
-  const uint32_t nb = (n_docs + 1 + 255) / 256;
-  if (!c->sn_off.ensure(8ull * n_docs + 16) || !c->sn_bs.ensure(8ull * nb + 16) || !c->out.ensure((uint64_t)n_docs + 64) ||
-      !c->out_off.ensure(8ull * n_docs + 8) || !c->out_len.ensure(8ull * n_docs + 8) || !c->status.ensure(4ull * n_docs + 4))
-    return YGM_ENOMEM;
-  HIPCHK(hipEventRecord(c->e0, s));
-  if (ygm_k_launch_cont_plan(d_states, d_state_off, n_docs, c->flags, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), s)) return YGM_EDEVICE;
-  uint64_t total = 0;
-  if (n_docs) {
-    HIPCHK(hipMemcpyAsync(c->h_meta, c->sn_off.as<uint64_t>() + n_docs, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(&total, c->h_meta, 8);
-  }
-  if (!c->sn_ws.ensure(total + 64)) return YGM_ENOMEM;
+  // a workspace batch of its own: k_cont_count as the count launch, the answers (a byte per document) in c->out
+  WsBatch B;
+  if ((e = ws_begin(c, s, n_docs, B))) return e;
+  if (!c->out.ensure((uint64_t)n_docs + 64)) return YGM_ENOMEM;
+  if ((e = ws_plan(B, d_states, d_state_off, c->flags, true))) return e;
   if (ygm_k_launch_cont(d_states, d_state_off, d_updates, d_update_off, n_docs, c->flags, c->sn_off.as<uint64_t>(), c->sn_ws.as<uint8_t>(),
                         c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), s))
     return YGM_EDEVICE;
   if (n_docs && ygm_k_launch_v2_status(c->s2_st.as<int32_t>(), n_docs, c->status.as<int32_t>(), c->out_len.as<uint64_t>(), s))
     return YGM_EDEVICE;
-  HIPCHK(hipEventRecord(c->e1, s));
-  HIPCHK(hipStreamSynchronize(s));
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
-  c->stats.calls++; c->stats.docs += n_docs;
-  out->data = c->out.as<uint8_t>(); out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
-  out->status = c->status.as<int32_t>(); out->data_bytes = n_docs; out->payload_bytes = n_docs;
+  if ((e = ws_finish(B, 0, c->out.as<uint8_t>(), n_docs, 0, out))) return e;   // (the call counts no bytes in or out)
+  out->payload_bytes = n_docs;
   return YGM_OK;
 }
 
 int ygm_diff_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_doc_off, const uint8_t* d_sv_arena,
                        const uint64_t* d_sv_off, uint32_t n_docs, void* stream, ygm_device_result* out) {
+  if (!c || !out) return YGM_EINVAL;
   // (the state-vector arena's extent is the last offset; its 16-byte window reads stay inside its padding)
-  uint64_t sv_end = 0;
-  if (n_docs && hipMemcpy(&sv_end, d_sv_off + n_docs, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
+  int e = 0;
+  (void)hipSetDevice(c->device);
+  const uint64_t sv_end = n_docs ? read_u64(c, stream ? (hipStream_t)stream : c->stream, d_sv_off + n_docs, e) : 0;
+  if (e) return e;
   return run_doc_kernel(c, DOC_DIFF, d_arena, arena_bytes, d_doc_off, d_sv_arena, sv_end, d_sv_off, n_docs, stream, out);
 }
 
@@ -1036,29 +1009,31 @@ int ygm_sv_from_update_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t ar
 // structs, sv)]) (Y@23300) -- the state part diffed keeping each struct's parentSub bit (an integrated item's write),
 // the pending structs by the plain diff (the lazy writer's), on two child contexts; the three merged on a third, and
 // appended to the step2 result (`out`, the diff kernels' output region) in the documents' places
-// split (before the main diff reuses the snapshot's out_off): parts and state vectors into c->pq_*; tot: their bytes
-static int step2_pending_split(ygm_ctx* c, hipStream_t s, uint32_t P, const uint8_t* d_sv_arena, const uint64_t* d_sv_off, uint64_t (&tot)[4]) {
+// split (before the main diff reuses the snapshot's out_off): parts and state vectors into c->pq_*; tot: their bytes.
+// list: the P pending documents, or (gather) the asks of pending states -- ask a's parts come from the workspace record
+// of its state c->ask_ix[a], its state vector from the ask
+static int step2_pending_split(ygm_ctx* c, hipStream_t s, uint32_t P, const uint32_t* list, bool gather, const uint8_t* d_sv_arena,
+                               const uint64_t* d_sv_off, uint64_t (&tot)[4]) {
   const uint64_t np = (uint64_t)P + 1;
   if (!c->pq_off.ensure(8ull * 4 * np + 16) || !c->pq_st.ensure(4ull * P + 16) || !c->pn_off.ensure(8ull * (3ull * P + 1) + 16) ||
       !c->pn_du.ensure(4ull * np + 16))
     return YGM_ENOMEM;
   uint64_t* offs = c->pq_off.as<uint64_t>();
-  if (ygm_k_launch_pend_split(c->sn_pend.as<uint32_t>(), P, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), d_sv_arena, d_sv_off, offs,
-                              nullptr, nullptr, nullptr, nullptr, 0, s))
-    return YGM_EDEVICE;
-  c->stats.host_syncs++;
-  for (int k = 0; k < 4; k++) HIPCHK(hipMemcpyAsync((uint64_t*)c->h_meta + k, offs + (uint64_t)k * np + P, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  memcpy(tot, c->h_meta, sizeof tot);
+  auto launch = [&](int pass, uint8_t* da, uint8_t* db, uint8_t* dc, uint8_t* dsv) {
+    return gather ? ygm_k_launch_pend_split_g(list, P, c->ask_ix.as<uint32_t>(), c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), d_sv_arena,
+                                              d_sv_off, offs, da, db, dc, dsv, pass, s)
+                  : ygm_k_launch_pend_split(list, P, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), d_sv_arena, d_sv_off, offs, da, db, dc,
+                                            dsv, pass, s);
+  };
+  if (launch(0, nullptr, nullptr, nullptr, nullptr)) return YGM_EDEVICE;
+  const int e = read_u64s(c, s, {offs + P, offs + np + P, offs + 2 * np + P, offs + 3 * np + P}, tot);
+  if (e) return e;
   DevBuf* part[4] = {&c->pq_a, &c->pq_b, &c->pq_c, &c->pq_s};
   for (int k = 0; k < 4; k++) {
     if (!part[k]->ensure(tot[k] + 64)) return YGM_ENOMEM;
     HIPCHK(hipMemsetAsync(part[k]->as<uint8_t>() + tot[k], 0, 64, s));   // (readable tail padding for the kernels)
   }
-  if (ygm_k_launch_pend_split(c->sn_pend.as<uint32_t>(), P, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), d_sv_arena, d_sv_off, offs,
-                              c->pq_a.as<uint8_t>(), c->pq_b.as<uint8_t>(), c->pq_c.as<uint8_t>(), c->pq_s.as<uint8_t>(), 1, s))
-    return YGM_EDEVICE;
-  return YGM_OK;
+  return launch(1, c->pq_a.as<uint8_t>(), c->pq_b.as<uint8_t>(), c->pq_c.as<uint8_t>(), c->pq_s.as<uint8_t>()) ? YGM_EDEVICE : YGM_OK;
 }
 // finish (after the main diff): the two diffs, the join, the merge, the places in `out`
 static int step2_pending_finish(ygm_ctx* c, hipStream_t s, uint32_t P, const uint64_t (&tot)[4], ygm_device_result* out,
@@ -1107,11 +1082,11 @@ int ygm_sync_step2_opts_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t 
   uint32_t P = 0;   // documents the snapshot leaves pending (their parts split off now, answered after the diff)
   uint64_t ptot[4] = {0, 0, 0, 0};
   int e = snapshot_dev(c, d_states, states_bytes, d_state_off, n_docs, s, &r1, 0, &P, 0, d_state_opt);
-  if (!e && P) e = step2_pending_split(c, s, P, d_sv_arena, d_sv_off, ptot);
+  if (!e && P) e = step2_pending_split(c, s, P, c->sn_pend.as<uint32_t>(), false, d_sv_arena, d_sv_off, ptot);
   if (dbg) fprintf(stderr, "ygm step2: snapshot rc %d payload %llu\n", e, (unsigned long long)r1.payload_bytes);
   if (e || (e = pack_snapshots(c, s, r1, n_docs))) return e;
-  uint64_t sv_end = 0;
-  if (n_docs && hipMemcpy(&sv_end, d_sv_off + n_docs, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
+  const uint64_t sv_end = n_docs ? read_u64(c, s, d_sv_off + n_docs, e) : 0;
+  if (e) return e;
   e = run_doc_kernel(c, DOC_DIFF, c->s2_data.as<uint8_t>(), r1.payload_bytes, c->s2_off.as<uint64_t>(), d_sv_arena, sv_end, d_sv_off, n_docs, s,
                      out, YGM_F_KEEP_SUB);
   if (dbg) fprintf(stderr, "ygm step2: diff rc %d\n", e);
@@ -1134,8 +1109,10 @@ int ygm_diff_shared_v1_device(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena
                               const uint8_t* d_sv_arena, const uint64_t* d_sv_off, const uint32_t* d_ask_doc, uint32_t n_asks, void* stream,
                               ygm_device_result* out) {
   if (!c || !out || (n_asks && (!d_sv_off || !d_ask_doc))) return YGM_EINVAL;
-  uint64_t sv_end = 0;
-  if (n_asks && hipMemcpy(&sv_end, d_sv_off + n_asks, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
+  int e = 0;
+  (void)hipSetDevice(c->device);
+  const uint64_t sv_end = n_asks ? read_u64(c, stream ? (hipStream_t)stream : c->stream, d_sv_off + n_asks, e) : 0;
+  if (e) return e;
   return run_doc_kernel(c, DOC_DIFF, d_arena, arena_bytes, d_doc_off, d_sv_arena, sv_end, d_sv_off, n_docs, stream, out, 0, true, d_ask_doc, n_asks);
 }
 
@@ -1166,31 +1143,10 @@ int ygm_sync_step2_shared_opts_v1_device(ygm_ctx* c, const uint8_t* d_states, ui
     PA = (uint32_t)read_u64(c, s, c->ask_pn.as<uint64_t>(), e);
     if (e) return e;
   }
-  if (PA) {   // as step2_pending_split, over the ask list
-    const uint64_t np = (uint64_t)PA + 1;
-    if (!c->pq_off.ensure(8ull * 4 * np + 16) || !c->pq_st.ensure(4ull * PA + 16) || !c->pn_off.ensure(8ull * (3ull * PA + 1) + 16) ||
-        !c->pn_du.ensure(4ull * np + 16))
-      return YGM_ENOMEM;
-    uint64_t* offs = c->pq_off.as<uint64_t>();
-    if (ygm_k_launch_pend_split_g(c->ask_pl.as<uint32_t>(), PA, c->ask_ix.as<uint32_t>(), c->sn_ws.as<uint8_t>(), r1.off, d_sv_arena, d_sv_off,
-                                  offs, nullptr, nullptr, nullptr, nullptr, 0, s))
-      return YGM_EDEVICE;
-    c->stats.host_syncs++;
-    for (int k = 0; k < 4; k++) HIPCHK(hipMemcpyAsync((uint64_t*)c->h_meta + k, offs + (uint64_t)k * np + PA, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(ptot, c->h_meta, sizeof ptot);
-    DevBuf* part[4] = {&c->pq_a, &c->pq_b, &c->pq_c, &c->pq_s};
-    for (int k = 0; k < 4; k++) {
-      if (!part[k]->ensure(ptot[k] + 64)) return YGM_ENOMEM;
-      HIPCHK(hipMemsetAsync(part[k]->as<uint8_t>() + ptot[k], 0, 64, s));
-    }
-    if (ygm_k_launch_pend_split_g(c->ask_pl.as<uint32_t>(), PA, c->ask_ix.as<uint32_t>(), c->sn_ws.as<uint8_t>(), r1.off, d_sv_arena, d_sv_off,
-                                  offs, c->pq_a.as<uint8_t>(), c->pq_b.as<uint8_t>(), c->pq_c.as<uint8_t>(), c->pq_s.as<uint8_t>(), 1, s))
-      return YGM_EDEVICE;
-  }
+  if (PA && (e = step2_pending_split(c, s, PA, c->ask_pl.as<uint32_t>(), true, d_sv_arena, d_sv_off, ptot))) return e;
   if ((e = pack_snapshots(c, s, r1, n_states))) return e;
-  uint64_t sv_end = 0;
-  if (n_asks && hipMemcpy(&sv_end, d_sv_off + n_asks, 8, hipMemcpyDeviceToHost) != hipSuccess) return YGM_EDEVICE;
+  const uint64_t sv_end = n_asks ? read_u64(c, s, d_sv_off + n_asks, e) : 0;
+  if (e) return e;
   e = run_doc_kernel(c, DOC_DIFF, c->s2_data.as<uint8_t>(), r1.payload_bytes, c->s2_off.as<uint64_t>(), d_sv_arena, sv_end, d_sv_off, n_states, s,
                      out, YGM_F_KEEP_SUB, true, d_ask_state, n_asks);
   if (e) return e;
@@ -1223,9 +1179,9 @@ static int v21_pass(ygm_ctx* c, hipStream_t s, const uint8_t* arena, const uint6
     if (ygm_k_launch_v21(0, arena, off, n, doc_upd, n_docs, mode, c->flags, c->v2_len.as<uint64_t>(), c->v2_st.as<int32_t>(), nullptr, cl, s) ||
         ygm_k_launch_scan(c->v2_len.as<uint64_t>(), n, c->v2_bs.as<uint64_t>(), s))
       return YGM_EDEVICE;
-    HIPCHK(hipMemcpyAsync(c->h_meta, c->v2_len.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(&total, c->h_meta, 8);
+    int e = 0;
+    total = read_u64(c, s, c->v2_len.as<uint64_t>() + n, e);
+    if (e) return e;
   }
   if (!c->v2_v1.ensure(total + 64)) return YGM_ENOMEM;   // (the V1 kernels read up to 64 bytes past the arena)
   if (n && ygm_k_launch_v21(1, arena, off, n, doc_upd, n_docs, mode, c->flags, c->v2_len.as<uint64_t>(), c->v2_st.as<int32_t>(),
@@ -1256,9 +1212,10 @@ static int v12_pass(ygm_ctx* c, hipStream_t s, const uint8_t* v1, const uint64_t
                               c->v2_olen.as<uint64_t>(), c->v2_ost.as<int32_t>(), claim, c->v2_pay.as<unsigned long long>(),
                               c->v2_scr.as<uint8_t>(), slot_total, s))
       return YGM_EDEVICE;
-    HIPCHK(hipMemcpyAsync(c->h_meta, c->v2_pay.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(&fast_bytes, c->h_meta, 8); memcpy(&fast_docs, (uint8_t*)c->h_meta + 8, 8);
+    uint64_t pay[2];
+    const int e = read_u64_pair(c, s, c->v2_pay.as<uint64_t>(), pay);
+    if (e) return e;
+    fast_bytes = pay[0]; fast_docs = pay[1];
   }
   if (fast && fast_docs == n_docs) {   // every document done by the fast encoder: no general pass
     out->data = c->v2_out.as<uint8_t>(); out->off = c->v2_fo.as<uint64_t>(); out->len = c->v2_olen.as<uint64_t>();
@@ -1270,9 +1227,9 @@ static int v12_pass(ygm_ctx* c, hipStream_t s, const uint8_t* v1, const uint64_t
                                c->v2_off.as<uint64_t>(), c->v2_ost.as<int32_t>(), claim, s) ||
         ygm_k_launch_scan(c->v2_off.as<uint64_t>(), n_docs, c->v2_bs.as<uint64_t>(), s))
       return YGM_EDEVICE;
-    HIPCHK(hipMemcpyAsync(c->h_meta, c->v2_off.as<uint64_t>() + n_docs, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(&total, c->h_meta, 8);
+    int e = 0;
+    total = read_u64(c, s, c->v2_off.as<uint64_t>() + n_docs, e);
+    if (e) return e;
   }
   if (!c->v2_out.ensure(slot_total + total + 64, slot_total, s)) return YGM_ENOMEM;
   if (n_docs && ygm_k_launch_v12_write(v1, v1_off, v1_len, v2a, v2n, upd_off, doc_upd, n_docs, mode, c->flags, c->v2_L.as<uint32_t>(),

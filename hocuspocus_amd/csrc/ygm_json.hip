@@ -1,6 +1,7 @@
 // ygm_json.hip -- stored documents as ProseMirror / Tiptap JSON (ygm_json_v1; ygm_json.hpp for the semantics):
-//   k_json : shaped like k_text (ygm_text.hip): a wave's documents staged in LDS, dpw per wave, workspaces from the
-//            snapshot's count and scan launches (ygm_k_launch_snap_plan), the JSON in the workspace's output region.
+//   k_json : a wave's documents staged in LDS, dpw per wave (staging, lane prologue and epilogue: ygm_docstage.hpp),
+//            workspaces from the snapshot's count and scan launches (ygm_k_launch_snap_plan), the JSON in the
+//            workspace's output region.
 // There is no LDS flat tier: the flat-text envelope has no nested types, so it holds no ProseMirror document.
 // Unlike the text, the JSON is not bounded by Caps::out (every op repeats the current marks).  A document whose JSON
 // does not fit records the needed length, claims that many bytes of the overflow region after the workspaces with
@@ -15,56 +16,34 @@
 #include "ygm_common.hpp"
 #include "ygm_docmeta.hpp"
 #include "ygm_json.hpp"
+#include "ygm_docstage.hpp"
 #include "ygm_launch.hpp"
 
 namespace ygm {
 
-constexpr int JS_NT = 64;             // one wave per block, as the snapshot kernels
-constexpr uint32_t JS_STAGE = 40960;  // LDS bytes that hold a wave's documents (k_text's TX_STAGE)
-
-// k_text's staging: the wave's consecutive documents [d0, d1) into LDS with 16-byte loads when they fit; returns the
-// lane's input pointer
-YDEV const uint8_t* json_stage(uint8_t* stg, const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, uint32_t d0, uint32_t d1,
-                               uint32_t d) {
-  const uint64_t a = doc_off[d0], b = doc_off[d1];
-  const uint64_t a16 = a & ~15ull;
-  const bool staged = b >= a && b - a16 <= JS_STAGE;
-  if (staged) {
-    const uint4* src = (const uint4*)(arena + a16);
-    for (uint32_t c = threadIdx.x; 16u * c < b - a16; c += JS_NT) ((uint4*)stg)[c] = src[c];   // (arena tail padding >= 16)
-  }
-  __syncthreads();
-  if (d >= d1) return nullptr;
-  const uint64_t x = doc_off[d];
-  return staged && x >= a && doc_off[d + 1] <= b ? stg + (x - a16) : arena + x;
-}
+using docstage::Lane;
 
 // again == 0: documents [0, n_docs), dpw per wave.  again == 1: the n_list documents of list[], the lanes of a wave
 // taking consecutive entries; document d writes out_len[d] bytes (the length its first run recorded) at out_off[d].
 // ovf_base: where the overflow region starts in ws (after the workspaces).
-__global__ __launch_bounds__(JS_NT) void k_json(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+__global__ __launch_bounds__(docstage::NT) void k_json(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
                                                const uint8_t* __restrict__ names, const uint64_t* __restrict__ name_off, uint32_t n_docs,
                                                uint32_t flags, uint32_t kind, const uint4* __restrict__ cnt, const uint64_t* __restrict__ ws_off,
                                                uint8_t* __restrict__ ws, uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
                                                int32_t* __restrict__ status, DocMeta* __restrict__ meta, uint32_t dpw, uint64_t base,
                                                uint64_t ovf_base, uint32_t* __restrict__ list, uint32_t n_list, uint32_t again) {
-  __shared__ __attribute__((aligned(16))) uint8_t stg[JS_STAGE + 16];
+  __shared__ __attribute__((aligned(16))) uint8_t stg[docstage::STAGE + 16];
   uint64_t mine = 0;
   if (!again) {
-    const uint32_t d0 = blockIdx.x * dpw, d1 = d0 + dpw < n_docs ? d0 + dpw : n_docs;
-    const uint32_t d = d0 + threadIdx.x;
-    const uint8_t* in = json_stage(stg, arena, doc_off, d0, d1, threadIdx.x < dpw ? d : d1);
-    if (threadIdx.x < dpw && d < n_docs) {
+    const Lane L = docstage::lane_doc(stg, arena, doc_off, n_docs, dpw);
+    const uint32_t d = L.d;
+    if (L.on) {
       const uint4 c = cnt[d];
       const uint64_t a = doc_off[d], b = doc_off[d + 1], na = name_off[d], nb = name_off[d + 1];
-      int st = ST_OK;
       uint32_t oo = 0, ol = 0;
-      if (b < a || b - a >= (1ull << 30) || nb < na || nb - na >= (1ull << 30)) st = ST_INVAL;
-      else if (c.w == 0) st = ST_MALFORMED;   // (an empty update: yjs throws reading it)
-      else {
-        const snap::Caps k = snap::caps_of(c.x, c.y, c.z, c.w);
-        st = json::json_doc(in, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, oo, ol);
-      }
+      snap::Caps k;
+      int st = docstage::lane_caps(nb >= na && nb - na < (1ull << 30), a, b, c, k);
+      if (st == ST_OK) st = json::json_doc(L.in, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, oo, ol);
       if (st == json::ST_JSON_MORE) {   // ol: the length needed
         const uint32_t i = atomicAdd(&meta->fb_count, 1u);
         const unsigned long long at = atomicAdd(&meta->cursor, (unsigned long long)snap::al16(ol));
@@ -72,12 +51,7 @@ __global__ __launch_bounds__(JS_NT) void k_json(const uint8_t* __restrict__ aren
         out_off[d] = ovf_base + at;
         out_len[d] = ol;
         status[d] = st;
-      } else {
-        out_off[d] = base + ws_off[d] + oo;
-        out_len[d] = st == ST_OK ? ol : 0u;
-        status[d] = st;
-        mine = st == ST_OK ? ol : 0u;
-      }
+      } else mine = docstage::put(d, out_off, out_len, status, base + ws_off[d] + oo, st == ST_OK ? ol : 0u, st);
     }
   } else {
     const uint32_t i = blockIdx.x * dpw + threadIdx.x;
@@ -90,13 +64,12 @@ __global__ __launch_bounds__(JS_NT) void k_json(const uint8_t* __restrict__ aren
       uint32_t ol = 0;
       int st = json::json_run(arena + a, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, ws + out_off[d], need, ol);
       if (st == json::ST_JSON_MORE || (st == ST_OK && ol != need)) st = ST_NOMEM;   // (cannot happen: the same walk twice)
-      out_len[d] = st == ST_OK ? ol : 0u;
+      out_len[d] = st == ST_OK ? ol : 0u;   // (out_off[d]: the place the first run claimed)
       status[d] = st;
       mine = st == ST_OK ? ol : 0u;
     }
   }
-  mine = wave_sum(mine);
-  if ((threadIdx.x & (WAVE - 1)) == 0 && mine) atomicAdd(&meta->payload, (unsigned long long)mine);
+  docstage::add_payload(mine, &meta->payload);
 }
 
 }  // namespace ygm
@@ -113,15 +86,11 @@ int ygm_k_launch_json(const uint8_t* arena, const uint64_t* doc_off, const uint8
                       int again, hipStream_t s) {
   const uint32_t n = again ? n_list : n_docs;
   if (n == 0) return 0;
-  const char* env = getenv("YGM_SNAP_DPW");
-  uint32_t dpw = env ? (uint32_t)atoi(env) : 16u;
-  if (dpw < 1 || dpw > (uint32_t)JS_NT) dpw = 16u;
+  const uint32_t dpw = docstage::docs_per_wave(0);
   const uint32_t g = (n + dpw - 1) / dpw;
-  hipLaunchKernelGGL(k_json, dim3(g), dim3(JS_NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off, ws,
+  hipLaunchKernelGGL(k_json, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off, ws,
                      out_off, out_len, status, (DocMeta*)meta, dpw, base, ovf_base, list, n_list, again ? 1u : 0u);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", __func__, hipGetErrorString(e)); return -1; }
-  return 0;
+  return ygm_launch_rc(__func__);
 }
 
 }  // extern "C"

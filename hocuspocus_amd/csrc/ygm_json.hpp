@@ -195,13 +195,7 @@ struct Walk {
 YDEV void emit_json(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32_t kind, snap::OutCap& o) {
   using namespace snap;
   (void)kind;
-  int32_t root = -1;
-  for (uint32_t t = 0; t < D.n_ty && root < 0; t++) {
-    if (D.ty[t].item != -1 || D.ty[t].name_len != name_len) continue;
-    bool eq = true;
-    for (uint32_t i = 0; i < name_len && eq; i++) eq = D.in[D.ty[t].name_off + i] == name[i];
-    if (eq) root = (int32_t)t;
-  }
+  const int32_t root = find_root(D, name, name_len);
   lit(o, "{\"type\":\"doc\",\"content\":[");
   if (root < 0) { lit(o, "]}"); return; }   // doc.getXmlFragment(name) of a name the update has no root for: an empty fragment
   Walk W{D, o, 0};
@@ -293,11 +287,9 @@ YDEV void emit_json(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32
 YDEV_NI int json_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, const uint8_t* name,
                      uint32_t name_len, uint32_t kind, uint8_t* out, uint32_t out_cap, uint32_t& out_len) {
   snap::Doc D;
-  text::carve(D, in, n, flags, ws, k, out, out_cap);
+  snap::carve(D, in, n, flags, ws, k, out, out_cap);
   out_len = 0;
-  D.parse();
-  if (!D.err) D.integrate_all();
-  if (!D.err) D.apply_ds();
+  D.load();
   if (D.err) return D.err;
   snap::OutCap o{out, 0, out_cap};
   emit_json(D, name, name_len, kind, o);

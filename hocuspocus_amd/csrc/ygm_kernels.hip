@@ -3484,14 +3484,14 @@ int ygm_k_launch_big_scan(const uint8_t* arena, const uint64_t* upd_off, const u
   if (n_fb == 0) return 0;
   BigScan S; size_t total;
   big_scan_layout(n_fb, fb_bytes, S, (uint8_t*)scan, total);
-  if (hipMemsetAsync(S.cnt, 0, 64, s) != hipSuccess) return launch_rc(__func__);
+  if (hipMemsetAsync(S.cnt, 0, 64, s) != hipSuccess) return ygm_launch_rc(__func__);
   hipLaunchKernelGGL(k_big_pick, dim3((n_fb + 15) / 16), dim3(1024), 0, s, arena, upd_off, doc_upd, fb_list, n_fb, S);
   // the scan: a persistent grid over the tasks (at most 16 workgroups per CU; the task count is on the device)
   const uint64_t g = S.ntask_cap < 16ull * device_cus() ? S.ntask_cap : 16ull * device_cus();
   hipLaunchKernelGGL(k_big_scan, dim3((uint32_t)g), dim3(256), 0, s, arena, upd_off, doc_upd, fb_list, flags, S);
   const uint64_t gv = S.vq_cap / 256 + 1 < 8ull * device_cus() ? S.vq_cap / 256 + 1 : 8ull * device_cus();
   hipLaunchKernelGGL(k_big_val, dim3((uint32_t)gv), dim3(256), 0, s, arena, upd_off, doc_upd, fb_list, flags, S);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 // The mid size starts after the 16-wave size's workgroups are resident: a 16-wave workgroup needs a whole CU (its LDS),
 // and once the mid size's four-per-CU workgroups (tens of thousands queued behind them) hold every CU, no CU drains
@@ -3513,7 +3513,7 @@ int ygm_k_launch_big_wait(void* meta, uint32_t n_large, hipStream_t s) {
   const uint32_t want = n_large < ncu ? n_large : ncu;
   if (want == 0) return 0;
   hipLaunchKernelGGL(k_big_wait, dim3(1), dim3(64), 0, s, (DocMeta*)meta, want);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 // large = 0: the mid size, large = 1: the 16-wave size, over the fb_list indices in fbx[0, n) (the mid size sends a
 // document whose log exceeds its LDS to up_list, meta->mid_defer)
@@ -3533,7 +3533,7 @@ int ygm_k_launch_merge_big(int large, const uint8_t* arena, const uint64_t* upd_
     hipLaunchKernelGGL(k_merge_big<BigCfgM>, dim3(n), dim3(BigCfgM::THREADS), 0, s, arena, upd_off, doc_upd, fb_list, flags, out, out_off,
                        out_len, status, (DocMeta*)meta, fb2_list, (BigBlk*)blk, blk_cap, (BigRec*)rec, rec_cap, slot_total, out_cap, S,
                        fbx, up_list);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 size_t ygm_k_meta_bytes() { return sizeof(DocMeta); }
 size_t ygm_k_seq_reader_bytes() { return sizeof(Stream); }
@@ -3548,7 +3548,7 @@ int ygm_k_launch_doc(int mode, const uint8_t* arena, const uint64_t* doc_off, co
     hipLaunchKernelGGL(k_doc<0>, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out, out_off, out_len, status, lb, (DocMeta*)meta, out_cap);
   else
     hipLaunchKernelGGL(k_doc<1>, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out, out_off, out_len, status, lb, (DocMeta*)meta, out_cap);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 int ygm_k_launch_doc_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
@@ -3559,7 +3559,7 @@ int ygm_k_launch_doc_gather(const uint8_t* arena, const uint64_t* doc_off, const
   if (tiles == 0) return 0;
   hipLaunchKernelGGL(k_doc_gather, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out,
                      out_off, out_len, status, lb, (DocMeta*)meta, out_cap, ask_ix);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 // ======================================================================= host API: packed results
@@ -3649,7 +3649,7 @@ int ygm_k_launch_pack(const uint8_t* src, const uint64_t* off, const uint64_t* l
   hipLaunchKernelGGL(k_pack_off, dim3(nb), dim3(DOC_NT), 0, s, len, status, n, (const uint64_t*)bsum, poff);
   hipLaunchKernelGGL(k_pack_chunks, dim3(8u * device_cus()), dim3(256), 0, s, src, off, n, (const uint64_t*)poff,
                      (const uint64_t*)(bsum + nb), dst);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 // workgroups of `threads` resident at once on the device (occupancy x CUs), for persistent grids
@@ -3681,7 +3681,7 @@ int ygm_k_launch_merge_lean(const uint8_t* arena, const uint64_t* upd_off, const
     hipLaunchKernelGGL((k_merge_lean<0, 0>), dim3(grid), dim3(WAVE), 0, s, arena, upd_off, doc_upd, n_docs, flags, out, out_off, out_len,
                        status, (DocMeta*)meta, (DocMeta*)meta_next, defer_list, out_cap, (const uint32_t*)nullptr, 0u,
                        (const uint64_t*)nullptr, (const uint16_t*)nullptr);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 // The update-offset table of the compact input form, for the documents of `list` (every document: list == nullptr):
 // a wave per document scans its lengths from its base.  An offset past the document's end is clamped to it (lengths
@@ -3714,7 +3714,7 @@ int ygm_k_launch_build_off(const uint64_t* doc_off, const uint16_t* upd_len, con
                            uint64_t* upd_off, hipStream_t s) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_build_off, dim3((n + 3) / 4), dim3(256), 0, s, doc_off, upd_len, doc_upd, list, n, upd_off);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 // the wide lean kernel over the narrow one's deferred list (n_list entries); its own deferrals go to defer_list
 // (count: DocMeta::wide_defer)
@@ -3728,7 +3728,7 @@ int ygm_k_launch_merge_lean_wide(const uint8_t* arena, const uint64_t* upd_off, 
   hipLaunchKernelGGL((k_merge_lean<1, 0>), dim3(grid), dim3(WAVE), 0, s, arena, upd_off, doc_upd, n_docs, flags, out, out_off, out_len,
                      status, (DocMeta*)meta, (DocMeta*)meta_next, defer_list, out_cap, list, n_list, (const uint64_t*)nullptr,
                      upd_len);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 // YGM_WAVE_GRID / YGM_FAST_GRID (testing knobs, as YGM_V12F_GRID of the V2 transcoders): a positive value replaces the
@@ -3751,7 +3751,7 @@ int ygm_k_launch_merge_wave(const uint8_t* arena, const uint64_t* upd_off, const
   const uint32_t grid = n_docs < resident ? n_docs : resident;
   hipLaunchKernelGGL(k_merge_wave, dim3(grid), dim3(WAVE), 0, s, arena, upd_off, doc_upd, docs, n_dev, n_docs,
                      flags, out, out_off, out_len, status, (DocMeta*)meta, defer_list, fb_list, out_cap);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 int ygm_k_launch_route_big(const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs, const unsigned int* n_dev, uint32_t n_docs,
@@ -3761,7 +3761,7 @@ int ygm_k_launch_route_big(const uint64_t* upd_off, const uint32_t* doc_upd, con
   const uint32_t grid = (n_docs + 255u) / 256u < 2048u ? (n_docs + 255u) / 256u : 2048u;   // (n_docs: the bound of the device count)
   hipLaunchKernelGGL(k_route_big, dim3(grid), dim3(256), 0, s, upd_off, doc_upd, docs, n_dev, n_docs, flags, out_off, out_len, status,
                      (DocMeta*)meta, fb_list, rest);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 int ygm_k_launch_merge_fast(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs,
@@ -3774,7 +3774,7 @@ int ygm_k_launch_merge_fast(const uint8_t* arena, const uint64_t* upd_off, const
   const uint32_t grid = n_docs < resident ? n_docs : resident;
   hipLaunchKernelGGL(k_merge_fast, dim3(grid), dim3(M_NT), 0, s, arena, upd_off, doc_upd, docs, n_dev, n_docs, flags, out, out_off, out_len,
                      status, slot_total, (DocMeta*)meta, fb_list, out_cap);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 int ygm_k_launch_merge_seq(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list, uint32_t n_fb,
@@ -3785,7 +3785,7 @@ int ygm_k_launch_merge_seq(const uint8_t* arena, const uint64_t* upd_off, const 
   SeqScratch scr{(Stream*)readers, order, tmp, ubase, ulen, cnt, (DRec*)drec, upd_cap, byte_cap};
   hipLaunchKernelGGL(k_merge_seq, dim3((n_fb + 63) / 64), dim3(64), 0, s, arena, upd_off, doc_upd, fb_list, n_fb, flags, out, out_off,
                      out_len, status, (DocMeta*)meta, scr, slot_total, out_cap);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 }  // extern "C"

@@ -1,10 +1,19 @@
 // ygm_launch.hpp -- the kernel launchers (ygm_k_*): defined in the .hip files, called by the host runtime
 // (ygm_engine.cpp).  Every definer and the caller include this header, so a definition that disagrees with its
-// declaration does not compile (C-linkage functions cannot be overloaded).
+// declaration does not compile (C-linkage functions cannot be overloaded).  ygm_launch_rc is every launcher's return:
+// the launch's error, reported once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
+
+// 0, or -1 with one stderr line when the launches since the last check left an error (fn: the launcher's __func__)
+static inline int ygm_launch_rc(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", fn, hipGetErrorString(e)); return -1; }
+  return 0;
+}
 
 extern "C" {
 size_t ygm_k_meta_bytes();

@@ -5,9 +5,12 @@
 //   k_snap_scan* : exclusive scan of the workspace sizes (three launches, 256 documents per block)
 //   k_snap       : per document, integrate + gc + merge + encode into its workspace's output region
 //   k_pend_*     : documents left pending (ST_PEND): their [state, pendingDs, pending structs] packed as three-update
-//                  documents for the merge kernels (plan, copy), then the merged bytes' places written back (fix)
+//                  documents for the merge kernels (plan, copy), then the merged bytes' places written back (fix);
+//                  k_pend_split* / k_pend_join*: their three parts diffed and merged for SyncStep2
+//   k_cont_count, k_cont : read-only SyncStep2 (snapshotContainsUpdate), a thread per document
 // A thread per document keeps the reference's sequential algorithm (YATA integration order matters)
-// while 64 documents share a wave; the workspace is per document, so nothing is shared.
+// while up to 64 documents share a wave; the workspace is per document, so nothing is shared.  The staging into LDS,
+// the lane prologue and the epilogue of k_snap_count and k_snap are ygm_docstage.hpp's, shared with k_text and k_json.
 // k_snap_text and k_snap take a nullable per-document option array (one byte each; bit 0, YGM_DOC_NO_GC: the document
 // is a Y.Doc({gc: false}), snap::F_SNAP_NOGC for that document alone; any other bit: ST_INVAL for that document, the
 // byte not used otherwise).  The count pass does not depend on it.
@@ -19,31 +22,12 @@
 #include "ygm_common.hpp"
 #include "ygm_snapshot.hpp"
 #include "ygm_snap_text.hpp"
+#include "ygm_docstage.hpp"
 #include "ygm_launch.hpp"
 
 namespace ygm {
 
-constexpr int SN_NT = 64;   // one wave per block: documents are independent
-constexpr uint32_t SN_DPW = 16;       // documents per wave of the count pass (lanes 0..15)
-constexpr uint32_t SN_STAGE = 40960;  // LDS bytes that hold a wave's documents
-
-// The wave's documents [d0, d1) are consecutive in the arena: when their bytes fit, the wave copies them into LDS
-// with 16-byte loads and each lane parses its document from there (the codec walks bytes one dependent read at a
-// time: ~100 cycles from LDS instead of a global-memory round trip).  Returns the lane's input pointer.
-YDEV const uint8_t* snap_stage(uint8_t* stg, const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, uint32_t d0,
-                               uint32_t d1, uint32_t d) {
-  const uint64_t a = doc_off[d0], b = doc_off[d1];
-  const uint64_t a16 = a & ~15ull;
-  const bool staged = b >= a && b - a16 <= SN_STAGE;
-  if (staged) {
-    const uint4* src = (const uint4*)(arena + a16);
-    for (uint32_t c = threadIdx.x; 16u * c < b - a16; c += SN_NT) ((uint4*)stg)[c] = src[c];   // (arena tail padding >= 16)
-  }
-  __syncthreads();
-  if (d >= d1) return nullptr;
-  const uint64_t x = doc_off[d];
-  return staged && x >= a && doc_off[d + 1] <= b ? stg + (x - a16) : arena + x;
-}
+using docstage::Lane;
 
 // k_snap_text: one document per workgroup (one wave): lane 0 runs the flat-text snapshot (ygm_snap_text.hpp) with
 // its workspace in the workgroup's LB bytes of LDS and its input read through the scalar cache (aligned dwords from
@@ -52,7 +36,7 @@ YDEV const uint8_t* snap_stage(uint8_t* stg, const uint8_t* __restrict__ arena, 
 // Documents outside the envelope or the workspace are left unclaimed (a second launch with a larger LB, then the
 // count / scan / k_snap path).  Outputs go to per-document slots at align16(2 * doc_off[d] + 64 * d), 2n + 48 bytes.
 template <uint32_t LB>
-__global__ __launch_bounds__(SN_NT) void k_snap_text(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, uint32_t n_docs,
+__global__ __launch_bounds__(docstage::NT) void k_snap_text(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, uint32_t n_docs,
                                                     uint32_t flags, uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
                                                     uint64_t* __restrict__ out_len, int32_t* __restrict__ status, uint8_t* __restrict__ claim,
                                                     unsigned long long* __restrict__ pay, uint32_t again, uint64_t slot_total,
@@ -78,19 +62,17 @@ __global__ __launch_bounds__(SN_NT) void k_snap_text(const uint8_t* __restrict__
   claim[d] = ok ? 1 : 0;
 }
 
-__global__ __launch_bounds__(SN_NT) void k_snap_count(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+__global__ __launch_bounds__(docstage::NT) void k_snap_count(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
                                                      uint32_t n_docs, uint32_t flags, uint4* __restrict__ cnt,
                                                      uint64_t* __restrict__ need, const uint8_t* __restrict__ claim) {
-  __shared__ __attribute__((aligned(16))) uint8_t stg[SN_STAGE + 16];
-  const uint32_t d0 = blockIdx.x * SN_DPW, d1 = d0 + SN_DPW < n_docs ? d0 + SN_DPW : n_docs;
-  const uint32_t d = d0 + threadIdx.x;
-  const uint8_t* in = snap_stage(stg, arena, doc_off, d0, d1, threadIdx.x < SN_DPW ? d : d1);
-  if (threadIdx.x >= SN_DPW || d >= n_docs) return;
+  __shared__ __attribute__((aligned(16))) uint8_t stg[docstage::STAGE + 16];
+  const Lane L = docstage::lane_doc(stg, arena, doc_off, n_docs, docstage::DPW);
+  const uint32_t d = L.d;
+  if (!L.on) return;
   if (claim && claim[d]) { cnt[d] = make_uint4(0, 0, 0, 0); need[d] = 0; return; }   // k_snap_text wrote it
-  const uint64_t a = doc_off[d], b = doc_off[d + 1];
   uint32_t S = 0, D = 0, C = 0;
-  const uint32_t n = b > a && b - a < (1ull << 30) ? (uint32_t)(b - a) : 0u;
-  if (n) snap::count_doc(in, n, flags, S, D, C);
+  const uint32_t n = docstage::doc_len(doc_off[d], doc_off[d + 1]);
+  if (n) snap::count_doc(L.in, n, flags, S, D, C);
   cnt[d] = make_uint4(S, D, C, n);
   need[d] = snap::al16(snap::ws_bytes(snap::caps_of(S, D, C, n)));
 }
@@ -128,39 +110,28 @@ __global__ __launch_bounds__(256) void k_snap_scan_apply(uint64_t* __restrict__ 
   if (i == n) v[n] = bs[gridDim.x];
 }
 
-__global__ __launch_bounds__(SN_NT) void k_snap(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, uint32_t n_docs,
+__global__ __launch_bounds__(docstage::NT) void k_snap(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, uint32_t n_docs,
                                                uint32_t flags, const uint4* __restrict__ cnt, const uint64_t* __restrict__ ws_off,
                                                uint8_t* __restrict__ ws, uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
                                                int32_t* __restrict__ status, unsigned long long* __restrict__ payload, uint32_t dpw,
                                                const uint8_t* __restrict__ claim, uint64_t base, uint32_t* __restrict__ pend_list,
                                                unsigned int* __restrict__ pend_n, const uint8_t* __restrict__ opt) {
-  // dpw documents per wave (lanes >= dpw idle): the per-document code diverges from lane to lane, so
-  // fewer documents per wave trade SIMD lanes for less serialised divergence and more waves in flight
-  __shared__ __attribute__((aligned(16))) uint8_t stg[SN_STAGE + 16];
-  const uint32_t d0 = blockIdx.x * dpw, d1 = d0 + dpw < n_docs ? d0 + dpw : n_docs;
-  const uint32_t d = d0 + threadIdx.x;
-  const uint8_t* in = snap_stage(stg, arena, doc_off, d0, d1, threadIdx.x < dpw ? d : d1);
+  __shared__ __attribute__((aligned(16))) uint8_t stg[docstage::STAGE + 16];
+  const Lane L = docstage::lane_doc(stg, arena, doc_off, n_docs, dpw);
+  const uint32_t d = L.d;
   uint64_t mine = 0;
-  if (threadIdx.x < dpw && d < n_docs && !(claim && claim[d])) {
+  if (L.on && !(claim && claim[d])) {
     const uint4 c = cnt[d];
     const uint64_t a = doc_off[d], b = doc_off[d + 1];
-    int st = ST_OK;
     uint32_t oo = 0, ol = 0;
     uint32_t fl;
-    if (!snap::doc_flags(flags, opt, d, fl) || b < a || b - a >= (1ull << 30)) st = ST_INVAL;
-    else if (c.w == 0) st = ST_MALFORMED;   // (an empty update: yjs throws reading it)
-    else {
-      const snap::Caps k = snap::caps_of(c.x, c.y, c.z, c.w);
-      st = snap::snapshot_doc(in, c.w, fl, ws + base + ws_off[d], k, oo, ol);
-    }
-    out_off[d] = base + ws_off[d] + oo;
-    out_len[d] = (st == ST_OK || st == snap::ST_PEND) ? ol : 0u;
-    status[d] = st;
+    snap::Caps k;
+    int st = docstage::lane_caps(snap::doc_flags(flags, opt, d, fl), a, b, c, k);
+    if (st == ST_OK) st = snap::snapshot_doc(L.in, c.w, fl, ws + base + ws_off[d], k, oo, ol);
+    mine = docstage::put(d, out_off, out_len, status, base + ws_off[d] + oo, (st == ST_OK || st == snap::ST_PEND) ? ol : 0u, st);
     if (st == snap::ST_PEND) pend_list[atomicAdd(pend_n, 1u)] = d;   // (rare: one atomic per such document)
-    mine = st == ST_OK ? ol : 0u;
   }
-  mine = wave_sum(mine);
-  if ((threadIdx.x & (WAVE - 1)) == 0 && mine) atomicAdd(payload, (unsigned long long)mine);
+  docstage::add_payload(mine, payload);
 }
 
 // ---- pending documents: [state, pendingDs, pending structs] (PendHdr) -> three-update documents for the merge kernels
@@ -366,14 +337,13 @@ __global__ __launch_bounds__(256) void k_pend_join_copy(uint32_t P, const uint8_
 // [k, k + l) lies in one snapshot range [a, b) with a <= k and k + l <= b (sortAndMergeDeleteSet).
 struct CtSv { uint32_t client, end; };
 struct CtDs { uint32_t client, clock, end, pad; };
-__global__ __launch_bounds__(SN_NT) void k_cont_count(const uint8_t* __restrict__ st_arena, const uint64_t* __restrict__ st_off,
+__global__ __launch_bounds__(docstage::NT) void k_cont_count(const uint8_t* __restrict__ st_arena, const uint64_t* __restrict__ st_off,
                                                      uint32_t n_docs, uint32_t flags, uint64_t* __restrict__ need) {
-  const uint32_t d = blockIdx.x * SN_NT + threadIdx.x;
+  const uint32_t d = blockIdx.x * docstage::NT + threadIdx.x;
   if (d >= n_docs) return;
-  const uint64_t a = st_off[d], b = st_off[d + 1];
   uint32_t S = 0, D = 0, C = 0;
-  const uint32_t n = b > a && b - a < (1ull << 30) ? (uint32_t)(b - a) : 0u;
-  if (n) snap::count_doc(st_arena + a, n, flags, S, D, C);
+  const uint32_t n = docstage::doc_len(st_off[d], st_off[d + 1]);
+  if (n) snap::count_doc(st_arena + st_off[d], n, flags, S, D, C);
   need[d] = snap::al16((uint64_t)(C + 1) * sizeof(CtSv)) + snap::al16((uint64_t)(D + 1) * sizeof(CtDs));
 }
 // ws holds ws_bytes (k_cont_count's size for the document): a snapshot with more blocks or ranges than
@@ -438,12 +408,12 @@ YDEV_NI int contains_doc(const uint8_t* sp, uint32_t sn, const uint8_t* up, uint
   res = 1;
   return ST_OK;
 }
-__global__ __launch_bounds__(SN_NT) void k_cont(const uint8_t* __restrict__ st_arena, const uint64_t* __restrict__ st_off,
+__global__ __launch_bounds__(docstage::NT) void k_cont(const uint8_t* __restrict__ st_arena, const uint64_t* __restrict__ st_off,
                                                const uint8_t* __restrict__ up_arena, const uint64_t* __restrict__ up_off, uint32_t n_docs,
                                                uint32_t flags, const uint64_t* __restrict__ ws_off, uint8_t* __restrict__ ws,
                                                uint8_t* __restrict__ out, uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
                                                int32_t* __restrict__ status) {
-  const uint32_t d = blockIdx.x * SN_NT + threadIdx.x;
+  const uint32_t d = blockIdx.x * docstage::NT + threadIdx.x;
   if (d >= n_docs) return;
   const uint64_t a = st_off[d], b = st_off[d + 1], ua = up_off[d], ub = up_off[d + 1];
   uint32_t res = 0;
@@ -460,12 +430,6 @@ using namespace ygm;
 
 extern "C" {
 
-static int snap_rc(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", fn, hipGetErrorString(e)); return -1; }
-  return 0;
-}
-
 // phase 1: counts and the scanned workspace offsets (ws_off: n_docs + 1 entries, total at [n_docs];
 // bs: ceil(n / 256) + 1 scratch entries)
 int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
@@ -475,31 +439,31 @@ int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32
   // again == 0: 6 KiB of LDS per document (207 parts); again == 1: 24 KiB (865 parts) for the documents the first launch left.
   // YGM_SNAP_TEXT="KiB" picks another measured size for the first launch.
   if (again) {
-    hipLaunchKernelGGL((k_snap_text<24576>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
+    hipLaunchKernelGGL((k_snap_text<24576>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
                        claim, pay, 1u, slot_total, opt);
-    return snap_rc(__func__);
+    return ygm_launch_rc(__func__);
   }
   const char* env = getenv("YGM_SNAP_TEXT");
   const int lb = env ? atoi(env) : 6;
-#define SNT(L) if (lb == L) { hipLaunchKernelGGL((k_snap_text<L * 1024>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, \
-                                                   out_off, out_len, status, claim, pay, 0u, slot_total, opt); return snap_rc(__func__); }
+#define SNT(L) if (lb == L) { hipLaunchKernelGGL((k_snap_text<L * 1024>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, out, \
+                                                   out_off, out_len, status, claim, pay, 0u, slot_total, opt); return ygm_launch_rc(__func__); }
   SNT(4) SNT(5) SNT(8)
 #undef SNT
-  if (lb == 53) { hipLaunchKernelGGL((k_snap_text<5376>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
-                                     claim, pay, 0u, slot_total, opt); return snap_rc(__func__); }
-  hipLaunchKernelGGL((k_snap_text<6144>), dim3(n_docs), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status, claim,
+  if (lb == 53) { hipLaunchKernelGGL((k_snap_text<5376>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
+                                     claim, pay, 0u, slot_total, opt); return ygm_launch_rc(__func__); }
+  hipLaunchKernelGGL((k_snap_text<6144>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status, claim,
                      pay, 0u, slot_total, opt);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_snap_plan(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, void* cnt, uint64_t* ws_off,
                            uint64_t* bs, const uint8_t* claim, hipStream_t s) {
   if (n_docs == 0) return 0;
-  const uint32_t g = (n_docs + SN_DPW - 1) / SN_DPW, nb = (n_docs + 1 + 255) / 256;
-  hipLaunchKernelGGL(k_snap_count, dim3(g), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, (uint4*)cnt, ws_off, claim);
+  const uint32_t g = (n_docs + docstage::DPW - 1) / docstage::DPW, nb = (n_docs + 1 + 255) / 256;
+  hipLaunchKernelGGL(k_snap_count, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, (uint4*)cnt, ws_off, claim);
   hipLaunchKernelGGL(k_snap_scan_sum, dim3(nb), dim3(256), 0, s, (const uint64_t*)ws_off, n_docs, bs);
   hipLaunchKernelGGL(k_snap_scan_top, dim3(1), dim3(1024), 0, s, bs, nb);
   hipLaunchKernelGGL(k_snap_scan_apply, dim3(nb), dim3(256), 0, s, ws_off, n_docs, (const uint64_t*)bs);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 // exclusive scan of v[0..n) in place, total at v[n] (bs: ceil((n + 1) / 256) + 1 scratch entries)
 int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s) {
@@ -508,7 +472,7 @@ int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s) {
   hipLaunchKernelGGL(k_snap_scan_sum, dim3(nb), dim3(256), 0, s, (const uint64_t*)v, n, bs);
   hipLaunchKernelGGL(k_snap_scan_top, dim3(1), dim3(1024), 0, s, bs, nb);
   hipLaunchKernelGGL(k_snap_scan_apply, dim3(nb), dim3(256), 0, s, v, n, (const uint64_t*)bs);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 // phase 2: the snapshots (ws sized from ws_off[n_docs])
 // dpw_hint: documents per wave when YGM_SNAP_DPW is not set (0: the default 16)
@@ -516,13 +480,11 @@ int ygm_k_launch_snap_w(const uint8_t* arena, const uint64_t* doc_off, uint32_t 
                         uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
                         uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, const uint8_t* opt, hipStream_t s) {
   if (n_docs == 0) return 0;
-  const char* env = getenv("YGM_SNAP_DPW");
-  uint32_t dpw = env ? (uint32_t)atoi(env) : (dpw_hint ? dpw_hint : 16u);
-  if (dpw < 1 || dpw > (uint32_t)SN_NT) dpw = 16u;
+  const uint32_t dpw = docstage::docs_per_wave(dpw_hint);
   const uint32_t g = (n_docs + dpw - 1) / dpw;
-  hipLaunchKernelGGL(k_snap, dim3(g), dim3(SN_NT), 0, s, arena, doc_off, n_docs, flags, (const uint4*)cnt, ws_off, ws, out_off, out_len,
+  hipLaunchKernelGGL(k_snap, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, (const uint4*)cnt, ws_off, ws, out_off, out_len,
                      status, payload, dpw, claim, base, pend_list, pend_n, opt);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
                       uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
@@ -532,19 +494,19 @@ int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_
 int ygm_k_launch_pend_plan(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, uint64_t* upd_off, uint32_t* doc_upd,
                            hipStream_t s) {
   hipLaunchKernelGGL(k_pend_plan, dim3(1), dim3(1024), 0, s, list, P, ws, out_off, upd_off, doc_upd);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_pend_copy(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const uint64_t* upd_off, uint8_t* dst,
                            hipStream_t s) {
   if (P == 0) return 0;
   hipLaunchKernelGGL(k_pend_copy, dim3(P), dim3(256), 0, s, list, ws, out_off, upd_off, dst);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_pend_fix(const uint32_t* list, uint32_t P, const uint64_t* m_off, const uint64_t* m_len, const int32_t* m_st,
                           const int32_t* pst, uint64_t tail, uint64_t* out_off, uint64_t* out_len, int32_t* status, hipStream_t s) {
   if (P == 0) return 0;
   hipLaunchKernelGGL(k_pend_fix, dim3((P + 255) / 256), dim3(256), 0, s, list, P, m_off, m_len, m_st, pst, tail, out_off, out_len, status);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_pend_split(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const uint8_t* sv,
                             const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc, uint8_t* dsv, int pass,
@@ -552,13 +514,13 @@ int ygm_k_launch_pend_split(const uint32_t* list, uint32_t P, const uint8_t* ws,
   if (P == 0) return 0;
   if (pass == 0) hipLaunchKernelGGL(k_pend_split_plan, dim3(1), dim3(1024), 0, s, list, P, ws, out_off, sv_off, offs);
   else hipLaunchKernelGGL(k_pend_split_copy, dim3(P), dim3(256), 0, s, list, P, ws, out_off, sv, sv_off, (const uint64_t*)offs, da, db, dc, dsv);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_ask_pending(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, uint32_t* list, unsigned int* n_out,
                              hipStream_t s) {
   if (n_asks == 0) return 0;
   hipLaunchKernelGGL(k_ask_pending, dim3((n_asks + 255) / 256), dim3(256), 0, s, ask_ix, n_asks, st_state, list, n_out);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_pend_split_g(const uint32_t* list, uint32_t P, const uint32_t* ask_ix, const uint8_t* ws, const uint64_t* out_off,
                               const uint8_t* sv, const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc,
@@ -567,7 +529,7 @@ int ygm_k_launch_pend_split_g(const uint32_t* list, uint32_t P, const uint32_t* 
   if (pass == 0) hipLaunchKernelGGL(k_pend_split_plan_g, dim3(1), dim3(1024), 0, s, list, P, ask_ix, ws, out_off, sv_off, offs);
   else hipLaunchKernelGGL(k_pend_split_copy_g, dim3(P), dim3(256), 0, s, list, P, ask_ix, ws, out_off, sv, sv_off, (const uint64_t*)offs, da,
                           db, dc, dsv);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_pend_join(uint32_t P, const uint8_t* ad, const uint64_t* a_off, const uint64_t* a_len, const int32_t* a_st, const uint8_t* bd,
                            const uint64_t* offs, const uint8_t* cd, const uint64_t* c_off, const uint64_t* c_len, const int32_t* c_st,
@@ -575,28 +537,28 @@ int ygm_k_launch_pend_join(uint32_t P, const uint8_t* ad, const uint64_t* a_off,
   if (P == 0) return 0;
   if (pass == 0) hipLaunchKernelGGL(k_pend_join_plan, dim3(1), dim3(1024), 0, s, P, a_len, a_st, offs, c_len, c_st, upd_off, doc_upd, pst);
   else hipLaunchKernelGGL(k_pend_join_copy, dim3(P), dim3(256), 0, s, P, ad, a_off, bd, offs, cd, c_off, (const uint64_t*)upd_off, dst);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 // read-only SyncStep2 containment: workspace plan (the snapshot scan), then one thread per document
 int ygm_k_launch_cont_plan(const uint8_t* st_arena, const uint64_t* st_off, uint32_t n_docs, uint32_t flags, uint64_t* ws_off, uint64_t* bs,
                            hipStream_t s) {
   if (n_docs == 0) return 0;
-  const uint32_t g = (n_docs + SN_NT - 1) / SN_NT, nb = (n_docs + 1 + 255) / 256;
-  hipLaunchKernelGGL(k_cont_count, dim3(g), dim3(SN_NT), 0, s, st_arena, st_off, n_docs, flags, ws_off);
+  const uint32_t g = (n_docs + docstage::NT - 1) / docstage::NT, nb = (n_docs + 1 + 255) / 256;
+  hipLaunchKernelGGL(k_cont_count, dim3(g), dim3(docstage::NT), 0, s, st_arena, st_off, n_docs, flags, ws_off);
   hipLaunchKernelGGL(k_snap_scan_sum, dim3(nb), dim3(256), 0, s, (const uint64_t*)ws_off, n_docs, bs);
   hipLaunchKernelGGL(k_snap_scan_top, dim3(1), dim3(1024), 0, s, bs, nb);
   hipLaunchKernelGGL(k_snap_scan_apply, dim3(nb), dim3(256), 0, s, ws_off, n_docs, (const uint64_t*)bs);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_cont(const uint8_t* st_arena, const uint64_t* st_off, const uint8_t* up_arena, const uint64_t* up_off, uint32_t n_docs,
                       uint32_t flags, const uint64_t* ws_off, uint8_t* ws, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
                       int32_t* status, hipStream_t s) {
   if (n_docs == 0) return 0;
-  const uint32_t g = (n_docs + SN_NT - 1) / SN_NT;
-  hipLaunchKernelGGL(k_cont, dim3(g), dim3(SN_NT), 0, s, st_arena, st_off, up_arena, up_off, n_docs, flags, ws_off, ws, out, out_off, out_len,
+  const uint32_t g = (n_docs + docstage::NT - 1) / docstage::NT;
+  hipLaunchKernelGGL(k_cont, dim3(g), dim3(docstage::NT), 0, s, st_arena, st_off, up_arena, up_off, n_docs, flags, ws_off, ws, out, out_off, out_len,
                      status);
-  return snap_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@
 // reference's: struct store per client (input structs in clock order, each a chain of its split
 // parts), document lists through left/right item indices, a type table (root types by name,
 // nested types per ContentType item) with per-type key lists for map entries.
+// The text and the JSON of a stored document (ygm_text.hpp, ygm_json.hpp) are this document with another last
+// stage: carve (the workspace), Doc::load (parse, integrate, apply the delete set) and find_root serve all three.
 //
 // Pending structs and a pending delete set (missing dependencies, clock gaps, Skips followed by structs, ranges past
 // the state): integrateStructs' dependency stack is followed as the reference runs it, its quirks included (the rest
@@ -863,20 +865,22 @@ struct Doc {
     return (uint32_t)sizeof(PendHdr) + o.n;
   }
 
-  YDEV uint32_t run() {
+  // the first three stages, what every stored-document operation reads: the integrated lists minus deleted items
+  YDEV void load() {
     parse();
     if (!err) integrate_all();
     if (!err) apply_ds();
+  }
+  YDEV uint32_t run() {
+    load();
     if (!err && !(flags & F_SNAP_NOGC)) gc_pass();   // (doc.gc false: deleted content stays)
     if (!err) merge_pass();
     return err ? 0u : encode();
   }
 };
 
-// carves a workspace (ws, ws_core_bytes(caps)) and runs the document, writing at most out_cap bytes at out
-YDEV_NI int snapshot_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const Caps& k, uint8_t* out, uint32_t out_cap,
-                         uint32_t& out_len) {
-  Doc D;
+// D: the document in[0, n) over a workspace carved from ws (ws_core_bytes(k) bytes), its output region out[0, out_cap)
+YDEV void carve(Doc& D, const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const Caps& k, uint8_t* out, uint32_t out_cap) {
   uint8_t* p = ws;
   D.in = in; D.n = n; D.flags = flags; D.err = 0; D.epoch = 0; D.n_ins = 0; D.hint_id = 0; D.hint_k = -1; D.pend = false;
   D.n_pds = 0; D.n_rest = 0;
@@ -892,6 +896,24 @@ YDEV_NI int snapshot_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t*
   D.seq = (int32_t*)p; D.cap_seq = k.seq; p += al16(4ull * k.seq);
   D.ch = (int32_t*)p; D.ch_mask = k.hc - 1u;
   D.out = out; D.cap_out = out_cap;
+}
+
+// the root type named name[0, name_len) (doc.get(name)), or -1: the update has no root of that name
+YDEV int32_t find_root(const Doc& D, const uint8_t* name, uint32_t name_len) {
+  for (uint32_t t = 0; t < D.n_ty; t++) {
+    if (D.ty[t].item != -1 || D.ty[t].name_len != name_len) continue;
+    bool eq = true;
+    for (uint32_t i = 0; i < name_len && eq; i++) eq = D.in[D.ty[t].name_off + i] == name[i];
+    if (eq) return (int32_t)t;
+  }
+  return -1;
+}
+
+// carves a workspace (ws, ws_core_bytes(caps)) and runs the document, writing at most out_cap bytes at out
+YDEV_NI int snapshot_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const Caps& k, uint8_t* out, uint32_t out_cap,
+                         uint32_t& out_len) {
+  Doc D;
+  carve(D, in, n, flags, ws, k, out, out_cap);
   out_len = D.run();
   return D.err ? D.err : D.pend ? ST_PEND : 0;
 }

@@ -1,8 +1,9 @@
 // ygm_text.hip -- plain text of stored documents (ygm_text_v1; ygm_text.hpp for the semantics):
 //   k_text_flat : flat-text documents asked by their single root name, one per wave: lane 0 integrates in LDS
 //                 (snapt::TDoc, as k_snap_text), the wave copies the live slices out; what it leaves unclaimed takes
-//   k_text      : the general path, shaped like k_snap: documents staged in LDS, dpw per wave, workspaces from the
-//                 snapshot's count and scan launches (ygm_k_launch_snap_plan), the text in the workspace's output region
+//   k_text      : the general path: documents staged in LDS, dpw per wave (staging, lane prologue and epilogue:
+//                 ygm_docstage.hpp), workspaces from the snapshot's count and scan launches (ygm_k_launch_snap_plan),
+//                 the text in the workspace's output region
 // Outputs of the flat tier go to per-document slots at align16(2 * doc_off[d] + 64 * d), as k_snap_text's (the text
 // is never longer than the input: disjoint slices of it).
 #include <hip/hip_runtime.h>
@@ -12,30 +13,13 @@
 
 #include "ygm_common.hpp"
 #include "ygm_text.hpp"
+#include "ygm_docstage.hpp"
 #include "ygm_launch.hpp"
 
 namespace ygm {
 
-constexpr int TX_NT = 64;             // one wave per block, as the snapshot kernels
-constexpr uint32_t TX_STAGE = 40960;  // LDS bytes that hold a wave's documents (k_snap's SN_STAGE)
+using docstage::Lane;
 constexpr uint32_t TX_SHORT = 16;     // a part up to this long is copied by its own lane
-
-// k_snap's staging (snap_stage, ygm_snapshot.hip): the wave's consecutive documents [d0, d1) into LDS with 16-byte
-// loads when they fit; returns the lane's input pointer
-YDEV const uint8_t* text_stage(uint8_t* stg, const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off, uint32_t d0, uint32_t d1,
-                               uint32_t d) {
-  const uint64_t a = doc_off[d0], b = doc_off[d1];
-  const uint64_t a16 = a & ~15ull;
-  const bool staged = b >= a && b - a16 <= TX_STAGE;
-  if (staged) {
-    const uint4* src = (const uint4*)(arena + a16);
-    for (uint32_t c = threadIdx.x; 16u * c < b - a16; c += TX_NT) ((uint4*)stg)[c] = src[c];   // (arena tail padding >= 16)
-  }
-  __syncthreads();
-  if (d >= d1) return nullptr;
-  const uint64_t x = doc_off[d];
-  return staged && x >= a && doc_off[d + 1] <= b ? stg + (x - a16) : arena + x;
-}
 
 // k_text_flat: one document per workgroup (one wave).  Lane 0 runs TDoc::parse / integrate_all / apply_ds over the
 // workgroup's LB bytes of LDS exactly as k_snap_text does (same layout, same envelope), checks the asked name and
@@ -45,7 +29,7 @@ YDEV const uint8_t* text_stage(uint8_t* stg, const uint8_t* __restrict__ arena, 
 // types.  A document outside the envelope, asked by another name, or whose slot lies past the region is left
 // unclaimed for k_text.
 template <uint32_t LB>
-__global__ __launch_bounds__(TX_NT) void k_text_flat(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+__global__ __launch_bounds__(docstage::NT) void k_text_flat(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
                                                     const uint8_t* __restrict__ names, const uint64_t* __restrict__ name_off, uint32_t n_docs,
                                                     uint32_t flags, uint8_t* __restrict__ out, uint64_t* __restrict__ out_off,
                                                     uint64_t* __restrict__ out_len, int32_t* __restrict__ status, uint8_t* __restrict__ claim,
@@ -102,36 +86,26 @@ __global__ __launch_bounds__(TX_NT) void k_text_flat(const uint8_t* __restrict__
   }
 }
 
-__global__ __launch_bounds__(TX_NT) void k_text(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+__global__ __launch_bounds__(docstage::NT) void k_text(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
                                                const uint8_t* __restrict__ names, const uint64_t* __restrict__ name_off, uint32_t n_docs,
                                                uint32_t flags, uint32_t mode, const uint4* __restrict__ cnt, const uint64_t* __restrict__ ws_off,
                                                uint8_t* __restrict__ ws, uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
                                                int32_t* __restrict__ status, unsigned long long* __restrict__ payload, uint32_t dpw,
                                                const uint8_t* __restrict__ claim, uint64_t base) {
-  // dpw documents per wave (lanes >= dpw idle), as k_snap: the per-document code diverges from lane to lane
-  __shared__ __attribute__((aligned(16))) uint8_t stg[TX_STAGE + 16];
-  const uint32_t d0 = blockIdx.x * dpw, d1 = d0 + dpw < n_docs ? d0 + dpw : n_docs;
-  const uint32_t d = d0 + threadIdx.x;
-  const uint8_t* in = text_stage(stg, arena, doc_off, d0, d1, threadIdx.x < dpw ? d : d1);
+  __shared__ __attribute__((aligned(16))) uint8_t stg[docstage::STAGE + 16];
+  const Lane L = docstage::lane_doc(stg, arena, doc_off, n_docs, dpw);
+  const uint32_t d = L.d;
   uint64_t mine = 0;
-  if (threadIdx.x < dpw && d < n_docs && !(claim && claim[d])) {
+  if (L.on && !(claim && claim[d])) {
     const uint4 c = cnt[d];
     const uint64_t a = doc_off[d], b = doc_off[d + 1], na = name_off[d], nb = name_off[d + 1];
-    int st = ST_OK;
     uint32_t oo = 0, ol = 0;
-    if (b < a || b - a >= (1ull << 30) || nb < na || nb - na >= (1ull << 30)) st = ST_INVAL;
-    else if (c.w == 0) st = ST_MALFORMED;   // (an empty update: yjs throws reading it)
-    else {
-      const snap::Caps k = snap::caps_of(c.x, c.y, c.z, c.w);
-      st = text::text_doc(in, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), mode, oo, ol);
-    }
-    out_off[d] = base + ws_off[d] + oo;
-    out_len[d] = st == ST_OK ? ol : 0u;
-    status[d] = st;
-    mine = st == ST_OK ? ol : 0u;
+    snap::Caps k;
+    int st = docstage::lane_caps(nb >= na && nb - na < (1ull << 30), a, b, c, k);
+    if (st == ST_OK) st = text::text_doc(L.in, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), mode, oo, ol);
+    mine = docstage::put(d, out_off, out_len, status, base + ws_off[d] + oo, st == ST_OK ? ol : 0u, st);
   }
-  mine = wave_sum(mine);
-  if ((threadIdx.x & (WAVE - 1)) == 0 && mine) atomicAdd(payload, (unsigned long long)mine);
+  docstage::add_payload(mine, payload);
 }
 
 }  // namespace ygm
@@ -140,36 +114,28 @@ using namespace ygm;
 
 extern "C" {
 
-static int text_rc(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", fn, hipGetErrorString(e)); return -1; }
-  return 0;
-}
-
 // the flat tier at k_snap_text's two LDS sizes: again == 0: 6 KiB per document; again == 1: 24 KiB for the documents
 // the first launch left (claim[] written by every launch for the documents it looked at)
 int ygm_k_launch_text_flat(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
                            uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, uint8_t* claim,
                            unsigned long long* pay, int again, uint64_t slot_total, hipStream_t s) {
   if (n_docs == 0) return 0;
-  if (again) hipLaunchKernelGGL((k_text_flat<24576>), dim3(n_docs), dim3(TX_NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, out,
+  if (again) hipLaunchKernelGGL((k_text_flat<24576>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, out,
                                 out_off, out_len, status, claim, pay, 1u, slot_total);
-  else hipLaunchKernelGGL((k_text_flat<6144>), dim3(n_docs), dim3(TX_NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, out, out_off,
+  else hipLaunchKernelGGL((k_text_flat<6144>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, out, out_off,
                           out_len, status, claim, pay, 0u, slot_total);
-  return text_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 // the general path over the workspaces ygm_k_launch_snap_plan sized (cnt, ws_off); dpw as ygm_k_launch_snap_w
 int ygm_k_launch_text(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
                       uint32_t flags, uint32_t mode, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
                       uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim, uint64_t base, hipStream_t s) {
   if (n_docs == 0) return 0;
-  const char* env = getenv("YGM_SNAP_DPW");
-  uint32_t dpw = env ? (uint32_t)atoi(env) : 16u;
-  if (dpw < 1 || dpw > (uint32_t)TX_NT) dpw = 16u;
+  const uint32_t dpw = docstage::docs_per_wave(0);
   const uint32_t g = (n_docs + dpw - 1) / dpw;
-  hipLaunchKernelGGL(k_text, dim3(g), dim3(TX_NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, mode, (const uint4*)cnt, ws_off, ws,
+  hipLaunchKernelGGL(k_text, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, mode, (const uint4*)cnt, ws_off, ws,
                      out_off, out_len, status, payload, dpw, claim, base);
-  return text_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 }  // extern "C"

@@ -16,7 +16,8 @@
 //   flat tier    (TDoc, LDS): flat_prepare -- the asked name against the update's single root name, the list
 //                linearised into sq[]; the wave-wide copy is k_text_flat's (ygm_text.hip), flat_emit_seq its
 //                sequential twin for the host harness (tools/snapdev/textdev.cpp)
-//   general tier (Doc, global workspace): emit_text -- the walk with an explicit stack in Doc::st
+//   general tier (Doc, global workspace; carve, Doc::load and find_root are the snapshot's): emit_text -- the walk
+//                with an explicit stack in Doc::st
 #pragma once
 #include "ygm_snapshot.hpp"
 #include "ygm_snap_text.hpp"
@@ -74,27 +75,6 @@ YDEV void flat_emit_seq(const snapt::TDoc& D, uint32_t cnt, O& o) {
 }
 
 // ------------------------------------------------------------------ general tier
-// a Doc over the workspace snap::snapshot_run carves (ws_core_bytes(k) at ws), its output region at out
-YDEV void carve(snap::Doc& D, const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, uint8_t* out,
-                uint32_t out_cap) {
-  using namespace snap;
-  uint8_t* p = ws;
-  D.in = in; D.n = n; D.flags = flags; D.err = 0; D.epoch = 0; D.n_ins = 0; D.hint_id = 0; D.hint_k = -1; D.pend = false;
-  D.n_pds = 0; D.n_rest = 0;
-  D.it = (SI*)p; D.n_it = 0; D.cap_it = k.it; p += al16((uint64_t)k.it * sizeof(SI));
-  D.pc = (Piece*)p; D.n_pc = 0; D.cap_pc = k.pc; p += al16((uint64_t)k.pc * sizeof(Piece));
-  D.ty = (TypeRec*)p; D.n_ty = 0; D.cap_ty = k.ty; p += al16((uint64_t)k.ty * sizeof(TypeRec));
-  D.me = (MapEnt*)p; D.n_me = 0; D.cap_me = k.me; p += al16((uint64_t)k.me * sizeof(MapEnt));
-  D.cl = (Cli*)p; D.n_cl = 0; D.cap_cl = k.cl; p += al16((uint64_t)k.cl * sizeof(Cli));
-  D.tx = (Rng*)p; D.n_tx = 0; D.cap_tx = k.tx; p += al16((uint64_t)k.tx * sizeof(Rng));
-  D.dsin = (Rng*)p; D.n_dsin = 0; D.cap_dsin = k.dsin; p += al16((uint64_t)k.dsin * sizeof(Rng));
-  D.pds = (Rng*)p; p += al16((uint64_t)k.dsin * sizeof(Rng));
-  D.st = (int32_t*)p; D.cap_st = k.st; p += al16(4ull * k.st);
-  D.seq = (int32_t*)p; D.cap_seq = k.seq; p += al16(4ull * k.seq);
-  D.ch = (int32_t*)p; D.ch_mask = k.hc - 1u;
-  D.out = out; D.cap_out = out_cap;
-}
-
 // The walk.  Capacity: the string pieces are disjoint slices of the input (<= n bytes together); a split through a
 // surrogate pair drops the pair's 4 bytes and adds a U+FFFD on each side (6 bytes: <= 3 more per split, and splits
 // are parts beyond the S input structs, < it); one 0x0A at most per type returned from (<= ty = S + 2 <= it).  So
@@ -105,13 +85,7 @@ YDEV void carve(snap::Doc& D, const uint8_t* in, uint32_t n, uint32_t flags, uin
 // document) exhausts the bound and ends in ST_UNSUP.
 YDEV void emit_text(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32_t mode, snap::OutCap& o) {
   using namespace snap;
-  int32_t root = -1;
-  for (uint32_t t = 0; t < D.n_ty && root < 0; t++) {
-    if (D.ty[t].item != -1 || D.ty[t].name_len != name_len) continue;
-    bool eq = true;
-    for (uint32_t i = 0; i < name_len && eq; i++) eq = D.in[D.ty[t].name_off + i] == name[i];
-    if (eq) root = (int32_t)t;
-  }
+  const int32_t root = find_root(D, name, name_len);
   if (root < 0) return;   // doc.getText(name) of a name the update has no root for: an empty type
   const uint64_t limit = (uint64_t)D.n_it + D.n_ty + 1u;
   uint64_t steps = 0;
@@ -153,11 +127,9 @@ YDEV void emit_text(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32
 YDEV_NI int text_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, const uint8_t* name,
                      uint32_t name_len, uint32_t mode, uint8_t* out, uint32_t out_cap, uint32_t& out_len) {
   snap::Doc D;
-  carve(D, in, n, flags, ws, k, out, out_cap);
+  snap::carve(D, in, n, flags, ws, k, out, out_cap);
   out_len = 0;
-  D.parse();
-  if (!D.err) D.integrate_all();
-  if (!D.err) D.apply_ds();
+  D.load();
   if (D.err) return D.err;
   snap::OutCap o{out, 0, out_cap};
   emit_text(D, name, name_len, mode, o);

@@ -334,11 +334,6 @@ using namespace ygm;
 
 extern "C" {
 
-static int v2_rc(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", fn, hipGetErrorString(e)); return -1; }
-  return 0;
-}
 size_t ygm_k_v2_cols() { return v2::C_N; }
 int ygm_k_launch_v21(int pass, const uint8_t* arena, const uint64_t* upd_off, uint32_t n_upd, const uint32_t* doc_upd, uint32_t n_docs,
                      uint32_t mode, uint32_t flags, uint64_t* len_or_off, int32_t* st, uint8_t* out, uint8_t* cl, hipStream_t s) {
@@ -353,7 +348,7 @@ int ygm_k_launch_v21(int pass, const uint8_t* arena, const uint64_t* upd_off, ui
     hipLaunchKernelGGL(k_v21_write, dim3(g), dim3(V2_NT), 0, s, arena, upd_off, n_upd, mode, flags, (const uint64_t*)len_or_off,
                        (const int32_t*)st, out, (const uint8_t*)cl);
   }
-  return v2_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_v12_count(const uint8_t* v1, const uint64_t* v1_off, const uint64_t* v1_len, const int32_t* v1_st, const uint8_t* v2a,
                            uint64_t v2n, const uint64_t* upd_off, const uint32_t* doc_upd, const int32_t* ust, uint32_t n_docs, uint32_t mode,
@@ -362,7 +357,7 @@ int ygm_k_launch_v12_count(const uint8_t* v1, const uint64_t* v1_off, const uint
   const uint32_t g = (n_docs + V2_NT - 1) / V2_NT;
   hipLaunchKernelGGL(k_v12_count, dim3(g), dim3(V2_NT), 0, s, v1, v1_off, v1_len, v1_st, v2a, v2n, upd_off, doc_upd, ust, n_docs, mode, flags,
                      L, tot, st, claim);
-  return v2_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 size_t ygm_k_v12_fast_scratch() {
   const size_t a = v12f_scratch<V12F_D, V12F_FS>(), b = v12f_scratch<2, (int)v2f::F_IN>();
@@ -379,7 +374,7 @@ int ygm_k_launch_v12_fast(const uint8_t* v1, const uint64_t* v1_off, const uint6
                      ust, n_docs, out, fo, olen, ost, claim, payload, 0, scr, slot_total);
   hipLaunchKernelGGL((k_v12_fast<2, (int)v2f::F_IN>), dim3(n2 < g2 ? n2 : g2), dim3(WAVE), 0, s, v1, v1_off, v1_len, v1_st, slot_off, doc_upd,
                      ust, n_docs, out, fo, olen, ost, claim, payload, 1, scr, slot_total);
-  return v2_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_v12_write(const uint8_t* v1, const uint64_t* v1_off, const uint64_t* v1_len, const uint8_t* v2a, uint64_t v2n,
                            const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, uint32_t mode, uint32_t flags, const uint32_t* L,
@@ -389,18 +384,18 @@ int ygm_k_launch_v12_write(const uint8_t* v1, const uint64_t* v1_off, const uint
   const uint32_t g = (n_docs + V2_NT - 1) / V2_NT;
   hipLaunchKernelGGL(k_v12_write, dim3(g), dim3(V2_NT), 0, s, v1, v1_off, v1_len, v2a, v2n, upd_off, doc_upd, n_docs, mode, flags, L, off, st,
                      out, out_len, claim, base, fo);
-  return v2_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_v2_status(const int32_t* ust, uint32_t n, int32_t* status, uint64_t* len, hipStream_t s) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_v2_status, dim3((n + 255) / 256), dim3(256), 0, s, ust, n, status, len);
-  return v2_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 int ygm_k_launch_v2_lens(const uint64_t* off, const int32_t* st, uint32_t n, uint64_t* len, hipStream_t s) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_v2_lens, dim3((n + 255) / 256), dim3(256), 0, s, off, st, n, len);
-  return v2_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 }  // extern "C"

@@ -138,9 +138,7 @@ int ygm_k_launch_ver_cut(const uint8_t* S, const uint64_t* s_off, const int32_t*
   if (n_docs == 0) return 0;
   hipLaunchKernelGGL(k_ver_cut, dim3(n_docs), dim3(VR_NT), 0, s, S, s_off, s_st, V, v_off, n_docs, flags, out, out_total, out_off, out_len,
                      status);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", __func__, hipGetErrorString(e)); return -1; }
-  return 0;
+  return ygm_launch_rc(__func__);
 }
 
 int ygm_k_launch_ver_cut_gather(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint32_t* ix, const uint64_t* ask_base,
@@ -149,9 +147,7 @@ int ygm_k_launch_ver_cut_gather(const uint8_t* S, const uint64_t* s_off, const i
   if (n_asks == 0) return 0;
   hipLaunchKernelGGL(k_ver_cut_gather, dim3(n_asks), dim3(VR_NT), 0, s, S, s_off, s_st, ix, ask_base, V, v_off, n_asks, flags, out, out_total,
                      out_off, out_len, status);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { fprintf(stderr, "ygm: %s: %s\n", __func__, hipGetErrorString(e)); return -1; }
-  return 0;
+  return ygm_launch_rc(__func__);
 }
 
 }  // extern "C"

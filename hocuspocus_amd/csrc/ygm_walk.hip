@@ -900,13 +900,13 @@ int ygm_k_launch_ask_plan(const uint64_t* doc_off, uint32_t n_docs, const uint32
                           uint64_t* ask_base, uint64_t* bs, hipStream_t s) {
   if (n_asks == 0) return hipMemsetAsync(ask_base, 0, 8, s) != hipSuccess;
   hipLaunchKernelGGL(k_ask_plan, dim3((n_asks + 255) / 256), dim3(256), 0, s, doc_off, n_docs, ask_doc, n_asks, ask_ix, ask_base);
-  if (launch_rc(__func__)) return 1;
+  if (ygm_launch_rc(__func__)) return 1;
   return ygm_k_launch_scan(ask_base, n_asks, bs, s);
 }
 int ygm_k_launch_ask_status(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, int32_t* status, uint64_t* len, hipStream_t s) {
   if (n_asks == 0) return 0;
   hipLaunchKernelGGL(k_ask_status, dim3((n_asks + 255) / 256), dim3(256), 0, s, ask_ix, n_asks, st_state, status, len);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 // the gather walker over n_asks asks (state-vector tables per ask: k_sv_table needs no change)
 int ygm_k_launch_doc_lean_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
@@ -919,7 +919,7 @@ int ygm_k_launch_doc_lean_gather(const uint8_t* arena, const uint64_t* doc_off, 
   hipLaunchKernelGGL(k_sv_table, dim3(waves), dim3(WAVE), 0, s, sv_arena, sv_off, n_asks, tbl, tbl_n);
   hipLaunchKernelGGL(k_doc_walk_gather, dim3(grid), dim3(WAVE), 0, s, arena, doc_off, (const uint8_t*)tbl, (const uint32_t*)tbl_n, n_asks,
                      out, out_off, out_len, status, (DocMeta*)meta, defer_list, out_cap, ask_ix, ask_base);
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 size_t ygm_k_sv_table_bytes(uint32_t n_docs) { return 144ull * n_docs + 64; }
@@ -945,7 +945,7 @@ int ygm_k_launch_doc_lean(int mode, const uint8_t* arena, uint64_t arena_bytes, 
     hipLaunchKernelGGL(k_doc_walk<1>, dim3(grid), dim3(WAVE), 0, s, arena, doc_off, (const uint8_t*)tbl, (const uint32_t*)tbl_n, n_docs,
                        out, out_off, out_len, status, (DocMeta*)meta, defer_list, out_cap);
   }
-  return launch_rc(__func__);
+  return ygm_launch_rc(__func__);
 }
 
 }  // extern "C"
