@@ -220,6 +220,9 @@ int ygm_text_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, 
  *   rewrite such names)                                                                   YGM_EUNSUPPORTED
  *   a number in an attribute, mark or embed that is not an integer JSON.stringify writes without an exponent
  *   (as ygm_convert_v2_to_v1 refuses it)                                                  YGM_ENONCANON
+ *   a number of more than 15 significant digits in a mark or embed value (9007199254740992: the state's parse takes
+ *   it as not canonical, as in ygm_snapshot_v1, so the refusal holds for every root name asked, an absent one
+ *   included)                                                                             YGM_ENONCANON
  *   a BigInt (JSON.stringify throws)                                                      YGM_EMALFORMED
  *   a JSON of 2^31 bytes or more                                                          YGM_ENOMEM
  * Any other status is the one the state's parse and integration give in ygm_snapshot_v1.  The caller keeps its yjs

@@ -12,6 +12,7 @@
 // stored again (row i belongs to row i of the input fixture, whose sha256 is recorded); the edge sessions are
 // generated here by yjs and carry their own states.
 //   node tools/json_corpus.js <out.json.gz> [limit]     (limit: only the first `limit` states of each set)
+//   node tools/json_corpus.js --states <in.json> <out.json.gz>     (given states and the boundary sessions: see statesMode)
 const fs = require('fs')
 const path = require('path')
 const zlib = require('zlib')
@@ -34,9 +35,11 @@ const ContentAny = (() => {   // the content constructor, from a document of the
 
 class Refuse extends Error { constructor (st) { super('refused ' + st); this.st = st } }
 
-// a value that came from JSON text (a format or embed value): numbers JSON.stringify writes as plain integers
+// a value that came from JSON text (a format or embed value): numbers JSON.stringify writes as plain integers of at
+// most 15 significant digits (more are not canonical to the engine's JSON check, as in the snapshot)
+const sigDigits = v => String(Math.abs(v)).replace(/^0\./, '').replace(/\./, '').replace(/^0+/, '').replace(/0+$/, '').length
 function checkJson (v) {
-  if (typeof v === 'number') { if (!Number.isInteger(v) || /e/.test(String(v))) throw new Refuse(3) } else if (Array.isArray(v)) v.forEach(checkJson)
+  if (typeof v === 'number') { if (!Number.isInteger(v) || /e/.test(String(v)) || sigDigits(v) > 15) throw new Refuse(3) } else if (Array.isArray(v)) v.forEach(checkJson)
   else if (v !== null && typeof v === 'object') Object.keys(v).forEach(k => checkJson(v[k]))
 }
 // a value that came from an Any (an attribute): what the engine's Any -> JSON conversion writes
@@ -86,13 +89,39 @@ function jsonOf (doc, name) {
   return JSON.stringify({ type: 'doc', content: doc.getXmlFragment(name).toArray().map(serialize) })
 }
 
+// What the state's parse refuses whatever root is asked (include/ygm.h: "any other status is the one the state's
+// parse and integration give in ygm_snapshot_v1"), as far as the sessions of this tool reach it: YGM_ENONCANON for a
+// format or embed value holding a number JSON.stringify writes with an exponent or with more than 15 significant
+// digits, and for an Any integer below -2147483647 (13.5's writeAny stores it as a varint no Y.Doc writes back).
+function stateRefusal (doc) {
+  let st = 0
+  const json = v => {
+    if (typeof v === 'number') { if (Number.isFinite(v) && (/e/.test(String(v)) || sigDigits(v) > 15)) st = 3 } else if (Array.isArray(v)) v.forEach(json)
+    else if (v !== null && typeof v === 'object') Object.keys(v).forEach(k => json(v[k]))
+  }
+  const any = v => {
+    if (typeof v === 'number') { if (Number.isInteger(v) && v < -2147483647) st = 3 } else if (Array.isArray(v)) v.forEach(any)
+    else if (v !== null && typeof v === 'object' && !(v instanceof Uint8Array)) Object.keys(v).forEach(k => any(v[k]))
+  }
+  doc.store.clients.forEach(structs => structs.forEach(it => {
+    if (it.content === undefined) return   // (a GC struct)
+    const ref = it.content.getRef()
+    if (ref === 6) json(it.content.value)
+    else if (ref === 5) json(it.content.embed)
+    else if (ref === 8) it.content.arr.forEach(any)
+  }))
+  return st
+}
+
 // [[nameHex, status, json (utf8 string)], ...] for the state's roots (doc.share order) and the absent name
 function rootsOf (state) {
   const probe = new Y.Doc()
   Y.applyUpdate(probe, state)
   const names = Array.from(probe.share.keys())
   names.push(ABSENT)
+  const whole = stateRefusal(probe)
   return names.map(name => {
+    if (whole) return [Buffer.from(name, 'utf8').toString('hex'), whole, '']
     const doc = new Y.Doc()   // (a fresh document per ask: getXmlFragment fixes a root's type)
     Y.applyUpdate(doc, state)
     try {
@@ -106,14 +135,15 @@ function rootsOf (state) {
 const fullRow = r => [r[0], r[1], Buffer.from(r[2], 'utf8').toString('hex')]
 const hashRow = r => { const b = Buffer.from(r[2], 'utf8'); return [r[0], r[1], crypto.createHash('sha256').update(b).digest('hex'), b.length] }
 
-// ---- edge sessions: [note, state]
+// ---- sessions: [note, state]
+const frag = d => d.getXmlFragment('default')
+const el = (parent, at, nodeName) => { const e = new Y.XmlElement(nodeName); parent.insert(at, [e]); return e }
+const txt = (parent, at, s, attrs) => { const t = new Y.XmlText(); parent.insert(at, [t]); if (s !== null) t.insert(0, s, attrs); return t }
+const para = (parent, at, s) => { const e = el(parent, at, 'paragraph'); if (s !== null) txt(e, 0, s); return e }
+
 function edges () {
   const out = []
   const one = (note, id, f) => { const d = new Y.Doc(); d.clientID = id; f(d); out.push([note, Y.encodeStateAsUpdate(d)]) }
-  const frag = d => d.getXmlFragment('default')
-  const el = (parent, at, nodeName) => { const e = new Y.XmlElement(nodeName); parent.insert(at, [e]); return e }
-  const txt = (parent, at, s, attrs) => { const t = new Y.XmlText(); parent.insert(at, [t]); if (s !== null) t.insert(0, s, attrs); return t }
-  const para = (parent, at, s) => { const e = el(parent, at, 'paragraph'); if (s !== null) txt(e, 0, s); return e }
   // structure
   one('an empty fragment', 101, d => { const f = frag(d); para(f, 0, 'x'); f.delete(0, 1) })
   one('an XmlText directly under the fragment', 102, d => { const f = frag(d); txt(f, 0, 'top'); para(f, 1, 'after'); txt(f, 2, 'again') })
@@ -223,6 +253,71 @@ function edges () {
   return out
 }
 
+// ---- boundary sessions (tests/golden/json_overflow_v135.json.gz): keys at the edge of an array index, mark names
+// around the hashed form, numbers at the edge of what is written, XmlTexts and refused types between siblings
+const INDEX_KEYS = ['4294967295', '4294967294', '0', '00', '-1', '4294967296', '12345678901', '1.0', '7']
+function boundary () {
+  const out = []
+  const one = (note, id, f) => { const d = new Y.Doc(); d.clientID = id; f(d); out.push([note, Y.encodeStateAsUpdate(d)]) }
+  one('index keys as attributes: ' + INDEX_KEYS.join(' '), 201, d => { const e = para(frag(d), 0, 'x'); for (const k of INDEX_KEYS) e.setAttribute(k, 'v' + k) })
+  one('index keys as marks, set one by one: ' + INDEX_KEYS.join(' '), 202, d => { const t = txt(para(frag(d), 0, null), 0, 'keys'); for (const k of INDEX_KEYS) t.format(0, 4, { [k]: 'v' + k }) })
+  let id = 210
+  for (const k of ['--AbCd0123', '-AbCd0123x', 'c--AbCd012', 'c--AbCd01_2', 'c--AbCd0123x', 'é--AbCd0123', 'c--========']) {
+    one('mark name ' + k, id++, d => { txt(para(frag(d), 0, null), 0, 'marked', { [k]: { id: 7 } }) })
+  }
+  {   // a hashed mark set and nulled around a string that is deleted by a delete set alone (no document cleans the
+      // formats up): the mark is never current at a string, so it is never written
+    const a = new Y.Doc(); a.clientID = 120
+    const b = new Y.Doc(); b.clientID = 121
+    txt(para(frag(a), 0, null), 0, 'tail')
+    const ua = Y.encodeStateAsUpdate(a)
+    Y.applyUpdate(b, ua)
+    let ub = null
+    b.on('update', u => { ub = u })
+    frag(b).get(0).get(0).insert(0, 'x', { 'c--AbCd0123': true })   // clocks of 121: format 0, 'x' 1, format (null) 2
+    out.push(['a hashed mark set and nulled before any live string', Y.mergeUpdates([ua, ub, Uint8Array.from([0, 1, 121, 1, 1, 1])])])
+  }
+  for (const v of [2147483647, -2147483647, 2147483648, -2147483648, 0, -0]) {
+    one('attribute integer ' + (Object.is(v, -0) ? '-0' : String(v)), id++, d => { para(frag(d), 0, 'x').setAttribute('n', v) })
+  }
+  one('mark numbers 1e20, -0, 123456789012', id++, d => { txt(para(frag(d), 0, null), 0, 'nums', { a: 1e20, b: { z: -0 }, c: [123456789012] }) })
+  one('mark number 1e21', id++, d => { txt(para(frag(d), 0, null), 0, 'nums', { a: 1e21 }) })
+  one('a mark key and string values that hold digits, dots and e', id++, d => { txt(para(frag(d), 0, null), 0, 'strs', { '1.5e3': '2.5e10', k: { '1e5': '-3.14', 'e.1': ['0.5', 'e'] } }) })
+  one('mark number of 16 digits', id++, d => { txt(para(frag(d), 0, null), 0, 'nums', { big: { v: 9007199254740992 } }) })
+  one('four XmlTexts in one element: the first ends bold, one is empty, then an element, then text', id++, d => {
+    const e = el(frag(d), 0, 'paragraph')
+    txt(e, 0, 'ends-bold', { bold: true }); txt(e, 1, null); txt(e, 2, 'plain')
+    txt(el(e, 3, 'inner'), 0, 'inside'); txt(e, 4, 'last')
+  })
+  one('empty XmlTexts directly under the fragment, between elements', id++, d => {
+    const f = frag(d)
+    txt(f, 0, null); para(f, 1, 'a'); txt(f, 2, null); txt(f, 3, null); para(f, 4, 'b'); txt(f, 5, null)
+  })
+  one('embed values {} and an array', id++, d => { const t = txt(para(frag(d), 0, null), 0, 'abc'); t.insertEmbed(1, {}); t.insertEmbed(3, [1, [2, 'x'], {}], { bold: true }) })
+  one('refused: a nested XmlFragment child', id++, d => { const f = frag(d); para(f, 0, 'x'); f.insert(1, [new Y.XmlFragment()]) })
+  one('refused: an XmlHook child', id++, d => { const f = frag(d); para(f, 0, 'x'); f.insert(1, [new Y.XmlHook('hook')]) })
+  one('refused: a Y.Text child', id++, d => { const f = frag(d); para(f, 0, 'x'); f.insert(1, [new Y.Text('plain')]) })
+  return out
+}
+
+// --states <in.json> <out.json.gz>: in.json is { source, states: [hex] }; the output holds rootsOf of every state (its
+// roots and the absent name; a JSON of more than HASH_OVER bytes as [nameHex, status, sha256, length]) and the
+// boundary sessions with their states.  Driven by tools/json_overflow_fixture.py.
+const HASH_OVER = 4096
+const sizedRow = r => Buffer.byteLength(r[2], 'utf8') > HASH_OVER ? hashRow(r) : fullRow(r)
+function statesMode (inFile, outFile) {
+  const inp = JSON.parse(fs.readFileSync(inFile, 'utf8'))
+  const doc = {
+    source: inp.source,
+    absent: Buffer.from(ABSENT, 'utf8').toString('hex'),
+    hash_over: HASH_OVER,
+    states: inp.states.map(h => rootsOf(Buffer.from(h, 'hex')).map(sizedRow)),
+    sessions: boundary().map(([note, state]) => ({ note, state: Buffer.from(state).toString('hex'), roots: rootsOf(state).map(sizedRow) }))
+  }
+  fs.writeFileSync(outFile, zlib.gzipSync(Buffer.from(JSON.stringify(doc)), { level: 9 }))
+  console.log(JSON.stringify({ states: doc.states.length, sessions: doc.sessions.length }))
+}
+
 // --time <asks.bin>: the CPU path this replaces, on one core: per ask (tools/snapdev/jsondev.cpp's input: state, root
 // name) a fresh Y.Doc, applyUpdate, the serializer, JSON.stringify.  One JSON line.
 function timeAsks (file, lo, hi) {
@@ -251,6 +346,8 @@ function timeAsks (file, lo, hi) {
 
 if (require.main === module && process.argv[2] === '--time') {
   timeAsks(process.argv[3], process.argv[4] ? parseInt(process.argv[4], 10) : 0, process.argv[5] ? parseInt(process.argv[5], 10) : Infinity)
+} else if (require.main === module && process.argv[2] === '--states') {
+  statesMode(process.argv[3], process.argv[4])
 } else if (require.main === module) {
   const limit = process.argv[3] ? parseInt(process.argv[3], 10) : Infinity
   const inputs = {}
