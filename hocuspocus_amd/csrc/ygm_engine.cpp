@@ -236,7 +236,7 @@ static int read_meta(ygm_ctx* c, hipStream_t s, Meta& m, const void* slot) {
 }
 // Every read-back smaller than a Meta goes through the three helpers below (through the pinned h_meta), so
 // ygm_stats_t.host_syncs counts each of the calls' waits.
-static_assert(sizeof(Meta) >= 4 * sizeof(uint64_t), "h_meta holds read_u64s' four values");
+static_assert(sizeof(Meta) >= 5 * sizeof(uint64_t), "h_meta holds read_u64s' four values and the large tier's five counters");
 // one 8-byte value from each of up to four device places, read with one wait
 static int read_u64s(ygm_ctx* c, hipStream_t s, std::initializer_list<const uint64_t*> src, uint64_t* v) {
   if (src.size() > 4) return YGM_EINVAL;
@@ -393,6 +393,7 @@ int ygm_merge_v1_device_finish(ygm_ctx* c, ygm_device_result* out) {
     if (!P.wide_route) { n_gen = m.wide_defer; c->stats.docs_lean_wide += lean_defer - m.wide_defer; }
   }
   uint32_t n_seq = 0;
+  unsigned long long cnt[5] = {0, 0, 0, 0, 0};   // tier 4: the scan's counters ([4], the slow queue's entries: the YGM_TIER_COUNTS line's only)
   if (m.fb_count) {  // tier 4: large [snapshot, ...log] documents, one wave each; the rest go on to tier 5
     const uint64_t blk_cap = m.fb_bytes / 4 + 2ull * m.fb_count + 16, rec_cap = m.fb_bytes + 2ull * m.fb_count + 16;
     if (!c->big_blk.ensure(blk_cap * ygm_k_big_blk_bytes()) || !c->big_rec.ensure(rec_cap * ygm_k_big_rec_bytes()) ||
@@ -406,7 +407,6 @@ int ygm_merge_v1_device_finish(ygm_ctx* c, ygm_device_result* out) {
       return YGM_EDEVICE;
     unsigned long long* d_cnt; uint32_t *llist, *mlist;
     ygm_k_big_lists(c->big_scan.p, m.fb_count, m.fb_bytes, &d_cnt, &llist, &mlist);
-    unsigned long long cnt[4];
     c->stats.host_syncs++;
     HIPCHK(hipMemcpyAsync(c->h_meta, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -472,6 +472,10 @@ int ygm_merge_v1_device_finish(ygm_ctx* c, ygm_device_result* out) {
   if (getenv("YGM_TIER_COUNTS"))
     fprintf(stderr, "ygm merge tiers: docs %u lean_defer %u wide_defer %u to_wave %u to_workgroup %u to_large %u to_seq %u\n", P.n_docs,
             m.lean_defer, m.wide_defer, m.route_n, m.defer_count, m.fb_count, m.big_defer);
+  // ... and, when tier 4 ran, the large-document tier's: the scan's carves and slow queue, the two lists, the hand-ons
+  if (m.fb_count && getenv("YGM_TIER_COUNTS"))
+    fprintf(stderr, "ygm large tiers: docs %u positions %llu tasks %llu slow_queue %llu wide_first %llu mid_first %llu mid_to_wide %u to_seq %u\n",
+            m.fb_count, cnt[0], cnt[1], cnt[4], cnt[2], cnt[3], m.mid_defer, m.big_defer);
   const uint64_t extent = P.slot_total + m.cursor;
   c->stats.calls++; c->stats.docs += P.n_docs; c->stats.updates += P.n_upd;
   c->stats.docs_fast += n_gen - m.fb_count;   // finished by the wave / workgroup tiers (tier 4 counted above)

@@ -3478,6 +3478,7 @@ void ygm_k_big_lists(void* scan, uint32_t n_fb, uint64_t fb_bytes, unsigned long
   big_scan_layout(n_fb, fb_bytes, S, (uint8_t*)scan, total);
   *cnt = S.cnt; *llist = S.llist; *mlist = S.mlist;
 }
+static uint32_t grid_knob(const char* name);   // (the launchers' testing knobs, below)
 size_t ygm_k_big_scan_bytes(uint32_t n_fb, uint64_t fb_bytes) { BigScan S; size_t t; big_scan_layout(n_fb, fb_bytes, S, nullptr, t); return t; }
 int ygm_k_launch_big_scan(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list,
                           uint32_t n_fb, uint32_t flags, void* scan, uint64_t fb_bytes, hipStream_t s) {
@@ -3487,9 +3488,12 @@ int ygm_k_launch_big_scan(const uint8_t* arena, const uint64_t* upd_off, const u
   if (hipMemsetAsync(S.cnt, 0, 64, s) != hipSuccess) return ygm_launch_rc(__func__);
   hipLaunchKernelGGL(k_big_pick, dim3((n_fb + 15) / 16), dim3(1024), 0, s, arena, upd_off, doc_upd, fb_list, n_fb, S);
   // the scan: a persistent grid over the tasks (at most 16 workgroups per CU; the task count is on the device)
-  const uint64_t g = S.ntask_cap < 16ull * device_cus() ? S.ntask_cap : 16ull * device_cus();
+  // YGM_BIG_SCAN_GRID (testing knob, as YGM_WAVE_GRID): a positive value replaces both grids, so a workgroup takes
+  // many tasks / queue blocks in turn through the same LDS (s_q and s_b; k_big_val's s_cnt and s_ix)
+  const uint32_t env = grid_knob("YGM_BIG_SCAN_GRID");
+  const uint64_t g = env ? env : S.ntask_cap < 16ull * device_cus() ? S.ntask_cap : 16ull * device_cus();
   hipLaunchKernelGGL(k_big_scan, dim3((uint32_t)g), dim3(256), 0, s, arena, upd_off, doc_upd, fb_list, flags, S);
-  const uint64_t gv = S.vq_cap / 256 + 1 < 8ull * device_cus() ? S.vq_cap / 256 + 1 : 8ull * device_cus();
+  const uint64_t gv = env ? env : S.vq_cap / 256 + 1 < 8ull * device_cus() ? S.vq_cap / 256 + 1 : 8ull * device_cus();
   hipLaunchKernelGGL(k_big_val, dim3((uint32_t)gv), dim3(256), 0, s, arena, upd_off, doc_upd, fb_list, flags, S);
   return ygm_launch_rc(__func__);
 }
