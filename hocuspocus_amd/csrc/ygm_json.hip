@@ -1,4 +1,5 @@
-// ygm_json.hip -- stored documents as ProseMirror / Tiptap JSON (ygm_json_v1; ygm_json.hpp for the semantics):
+// ygm_json.hip -- stored documents as ProseMirror / Tiptap JSON (ygm_json_v1, and ygm_json_fields_v1's object of
+// several fields; ygm_json.hpp for the semantics):
 //   k_json : a wave's documents staged in LDS, dpw per wave (staging, lane prologue and epilogue: ygm_docstage.hpp),
 //            workspaces from the snapshot's count and scan launches (ygm_k_launch_snap_plan), the JSON in the
 //            workspace's output region.
@@ -26,6 +27,10 @@ using docstage::Lane;
 // again == 0: documents [0, n_docs), dpw per wave.  again == 1: the n_list documents of list[], the lanes of a wave
 // taking consecutive entries; document d writes out_len[d] bytes (the length its first run recorded) at out_off[d].
 // ovf_base: where the overflow region starts in ws (after the workspaces).
+// FIELDS (ygm_json_fields_v1): names / name_off hold a field list per document and the JSON is the object of its
+// fields; staging, workspaces and the overflow route are the same, so the single-field kernel is its own instantiation
+// and carries none of the fields code.
+template <bool FIELDS>
 __global__ __launch_bounds__(docstage::NT) void k_json(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
                                                const uint8_t* __restrict__ names, const uint64_t* __restrict__ name_off, uint32_t n_docs,
                                                uint32_t flags, uint32_t kind, const uint4* __restrict__ cnt, const uint64_t* __restrict__ ws_off,
@@ -43,7 +48,7 @@ __global__ __launch_bounds__(docstage::NT) void k_json(const uint8_t* __restrict
       uint32_t oo = 0, ol = 0;
       snap::Caps k;
       int st = docstage::lane_caps(nb >= na && nb - na < (1ull << 30), a, b, c, k);
-      if (st == ST_OK) st = json::json_doc(L.in, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, oo, ol);
+      if (st == ST_OK) st = json::json_doc<FIELDS>(L.in, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, oo, ol);
       if (st == json::ST_JSON_MORE) {   // ol: the length needed
         const uint32_t i = atomicAdd(&meta->fb_count, 1u);
         const unsigned long long at = atomicAdd(&meta->cursor, (unsigned long long)snap::al16(ol));
@@ -62,7 +67,7 @@ __global__ __launch_bounds__(docstage::NT) void k_json(const uint8_t* __restrict
       const uint32_t need = (uint32_t)out_len[d];
       const snap::Caps k = snap::caps_of(c.x, c.y, c.z, c.w);
       uint32_t ol = 0;
-      int st = json::json_run(arena + a, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, ws + out_off[d], need, ol);
+      int st = json::json_run<FIELDS>(arena + a, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, ws + out_off[d], need, ol);
       if (st == json::ST_JSON_MORE || (st == ST_OK && ol != need)) st = ST_NOMEM;   // (cannot happen: the same walk twice)
       out_len[d] = st == ST_OK ? ol : 0u;   // (out_off[d]: the place the first run claimed)
       status[d] = st;
@@ -79,16 +84,17 @@ using namespace ygm;
 extern "C" {
 
 // over the workspaces ygm_k_launch_snap_plan sized (cnt, ws_off); dpw as ygm_k_launch_text.  again: the listed
-// documents' second run (n_list of them)
+// documents' second run (n_list of them).  fields: names hold field lists (ygm_json_fields_v1)
 int ygm_k_launch_json(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
                       uint32_t flags, uint32_t kind, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
                       uint64_t* out_len, int32_t* status, void* meta, uint64_t base, uint64_t ovf_base, uint32_t* list, uint32_t n_list,
-                      int again, hipStream_t s) {
+                      int again, int fields, hipStream_t s) {
   const uint32_t n = again ? n_list : n_docs;
   if (n == 0) return 0;
   const uint32_t dpw = docstage::docs_per_wave(0);
   const uint32_t g = (n + dpw - 1) / dpw;
-  hipLaunchKernelGGL(k_json, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off, ws,
+  auto k = fields ? k_json<true> : k_json<false>;
+  hipLaunchKernelGGL(k, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off, ws,
                      out_off, out_len, status, (DocMeta*)meta, dpw, base, ovf_base, list, n_list, again ? 1u : 0u);
   return ygm_launch_rc(__func__);
 }

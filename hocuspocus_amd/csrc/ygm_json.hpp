@@ -25,6 +25,8 @@
 // Output size: every op repeats the current marks, so the JSON is not bounded by Caps::out.  OutCap counts past its
 // cap: json_run reports the needed length (ST_JSON_MORE) and the caller runs the document again into a region of
 // that size (k_json's second launch; tools/snapdev/jsondev.cpp).
+// ygm_json_fields_v1 -- every asked field of a document as one object keyed by field -- is the same load followed by
+// emit_fields, which writes each field's root with the same walk (emit_root); see there.
 #pragma once
 #include "ygm_text.hpp"
 #include "ygm_v2.hpp"
@@ -192,10 +194,10 @@ struct Walk {
 // a well-formed document (n_it + n_ty + 1 steps), a piece chain has at most n_pc pieces, a type's entries at most
 // n_me.  A list that cycles exhausts the bound and ends in ST_UNSUP.  The stack holds the ContentType items the walk
 // is inside of; what it needs on the way back (element or text) is read from the item again.
-YDEV void emit_json(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32_t kind, snap::OutCap& o) {
+// {"type":"doc","content":[...]} of root type `root` (a ty[] index), -1: the empty document.  D.tx and D.st are the
+// walk's alone and start empty: roots can be written one after another.
+YDEV void emit_root(snap::Doc& D, int32_t root, snap::OutCap& o) {
   using namespace snap;
-  (void)kind;
-  const int32_t root = find_root(D, name, name_len);
   lit(o, "{\"type\":\"doc\",\"content\":[");
   if (root < 0) { lit(o, "]}"); return; }   // doc.getXmlFragment(name) of a name the update has no root for: an empty fragment
   Walk W{D, o, 0};
@@ -281,9 +283,126 @@ YDEV void emit_json(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32
   }
   lit(o, "]}");
 }
+YDEV void emit_json(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32_t kind, snap::OutCap& o) {
+  (void)kind;
+  emit_root(D, snap::find_root(D, name, name_len), o);
+}
+
+// ---- every asked field of a document as one object (ygm_json_fields_v1):
+//     utf8(JSON.stringify(TiptapTransformer.fromYdoc(doc, fields)))      = { "<field>": <emit_root of that field>, ... }
+// A field list is zero or more lib0 varStrings back to back.  No name: every key of doc.share -- the root types in
+// ty[] order, which is the order yjs creates them in while it reads the structs (Doc::parse calls root_type where
+// readClientsStructRefs calls doc.get).  The object's keys follow data[field] = ... assignments in list order:
+// canonical array-index keys ascending, then the others by first assignment; a repeated name keeps its first place.
+// data["__proto__"] = ... sets the prototype and the key vanishes: refused (ST_UNSUP) where the field stands in that
+// order.  Nothing is kept per field: the list (or ty[]) is decoded again for every selection, as Walk::marks does over
+// the marks Map, so the cost is quadratic in the names (at most FIELDS_MAX) and the workspace holds nothing new.
+constexpr uint32_t FIELDS_MAX = 1024u;
+
+// a well-formed field list: varuints minimal and of at most 5 bytes, lengths inside the list, names strict UTF-8 (they
+// are written into the output), at most FIELDS_MAX names.  Anything else: ST_INVAL for the document.
+YDEV int fields_check(const uint8_t* fl, uint32_t fn) {
+  uint32_t pos = 0, count = 0;
+  while (pos < fn) {
+    uint64_t len = 0; uint32_t nb = 0; uint8_t r;
+    do {
+      if (pos >= fn || nb == 5) return ST_INVAL;
+      r = fl[pos++];
+      len |= (uint64_t)(r & 127) << (7 * nb++);
+    } while (r & 128);
+    if ((nb > 1 && r == 0) || len > (uint64_t)(fn - pos)) return ST_INVAL;
+    if (utf8_u16(fl + pos, (uint32_t)len) < 0) return ST_INVAL;
+    pos += (uint32_t)len;
+    if (++count > FIELDS_MAX) return ST_INVAL;
+  }
+  return ST_OK;
+}
+
+// the asked fields in turn: the names of a checked list, or (an empty list) the document's root types
+struct Fields {
+  const snap::Doc& D;
+  const uint8_t* fl; uint32_t fn;
+  uint32_t pos;   // the list's byte position, or the ty[] index
+  YDEV bool all() const { return fn == 0; }
+  // the next field: its name, where it stands (list position / ty[] index) and its root type (-1: none)
+  YDEV bool next(const uint8_t*& s, uint32_t& n, uint32_t& at, int32_t& root) {
+    if (all()) {
+      while (pos < D.n_ty && D.ty[pos].item != -1) pos++;
+      if (pos >= D.n_ty) return false;
+      at = pos; root = (int32_t)pos; s = D.in + D.ty[pos].name_off; n = D.ty[pos].name_len;
+      pos++;
+      return true;
+    }
+    if (pos >= fn) return false;
+    at = pos;
+    uint32_t len = 0, sh = 0; uint8_t r;
+    do { r = fl[pos++]; len |= (uint32_t)(r & 127) << sh; sh += 7; } while (r & 128);   // (checked: ends inside the list)
+    s = fl + pos; n = len; pos += len;
+    root = -2;   // (looked up when the field is written)
+    return true;
+  }
+  // list form: does the name stand in the list before position `at`?  (root types have one name each)
+  YDEV bool before(uint32_t at, const uint8_t* s, uint32_t n) const {
+    if (all()) return false;
+    Fields f{D, fl, fn, 0};
+    const uint8_t* t; uint32_t tn, ta; int32_t tr;
+    while (f.next(t, tn, ta, tr) && ta < at) {
+      if (tn != n) continue;
+      uint32_t i = 0;
+      while (i < n && t[i] == s[i]) i++;
+      if (i == n) return true;
+    }
+    return false;
+  }
+};
+
+YDEV void emit_fields(snap::Doc& D, const uint8_t* fl, uint32_t fn, snap::OutCap& o) {
+  Fields F{D, fl, fn, 0};
+  bool first = true, index_pass = true, any_prev = false;
+  uint64_t prev = 0;
+  for (;;) {
+    const uint8_t* s = nullptr; uint32_t n = 0, at = 0; int32_t root = -1;
+    bool got = false;
+    if (index_pass) {   // the smallest index key above the last one written (equal names give equal values: written once)
+      uint64_t best = 0;
+      const uint8_t* t; uint32_t tn, ta; int32_t tr;
+      F.pos = 0;
+      while (F.next(t, tn, ta, tr)) {
+        uint64_t v;
+        if (!index_key(t, tn, v) || (any_prev && v <= prev)) continue;
+        if (!got || v < best) { best = v; s = t; n = tn; root = tr; got = true; }
+      }
+      if (got) { prev = best; any_prev = true; }
+      else { index_pass = false; F.pos = 0; }
+    }
+    if (!index_pass) {   // then the other names, each where it stands first
+      uint64_t v;
+      while ((got = F.next(s, n, at, root)) && (index_key(s, n, v) || F.before(at, s, n))) {}
+      if (!got) break;
+    }
+    if (n == 9) {
+      const char* pr = "__proto__";
+      uint32_t i = 0;
+      while (i < 9 && s[i] == (uint8_t)pr[i]) i++;
+      if (i == 9) { D.fail(snap::ST_UNSUP); return; }
+    }
+    o.b(first ? '{' : ',');
+    first = false;
+    quoted(o, s, n); o.b(':');
+    if (o.n >= JSON_MAX) { D.fail(ST_NOMEM); return; }
+    emit_root(D, root == -2 ? snap::find_root(D, s, n) : root, o);
+    if (D.err) return;
+    if (o.n >= JSON_MAX) { D.fail(ST_NOMEM); return; }
+  }
+  if (first) o.b('{');
+  o.b('}');
+}
 
 // the JSON of root `name` of in[0, n) over a workspace carved from ws, at most out_cap bytes at out.  ST_JSON_MORE:
 // out_len is the length a second run needs.  Pending structs / a pending delete set: the integrated part (ST_OK).
+// FIELDS: name[0, name_len) is a field list and the JSON the object of its fields (emit_fields); the state's own
+// status comes before the list's.
+template <bool FIELDS = false>
 YDEV_NI int json_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, const uint8_t* name,
                      uint32_t name_len, uint32_t kind, uint8_t* out, uint32_t out_cap, uint32_t& out_len) {
   snap::Doc D;
@@ -292,17 +411,21 @@ YDEV_NI int json_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws,
   D.load();
   if (D.err) return D.err;
   snap::OutCap o{out, 0, out_cap};
-  emit_json(D, name, name_len, kind, o);
+  if (FIELDS) {
+    if (fields_check(name, name_len)) return ST_INVAL;
+    emit_fields(D, name, name_len, o);
+  } else emit_json(D, name, name_len, kind, o);
   if (D.err) return D.err;
   if (o.n >= JSON_MAX) return ST_NOMEM;
   out_len = o.n;
   return o.n > o.cap ? ST_JSON_MORE : ST_OK;
 }
 // document d's workspace from caps_of, its output region at the end (as text::text_doc)
+template <bool FIELDS = false>
 YDEV int json_doc(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, const uint8_t* name, uint32_t name_len,
                   uint32_t kind, uint32_t& out_off, uint32_t& out_len) {
   out_off = (uint32_t)snap::ws_core_bytes(k);
-  return json_run(in, n, flags, ws, k, name, name_len, kind, ws + out_off, k.out, out_len);
+  return json_run<FIELDS>(in, n, flags, ws, k, name, name_len, kind, ws + out_off, k.out, out_len);
 }
 
 }  // namespace json

@@ -80,7 +80,8 @@ EXPORTS = ("ygm_open", "ygm_close", "ygm_merge_v1", "ygm_diff_v1", "ygm_sv_from_
            "ygm_snapshot_opts_v1_device", "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device",
            "ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device",
            "ygm_version_restore_shared_v1", "ygm_version_restore_shared_v1_device",
-           "ygm_text_v1", "ygm_text_v1_device", "ygm_json_v1", "ygm_json_v1_device")
+           "ygm_text_v1", "ygm_text_v1_device", "ygm_json_v1", "ygm_json_v1_device",
+           "ygm_json_fields_v1", "ygm_json_fields_v1_device")
 
 
 def lib():
@@ -147,7 +148,9 @@ def lib():
         L.ygm_text_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
         L.ygm_json_v1.argtypes = [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
         L.ygm_json_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
-        for f in ("ygm_text_v1", "ygm_text_v1_device", "ygm_json_v1", "ygm_json_v1_device"):
+        L.ygm_json_fields_v1.argtypes = L.ygm_json_v1.argtypes
+        L.ygm_json_fields_v1_device.argtypes = L.ygm_json_v1_device.argtypes
+        for f in ("ygm_text_v1", "ygm_text_v1_device", "ygm_json_v1", "ygm_json_v1_device", "ygm_json_fields_v1", "ygm_json_fields_v1_device"):
             getattr(L, f).restype = i32
         L.ygm_merge_v2.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
         L.ygm_diff_v2.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
@@ -183,6 +186,21 @@ def _pack(blobs):
     if blobs:
         np.cumsum(np.fromiter((len(b) for b in blobs), dtype=np.uint64, count=len(blobs)), out=off[1:])
     return arena, off
+
+
+def encode_fields(fields) -> bytes:
+    """A document's field list for ygm_json_fields_v1: None or an empty list gives no bytes (every key of doc.share),
+    names (str or bytes) give their lib0 varStrings back to back -- a varuint byte length, then the UTF-8 bytes."""
+    out = bytearray()
+    for f in fields or ():
+        b = f.encode() if isinstance(f, str) else bytes(f)
+        n = len(b)
+        while n > 127:
+            out.append(0x80 | (n & 127))
+            n >>= 7
+        out.append(n)
+        out += b
+    return bytes(out)
 
 
 def _ptr(a):
@@ -550,6 +568,32 @@ class Engine:
         r = _DevResult()
         st = lib().ygm_json_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off), _dptr(d_names),
                                       _dptr(d_name_off), int(kind), n_docs, stream or None, ctypes.byref(r))
+        if st != OK:
+            raise YjsError(st)
+        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+
+    def json_fields_batch(self, states, fields, kind=JSON_PROSEMIRROR):
+        """Every asked field of stored documents as one JSON object (ygm_json_fields_v1): for
+        doc = Y.applyUpdate(new Y.Doc(), state), the UTF-8 of JSON.stringify(TiptapTransformer.fromYdoc(doc, fields))
+        -- the body of a change webhook -> list of bytes, or a YjsError for a refused document.  fields: per state
+        None or [] (every key of doc.share) or a list of names (str or bytes); see encode_fields."""
+        if len(states) != len(fields):
+            raise ValueError("one field list per state")
+        sa, so = _pack([bytes(s) for s in states])
+        fa, fo = _pack([encode_fields(f) for f in fields])
+        res = _Result()
+        st = lib().ygm_json_fields_v1(self._ctx, sa or None, _ptr(so), fa or None, _ptr(fo), int(kind), len(states), ctypes.byref(res))
+        if st != OK:
+            raise YjsError(st)
+        return [b if s == OK else YjsError(s) for s, b in self._unpack(res)]
+
+    def json_fields_device(self, d_states, states_bytes, d_state_off, d_fields, d_field_off, n_docs, kind=JSON_PROSEMIRROR,
+                           stream=0) -> "DeviceResult":
+        """Device-resident form (ygm_json_fields_v1_device): the states arena followed by TAIL_PAD readable bytes; the
+        field lists encoded as encode_fields does."""
+        r = _DevResult()
+        st = lib().ygm_json_fields_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off),
+                                             _dptr(d_fields), _dptr(d_field_off), int(kind), n_docs, stream or None, ctypes.byref(r))
         if st != OK:
             raise YjsError(st)
         return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)

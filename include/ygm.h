@@ -232,11 +232,45 @@ int ygm_text_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, 
  * states / state_off / names / name_off, tail padding, packing and the other statuses as ygm_text_v1.  A kind other
  * than YGM_JSON_PROSEMIRROR is YGM_EINVAL for the call (room for toJSON of Map and Array roots).  No options form:
  * the JSON depends neither on YGM_F_COMPAT_135 nor on garbage collection.
- * (Replaces packages/extension-webhook/src/index.ts:119, packages/transformer/src/Prosemirror.ts:26: the document a
- * change webhook or a REST read sends, transformer.fromYdoc(document, fieldName).) */
+ * (Replaces packages/transformer/src/Prosemirror.ts:26: transformer.fromYdoc(document, fieldName) with one field
+ * name, what a REST read of one field sends.  The body of a change webhook is ygm_json_fields_v1 below.) */
 #define YGM_JSON_PROSEMIRROR 0u
 int ygm_json_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *names,
                 const uint64_t *name_off, uint32_t kind, uint32_t n_docs, ygm_result *out);
+/* ---- every field of a stored document as one JSON object ----------------------
+ * The multi-field form of ygm_json_v1: one load of the state serializes every asked root, or all roots.  For
+ * doc = Y.applyUpdate(new Y.Doc(), state), document d's output is the UTF-8 of
+ *     JSON.stringify(TiptapTransformer.fromYdoc(doc, fields))        fields: undefined | string[]
+ * that is { "<field>": <what ygm_json_v1 gives for that field>, ... }.
+ * fields / field_off hold one field list per document (n_docs + 1 offsets; fields may be NULL when every list is
+ * empty).  A list is zero or more lib0 varStrings back to back, each a varuint byte length followed by UTF-8 bytes:
+ *   zero bytes         every key of doc.share -- fromYdoc(document) with no field name, or with []
+ *   one or more names  fromYdoc(document, [names...]); the empty name "" is a valid field
+ * Key order is JavaScript's own-property order of the data[field] = ... assignments made in list order (for all
+ * fields: doc.share insertion order, the order in which the state's structs first name their roots): canonical
+ * array-index keys ascending, then the other keys in first-assignment order.  A name repeated in a list keeps its
+ * first position and appears once.  Keys are escaped as JSON.stringify escapes strings.  A listed name the state has
+ * no root for gives {"type":"doc","content":[]}; a document with no roots, asked for all fields, gives {}; a root
+ * that has only map entries serializes as an empty doc; a state with pending structs / a pending delete set is read
+ * through its integrated part with YGM_OK, and roots that only pending structs name are in doc.share, so they
+ * appear, empty, in the all-fields form.
+ * A list gives its own document YGM_EINVAL, and nothing else, when a length runs past the list's end, a varuint is
+ * non-minimal or longer than 5 bytes, a name is not well-formed UTF-8 (it is written into the output), or the list
+ * holds more than 1024 names.
+ * Refusals leave length 0 and affect only their own document:
+ *   a state's parse or integration status (as ygm_json_v1) comes before anything about the fields, its list included
+ *   the refusal ygm_json_v1 gives for the first refusing field in output order (index keys ascending, then the
+ *   rest; the reference throws, so the order only has to be fixed)
+ *   a field named __proto__, where it stands in that order (in JavaScript the assignment sets the prototype and the
+ *   key silently vanishes; the caller's yjs path reproduces that)                          YGM_EUNSUPPORTED
+ *   an object of 2^31 bytes or more                                                        YGM_ENOMEM
+ * The object is larger than any of its roots: the second run of ygm_json_v1 covers it in the same way.  states /
+ * state_off, tail padding, packing and the other statuses as ygm_json_v1; a kind other than YGM_JSON_PROSEMIRROR is
+ * YGM_EINVAL for the call.  No options form: neither YGM_F_COMPAT_135 nor garbage collection changes the result.
+ * (Replaces packages/extension-webhook/src/index.ts:119 -- the `document` of every change webhook,
+ * transformer.fromYdoc(data.document) -- and packages/transformer/src/Prosemirror.ts:29-39.) */
+int ygm_json_fields_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *fields,
+                       const uint64_t *field_off, uint32_t kind, uint32_t n_docs, ygm_result *out);
 /* SyncStep2 payload of a stored document: Y.encodeStateAsUpdate(doc, sv) for doc = Y.applyUpdate(new Y.Doc(), state)
  * -- what the reference sends in reply to a SyncStep1 (packages/server/src/MessageReceiver.ts:137-138) for a
  * document loaded from stored bytes (extension-database Database.ts:44-50).  Computed as the doc-normalized
@@ -439,10 +473,16 @@ int ygm_text_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_by
 /* ygm_json_v1, device-resident, as ygm_text_v1_device: 64 readable bytes must follow both arenas, results are not
  * packed (a document's JSON lies in its workspace's output region, or in the overflow region after the workspaces
  * when it ran a second time), payload_bytes is the sum of the lengths.
- * (Replaces packages/extension-webhook/src/index.ts:119, packages/transformer/src/Prosemirror.ts:26, as ygm_json_v1.) */
+ * (Replaces packages/transformer/src/Prosemirror.ts:26, as ygm_json_v1.) */
 int ygm_json_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                        const uint8_t *d_names, const uint64_t *d_name_off, uint32_t kind, uint32_t n_docs, void *stream,
                        ygm_device_result *out);
+/* ygm_json_fields_v1, device-resident: tail padding, the unpacked result and payload_bytes as ygm_json_v1_device; a
+ * field list may start at any byte of its arena.
+ * (Replaces packages/extension-webhook/src/index.ts:119, packages/transformer/src/Prosemirror.ts:29-39.) */
+int ygm_json_fields_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
+                              const uint8_t *d_fields, const uint64_t *d_field_off, uint32_t kind, uint32_t n_docs,
+                              void *stream, ygm_device_result *out);
 int ygm_sync_step2_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                              const uint8_t *d_sv_arena, const uint64_t *d_sv_off, uint32_t n_docs, void *stream,
                              ygm_device_result *out);

@@ -296,6 +296,7 @@ static void job_execute(Job *j) {
   else if (j->op == 16) j->rc = ygm_version_restore_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->opt, j->n_docs, &r);
   else if (j->op == 18) j->rc = ygm_text_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_upd, j->n_docs, &r);   /* (n_upd: the mode) */
   else if (j->op == 19) j->rc = ygm_json_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_upd, j->n_docs, &r);   /* (n_upd: the kind) */
+  else if (j->op == 20) j->rc = ygm_json_fields_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_upd, j->n_docs, &r);   /* (sv: the field lists) */
   else if (j->op == 17) j->rc = ygm_version_restore_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->opt, j->n_upd, &r);
   else j->rc = ygm_sv_from_update_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
   if (j->rc != YGM_OK) return;
@@ -467,7 +468,7 @@ static napi_value js_diff(napi_env env, napi_callback_info info) {
   if (j->op == 18) {   /* text(handle, states, stateLens, names, nameLens, mode): YGM_TEXT_FLAT / YGM_TEXT_DEEP, kept in n_upd */
     if (argc < 6 || napi_get_value_uint32(env, argv[5], &j->n_upd) != napi_ok) { job_free(j); napi_throw_type_error(env, NULL, "text: mode (0 flat, 1 deep)"); return NULL; }
   }
-  if (j->op == 19) {   /* json(handle, states, stateLens, names, nameLens, kind): YGM_JSON_PROSEMIRROR, kept in n_upd */
+  if (j->op == 19 || j->op == 20) {   /* json / jsonFields(handle, states, stateLens, names | field lists, their lens, kind): YGM_JSON_PROSEMIRROR, kept in n_upd */
     if (argc < 6 || napi_get_value_uint32(env, argv[5], &j->n_upd) != napi_ok) { job_free(j); napi_throw_type_error(env, NULL, "json: kind (0 ProseMirror)"); return NULL; }
   }
   if ((j->op == 5 || j->op == 16) && get_opts(env, argc, argv, 5, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "step2Many / restoreVersionMany: one option byte per state"); return NULL; }
@@ -596,6 +597,9 @@ static napi_value init(napi_env env, napi_value exports) {
     { "text", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)18 },
     /* stored documents as ProseMirror / Tiptap JSON per (state, root name): transformer.fromYdoc(doc, name) (ygm_json_v1) */
     { "json", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)19 },
+    /* every asked field of stored documents as one JSON object per (state, field list): transformer.fromYdoc(doc) /
+       fromYdoc(doc, [names]) -- a list is lib0 varStrings back to back, none: every root (ygm_json_fields_v1) */
+    { "jsonFields", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)20 },
     { "stats", NULL, js_stats, NULL, NULL, NULL, napi_default, NULL },
     { "strerror", NULL, js_strerror, NULL, NULL, NULL, napi_default, NULL },
   };

@@ -13,6 +13,8 @@ export interface DocOptions { gc?: boolean }
 /** one option per document or state: an option byte (1 = no-GC), true (no-GC), or DocOptions; or the bytes themselves */
 export type DocOptionList = ArrayLike<number | boolean | DocOptions> | Uint8Array
 
+/** the fields of a document to serialize: null, undefined or [] for every key of doc.share, else their names */
+export type FieldList = (string | Uint8Array)[] | null | undefined
 export interface GpuEngineOptions { device?: number; compat135?: boolean; batchWindowMs?: number; maxBatchDocs?: number }
 
 export declare class GpuEngine {
@@ -52,6 +54,10 @@ export declare class GpuEngine {
   /** stored documents as ProseMirror / Tiptap JSON: JSON.stringify(TiptapTransformer.fromYdoc(doc, names[i])) of
    *  doc = Y.applyUpdate(new Y.Doc(), states[i]); a document outside the envelope gives a YgmError in its place */
   jsonMany (states: Uint8Array[], names: (string | Uint8Array)[]): Promise<(string | YgmError)[]>
+  /** every asked field of stored documents as one JSON object: JSON.stringify(TiptapTransformer.fromYdoc(doc, fields[i])) of
+   *  doc = Y.applyUpdate(new Y.Doc(), states[i]) -- a change webhook's `document`; fields[i]: null / [] for every key of
+   *  doc.share, or the names; one load of a state serves all its fields; a refusing field or one named __proto__ gives a YgmError */
+  jsonFieldsMany (states: Uint8Array[], fields: (FieldList)[]): Promise<(string | YgmError)[]>
   /** Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), new Y.Doc(opts))) of doc =
    *  Y.applyUpdate(new Y.Doc({ gc: false }), state); several versions of one document: restoreVersionShared */
   restoreVersion (state: Uint8Array, version: Uint8Array, opts?: DocOptions): Promise<Uint8Array>
@@ -92,6 +98,8 @@ export declare class GpuEnginePool {
   /** docNames[i] routes states[i]; names[i] is its root name */
   textMany (docNames: string[], states: Uint8Array[], names: (string | Uint8Array)[], opts?: { deep?: boolean }): Promise<(string | YgmError)[]>
   jsonMany (docNames: string[], states: Uint8Array[], names: (string | Uint8Array)[]): Promise<(string | YgmError)[]>
+  /** docNames[i] routes states[i]; fields[i] is its field list */
+  jsonFieldsMany (docNames: string[], states: Uint8Array[], fields: (FieldList)[]): Promise<(string | YgmError)[]>
   restoreVersionMany (names: string[], states: Uint8Array[], versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** names[i] naming states[i], routed as step2Shared; opts: one option per ask */
   restoreVersionShared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
@@ -173,10 +181,12 @@ export declare class GpuMerge implements Extension {
   /** restoreVersions followed by one text batch over the fulfilled results, settled per entry */
   versionTexts (entries: { documentName: string, version: Uint8Array, gc?: boolean }[], opts?: { field?: string, deep?: boolean }): Promise<({ status: 'fulfilled', value: string } | { status: 'rejected', reason: Error })[]>
   /** what each loaded document is: JSON.stringify(TiptapTransformer.fromYdoc(document, field)) (field 'default'), or the
-   *  parsed object with parse: true, one GPU batch; unloaded documents are left out, refused ones left out and named in `unserialized` */
-  jsonOf (names: string[], opts?: { field?: string, parse?: boolean }): Promise<Map<string, string | object>>
-  /** restoreVersions followed by one JSON batch over the fulfilled results, settled per entry */
-  versionJson (entries: { documentName: string, version: Uint8Array, gc?: boolean }[], opts?: { field?: string, parse?: boolean }): Promise<({ status: 'fulfilled', value: string | object } | { status: 'rejected', reason: Error })[]>
+   *  parsed object with parse: true, one GPU batch; unloaded documents are left out, refused ones left out and named in `unserialized`.
+   *  field: a root name; null or [] for every field (fromYdoc(document), the webhook body); string[] for those fields --
+   *  the last two give the object keyed by field */
+  jsonOf (names: string[], opts?: { field?: string | FieldList, parse?: boolean }): Promise<Map<string, string | object>>
+  /** restoreVersions followed by one JSON batch over the fulfilled results, settled per entry; field as jsonOf's */
+  versionJson (entries: { documentName: string, version: Uint8Array, gc?: boolean }[], opts?: { field?: string | FieldList, parse?: boolean }): Promise<({ status: 'fulfilled', value: string | object } | { status: 'rejected', reason: Error })[]>
   /** documents whose JSON the engine refused in jsonOf / versionJson: the caller keeps its yjs path (transformer.fromYdoc) for them */
   unserialized: { documentName: string, code: string }[]
   /** batched SyncStep1 responder over the captured state (snapshot + updates since) */

@@ -120,6 +120,24 @@ const DOC_NO_GC = 1
 const TEXT_FLAT = 0; const TEXT_DEEP = 1
 /** YGM_JSON_PROSEMIRROR: the one kind of ygm_json_v1 */
 const JSON_PROSEMIRROR = 0
+/**
+ * A document's field list for ygm_json_fields_v1: null, undefined or [] give no bytes (every key of doc.share); names
+ * (strings or UTF-8 bytes) give their lib0 varStrings back to back -- a varuint byte length, then the bytes.
+ */
+function encodeFields (fields) {
+  if (fields === null || fields === undefined || fields.length === 0) return Buffer.alloc(0)
+  if (!Array.isArray(fields)) throw new YgmError(8, 'a field list is null or an array of names')
+  const parts = []
+  for (const f of fields) {
+    const b = f instanceof Uint8Array ? f : Buffer.from(String(f), 'utf8')
+    const head = []
+    let n = b.length
+    while (n > 127) { head.push(0x80 | (n & 127)); n >>>= 7 }
+    head.push(n)
+    parts.push(Buffer.from(head), b)
+  }
+  return Buffer.concat(parts)
+}
 // per-document options -> option bytes, or undefined when none is set (the plain native entry points): an entry is an
 // option byte, `true` (no-GC), or { gc: boolean } as in yDocOptions; a Uint8Array is taken as it is
 function optBytes (opts, n) {
@@ -176,6 +194,10 @@ class GpuEngine {
       if (op === 'json') {   // a job is [state, root name bytes]
         const u = packBlobs(jobs.map(j => j[0])); const n = packBlobs(jobs.map(j => j[1]))
         return a.json(this.handle, u.arena, u.lens, n.arena, n.lens, JSON_PROSEMIRROR)
+      }
+      if (op === 'jsonFields') {   // a job is [state, encoded field list]
+        const u = packBlobs(jobs.map(j => j[0])); const f = packBlobs(jobs.map(j => j[1]))
+        return a.jsonFields(this.handle, u.arena, u.lens, f.arena, f.lens, JSON_PROSEMIRROR)
       }
       if (op === 'restoreVersion') {   // a job is [state, version, option byte]
         const u = packBlobs(jobs.map(j => j[0])); const v = packBlobs(jobs.map(j => j[1]))
@@ -319,6 +341,21 @@ class GpuEngine {
     return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
   }
 
+  /**
+   * Every asked field of stored documents as one JSON object, as an explicit batch: for
+   * doc = Y.applyUpdate(new Y.Doc(), states[i]) the string JSON.stringify(TiptapTransformer.fromYdoc(doc, fields[i]))
+   * -- the `document` of a change webhook (ygm_json_fields_v1).  fields[i]: null, undefined or [] for every key of
+   * doc.share, or an array of names (strings or UTF-8 bytes).  One load of the state serves all its fields.  Keys
+   * follow JavaScript's own-property order; a document with a refusing field, or a field named __proto__, gives a
+   * YgmError in its place.
+   */
+  async jsonFieldsMany (states, fields) {
+    if (fields.length !== states.length) throw new YgmError(8, 'one field list per state')
+    const jobs = states.map((s, i) => [s, encodeFields(fields[i])])
+    const r = await this._run('jsonFields', jobs)
+    return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
+  }
+
   /** update format V2 (yjs providers other than Hocuspocus's V1 path): Y.mergeUpdatesV2 / Y.diffUpdateV2 /
    *  Y.encodeStateVectorFromUpdateV2 / yjs 13.6 Y.convertUpdateFormatV1ToV2 / V2ToV1, as explicit batches */
   async mergeManyV2 (docs) { const r = await this._run('mergeV2', docs); return unpack(r) }
@@ -435,6 +472,8 @@ class GpuEnginePool {
   textMany (docNames, states, names, opts) { return this._many(docNames, [states, names], (e, a, b) => e.textMany(a, b, opts)) }
   /** jsonMany with one document name per state (the shard), beside its root name */
   jsonMany (docNames, states, names) { return this._many(docNames, [states, names], (e, a, b) => e.jsonMany(a, b)) }
+  /** jsonFieldsMany with one document name per state (the shard), beside its field list */
+  jsonFieldsMany (docNames, states, fields) { return this._many(docNames, [states, fields], (e, a, b) => e.jsonFieldsMany(a, b)) }
   stats () { return this.engines.map(e => e.stats()) }
   /**
    * Node-wide totals (the reference's server-wide counters, Hocuspocus.ts:138-160): every numeric field of the
@@ -449,4 +488,4 @@ class GpuEnginePool {
   close () { this.engines.forEach(e => e.close()) }
 }
 
-module.exports = { packJobs, GpuEngine, GpuEnginePool, fnv1a64, YgmError, STATUS, loadAddon, DOC_NO_GC, TEXT_FLAT, TEXT_DEEP, optBytes }
+module.exports = { packJobs, GpuEngine, GpuEnginePool, fnv1a64, YgmError, STATUS, loadAddon, DOC_NO_GC, TEXT_FLAT, TEXT_DEEP, optBytes, encodeFields }

@@ -261,15 +261,14 @@ class GpuMerge {
    * -- in one GPU batch over the captured states -> Map name -> JSON string, or the parsed object with parse: true.  A
    * document that is not loaded is left out; one the engine refuses (a root that is no XmlFragment of elements and
    * texts, a float attribute, ...) is left out and named in `unserialized`: the caller keeps its yjs path for it.
+   * field: a string (default 'default') is one root, fromYdoc(document, field); null or [] is every field,
+   * fromYdoc(document) -- the reference webhook's call -- and an array of names is fromYdoc(document, names): both give
+   * the object keyed by field, from one load of each state (ygm_json_fields_v1).
    */
   async jsonOf (names, { field = 'default', parse = false } = {}) {
-    const eng = this._engine()
     const states = await this._statesOf(names)
     const idx = names.map((_, i) => i).filter(i => states[i] && !(states[i] instanceof Error))
-    const fields = idx.map(() => field)
-    const res = !idx.length ? [] : typeof eng.shardOf === 'function'
-      ? await eng.jsonMany(idx.map(i => names[i]), idx.map(i => states[i]), fields)
-      : await eng.jsonMany(idx.map(i => states[i]), fields)
+    const res = !idx.length ? [] : await this._jsonMany(idx.map(i => names[i]), idx.map(i => states[i]), field)
     const out = new Map()
     idx.forEach((i, k) => {
       if (res[k] instanceof Error) this.unserialized.push({ documentName: names[i], code: res[k].code || String(res[k]) })
@@ -278,21 +277,31 @@ class GpuMerge {
     return out
   }
 
+  // one JSON batch over states: a string field is a root name (ygm_json_v1), null or an array a field list
+  // (ygm_json_fields_v1); docNames shard the batch over a pool's engines
+  _jsonMany (docNames, states, field) {
+    const eng = this._engine()
+    const pool = typeof eng.shardOf === 'function'
+    if (typeof field === 'string') {
+      const roots = states.map(() => field)
+      return pool ? eng.jsonMany(docNames, states, roots) : eng.jsonMany(states, roots)
+    }
+    if (field !== null && !Array.isArray(field)) throw new TypeError('field: a root name, null (every field) or an array of names')
+    const lists = states.map(() => field)
+    return pool ? eng.jsonFieldsMany(docNames, states, lists) : eng.jsonFieldsMany(states, lists)
+  }
+
   /**
    * versionJson(entries, { field, parse }): restoreVersions(entries) followed by one JSON batch over the fulfilled
    * results -- a saved version shown as a document, without a Y.Doc per version.  Settled per entry as restoreVersions
    * is: { status: 'fulfilled', value: string | object } or { status: 'rejected', reason } (a refused version is
-   * rejected with the engine's error and named in `unserialized`).
+   * rejected with the engine's error and named in `unserialized`).  field: as jsonOf's.
    */
   async versionJson (entries, { field = 'default', parse = false } = {}) {
-    const eng = this._engine()
     const out = await this.restoreVersions(entries)
     const ok = out.map((r, i) => r.status === 'fulfilled' ? i : -1).filter(i => i >= 0)
     if (!ok.length) return out
-    const fields = ok.map(() => field)
-    const res = typeof eng.shardOf === 'function'
-      ? await eng.jsonMany(ok.map(i => entries[i].documentName), ok.map(i => out[i].value), fields)
-      : await eng.jsonMany(ok.map(i => out[i].value), fields)
+    const res = await this._jsonMany(ok.map(i => entries[i].documentName), ok.map(i => out[i].value), field)
     ok.forEach((i, k) => {
       if (res[k] instanceof Error) {
         this.unserialized.push({ documentName: entries[i].documentName, code: res[k].code || String(res[k]) })
