@@ -65,23 +65,94 @@ class Stats(ctypes.Structure):
 
 _lib = None
 
-# every symbol include/ygm.h declares
-EXPORTS = ("ygm_open", "ygm_close", "ygm_merge_v1", "ygm_diff_v1", "ygm_sv_from_update_v1", "ygm_merge_v1_device",
-           "ygm_merge_v1_device_async", "ygm_merge_v1_device_finish",
-           "ygm_diff_v1_device", "ygm_sv_from_update_v1_device", "ygm_snapshot_v1", "ygm_snapshot_v1_device",
-           "ygm_contains_v1", "ygm_contains_v1_device", "ygm_stats", "ygm_strerror", "ygm_version",
-           "ygm_merge_v2", "ygm_diff_v2", "ygm_sv_from_update_v2", "ygm_convert_v1_to_v2", "ygm_convert_v2_to_v1",
-           "ygm_merge_v2_device", "ygm_diff_v2_device", "ygm_sv_from_update_v2_device", "ygm_convert_v1_to_v2_device",
-           "ygm_convert_v2_to_v1_device", "ygm_sync_step2_v1", "ygm_sync_step2_v1_device",
-           "ygm_merge_v1_device_lens", "ygm_merge_v1_device_lens_async",
-           "ygm_diff_shared_v1", "ygm_sync_step2_shared_v1", "ygm_diff_shared_v1_device",
-           "ygm_sync_step2_shared_v1_device",
-           "ygm_snapshot_opts_v1", "ygm_sync_step2_opts_v1", "ygm_sync_step2_shared_opts_v1",
-           "ygm_snapshot_opts_v1_device", "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device",
-           "ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device",
-           "ygm_version_restore_shared_v1", "ygm_version_restore_shared_v1_device",
-           "ygm_text_v1", "ygm_text_v1_device", "ygm_json_v1", "ygm_json_v1_device",
-           "ygm_json_fields_v1", "ygm_json_fields_v1_device")
+# ---- the C boundary: one entry per function include/ygm.h declares, in the header's order.  An entry is its argument
+# kinds and its result kind; lib() sets argtypes / restype from it and tests/test_abi.py holds it against the header.
+_KIND = {"p": ctypes.c_void_p, "u64": ctypes.c_uint64, "u32": ctypes.c_uint32, "int": ctypes.c_int,
+         "res": ctypes.POINTER(_Result), "dres": ctypes.POINTER(_DevResult), "stats": ctypes.POINTER(Stats),
+         "ctxp": ctypes.POINTER(ctypes.c_void_p)}
+_RET = {"int": ctypes.c_int, "void": None, "str": ctypes.c_char_p}
+
+
+def _sig(args, ret="int"):
+    return tuple(args.split()), ret
+
+
+def _dev_sig(sig, arena_bytes=True, out=True):
+    """The device-resident form of a host shape: the first arena's byte count after it, a stream before the result."""
+    args = list(sig[0][:-1])
+    if arena_bytes:
+        args.insert(2, "u64")
+    return tuple(args + ["p"] + (["dres"] if out else [])), sig[1]
+
+
+# the host shapes (each starts with the context)
+UNARY = _sig("p p p u32 res")                  # arena, off, n
+UNARY_OPT = _sig("p p p p u32 res")            # arena, off, opt, n
+PAIR = _sig("p p p p p u32 res")               # arena, off, second arena, its off, n
+PAIR_OPT = _sig("p p p p p p u32 res")         # a pair and one option array (where it stands: the header)
+PAIR_U32 = _sig("p p p p p u32 u32 res")       # a pair, a mode / kind, n
+MERGE = _sig("p p p p u32 u32 res")            # arena, upd_off, upd_doc, n_upd, n_docs
+SHARED = _sig("p p p u32 p p p u32 res")       # states, off, n_states, second arena, its off, ask, n_asks
+SHARED_OPT_STATE = _sig("p p p p u32 p p p u32 res")   # ... off, opt, n_states, ...
+SHARED_OPT_ASK = _sig("p p p u32 p p p p u32 res")     # ... ask, opt, n_asks
+MERGE_LENS = _sig("p p u64 p p p u32 u32 p dres")      # (device only) arena, bytes, doc_off, upd_len, doc_upd, n_upd, n_docs, stream
+
+SIGNATURES = {
+    "ygm_open": _sig("int u32 ctxp"),
+    "ygm_close": _sig("p", "void"),
+    "ygm_merge_v1": MERGE,
+    "ygm_diff_v1": PAIR,
+    "ygm_sv_from_update_v1": UNARY,
+    "ygm_snapshot_v1": UNARY,
+    "ygm_snapshot_opts_v1": UNARY_OPT,
+    "ygm_contains_v1": PAIR,
+    "ygm_text_v1": PAIR_U32,
+    "ygm_json_v1": PAIR_U32,
+    "ygm_json_fields_v1": PAIR_U32,
+    "ygm_sync_step2_v1": PAIR,
+    "ygm_sync_step2_opts_v1": PAIR_OPT,
+    "ygm_version_take_v1": UNARY,
+    "ygm_version_restore_v1": PAIR_OPT,
+    "ygm_diff_shared_v1": SHARED,
+    "ygm_sync_step2_shared_v1": SHARED,
+    "ygm_sync_step2_shared_opts_v1": SHARED_OPT_STATE,
+    "ygm_version_restore_shared_v1": SHARED_OPT_ASK,
+    "ygm_merge_v2": MERGE,
+    "ygm_diff_v2": PAIR,
+    "ygm_sv_from_update_v2": UNARY,
+    "ygm_convert_v1_to_v2": UNARY,
+    "ygm_convert_v2_to_v1": UNARY,
+    "ygm_merge_v1_device": _dev_sig(MERGE),
+    "ygm_merge_v1_device_async": _dev_sig(MERGE, out=False),
+    "ygm_merge_v1_device_finish": _sig("p dres"),
+    "ygm_merge_v1_device_lens": MERGE_LENS,
+    "ygm_merge_v1_device_lens_async": (MERGE_LENS[0][:-1], "int"),
+    "ygm_diff_v1_device": _dev_sig(PAIR),
+    "ygm_sv_from_update_v1_device": _dev_sig(UNARY),
+    "ygm_snapshot_v1_device": _dev_sig(UNARY),
+    "ygm_snapshot_opts_v1_device": _dev_sig(UNARY_OPT),
+    "ygm_contains_v1_device": _dev_sig(PAIR, arena_bytes=False),
+    "ygm_text_v1_device": _dev_sig(PAIR_U32),
+    "ygm_json_v1_device": _dev_sig(PAIR_U32),
+    "ygm_json_fields_v1_device": _dev_sig(PAIR_U32),
+    "ygm_sync_step2_v1_device": _dev_sig(PAIR),
+    "ygm_sync_step2_opts_v1_device": _dev_sig(PAIR_OPT),
+    "ygm_version_take_v1_device": _dev_sig(UNARY),
+    "ygm_version_restore_v1_device": _dev_sig(PAIR_OPT, arena_bytes=False),
+    "ygm_diff_shared_v1_device": _dev_sig(SHARED),
+    "ygm_sync_step2_shared_v1_device": _dev_sig(SHARED),
+    "ygm_sync_step2_shared_opts_v1_device": _dev_sig(SHARED_OPT_STATE),
+    "ygm_version_restore_shared_v1_device": _dev_sig(SHARED_OPT_ASK),
+    "ygm_merge_v2_device": _dev_sig(MERGE),
+    "ygm_diff_v2_device": _dev_sig(PAIR),
+    "ygm_sv_from_update_v2_device": _dev_sig(UNARY),
+    "ygm_convert_v1_to_v2_device": _dev_sig(UNARY),
+    "ygm_convert_v2_to_v1_device": _dev_sig(UNARY),
+    "ygm_stats": _sig("p stats"),
+    "ygm_strerror": _sig("int", "str"),
+    "ygm_version": _sig("", "str"),
+}
+EXPORTS = tuple(SIGNATURES)   # every symbol include/ygm.h declares
 
 
 def lib():
@@ -98,86 +169,22 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        vp, u64, u32, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
-        L.ygm_open.argtypes = [ctypes.c_int, u32, ctypes.POINTER(vp)]
-        L.ygm_close.argtypes = [vp]
-        L.ygm_close.restype = None
-        L.ygm_merge_v1.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
-        L.ygm_diff_v1.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_sv_from_update_v1.argtypes = [vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_merge_v1_device.argtypes = [vp, vp, u64, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_merge_v1_device_async.argtypes = [vp, vp, u64, vp, vp, u32, u32, vp]
-        L.ygm_merge_v1_device_finish.argtypes = [vp, ctypes.POINTER(_DevResult)]
-        L.ygm_merge_v1_device_lens.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_merge_v1_device_lens_async.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp]
-        L.ygm_diff_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_sv_from_update_v1_device.argtypes = [vp, vp, u64, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_snapshot_v1.argtypes = [vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_snapshot_v1_device.argtypes = [vp, vp, u64, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_contains_v1.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_contains_v1_device.argtypes = [vp, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_sync_step2_v1.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_sync_step2_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        for f in ("ygm_diff_shared_v1", "ygm_sync_step2_shared_v1"):
-            getattr(L, f).argtypes = [vp, vp, vp, u32, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-            getattr(L, f).restype = i32
-        for f in ("ygm_diff_shared_v1_device", "ygm_sync_step2_shared_v1_device"):
-            getattr(L, f).argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-            getattr(L, f).restype = i32
-        L.ygm_snapshot_opts_v1.argtypes = [vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_sync_step2_opts_v1.argtypes = [vp, vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_sync_step2_shared_opts_v1.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_snapshot_opts_v1_device.argtypes = [vp, vp, u64, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_sync_step2_opts_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_sync_step2_shared_opts_v1_device.argtypes = [vp, vp, u64, vp, vp, u32, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        for f in ("ygm_snapshot_opts_v1", "ygm_sync_step2_opts_v1", "ygm_sync_step2_shared_opts_v1", "ygm_snapshot_opts_v1_device",
-                  "ygm_sync_step2_opts_v1_device", "ygm_sync_step2_shared_opts_v1_device",
-           "ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device"):
-            getattr(L, f).restype = i32
-        L.ygm_version_take_v1.argtypes = [vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_version_restore_v1.argtypes = [vp, vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_version_take_v1_device.argtypes = [vp, vp, u64, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_version_restore_v1_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        for f in ("ygm_version_take_v1", "ygm_version_restore_v1", "ygm_version_take_v1_device", "ygm_version_restore_v1_device"):
-            getattr(L, f).restype = i32
-        L.ygm_version_restore_shared_v1.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_version_restore_shared_v1_device.argtypes = [vp, vp, u64, vp, u32, vp, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        for f in ("ygm_version_restore_shared_v1", "ygm_version_restore_shared_v1_device"):
-            getattr(L, f).restype = i32
-        L.ygm_text_v1.argtypes = [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
-        L.ygm_text_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_json_v1.argtypes = [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
-        L.ygm_json_v1_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_json_fields_v1.argtypes = L.ygm_json_v1.argtypes
-        L.ygm_json_fields_v1_device.argtypes = L.ygm_json_v1_device.argtypes
-        for f in ("ygm_text_v1", "ygm_text_v1_device", "ygm_json_v1", "ygm_json_v1_device", "ygm_json_fields_v1", "ygm_json_fields_v1_device"):
-            getattr(L, f).restype = i32
-        L.ygm_merge_v2.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(_Result)]
-        L.ygm_diff_v2.argtypes = [vp, vp, vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        for f in ("ygm_sv_from_update_v2", "ygm_convert_v1_to_v2", "ygm_convert_v2_to_v1"):
-            getattr(L, f).argtypes = [vp, vp, vp, u32, ctypes.POINTER(_Result)]
-        L.ygm_merge_v2_device.argtypes = [vp, vp, u64, vp, vp, u32, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_diff_v2_device.argtypes = [vp, vp, u64, vp, vp, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        for f in ("ygm_sv_from_update_v2_device", "ygm_convert_v1_to_v2_device", "ygm_convert_v2_to_v1_device"):
-            getattr(L, f).argtypes = [vp, vp, u64, vp, u32, vp, ctypes.POINTER(_DevResult)]
-        L.ygm_stats.argtypes = [vp, ctypes.POINTER(Stats)]
-        L.ygm_strerror.argtypes = [i32]
-        L.ygm_strerror.restype = ctypes.c_char_p
-        L.ygm_version.restype = ctypes.c_char_p
-        for f in ("ygm_open", "ygm_merge_v1", "ygm_diff_v1", "ygm_sv_from_update_v1", "ygm_merge_v1_device",
-                  "ygm_merge_v1_device_async", "ygm_merge_v1_device_finish",
-                  "ygm_diff_v1_device", "ygm_sv_from_update_v1_device", "ygm_snapshot_v1", "ygm_snapshot_v1_device",
-                  "ygm_contains_v1", "ygm_contains_v1_device", "ygm_stats", "ygm_merge_v2", "ygm_diff_v2", "ygm_sv_from_update_v2",
-                  "ygm_convert_v1_to_v2", "ygm_convert_v2_to_v1", "ygm_merge_v2_device", "ygm_diff_v2_device",
-                  "ygm_sv_from_update_v2_device", "ygm_convert_v1_to_v2_device", "ygm_convert_v2_to_v1_device",
-                  "ygm_sync_step2_v1", "ygm_sync_step2_v1_device", "ygm_merge_v1_device_lens", "ygm_merge_v1_device_lens_async"):
-            getattr(L, f).restype = i32
+        for name, (args, ret) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.argtypes = [_KIND[k] for k in args]
+            fn.restype = _RET[ret]
         _lib = L
     return _lib
 
 
 def strerror(code: int) -> str:
     return lib().ygm_strerror(code).decode()
+
+
+def _check(st):
+    """A batch call's (or one document's) status: anything but OK raises."""
+    if st != OK:
+        raise YjsError(st)
 
 
 def _pack(blobs):
@@ -209,8 +216,26 @@ def _ptr(a):
     return ctypes.c_char_p(a) if a else None
 
 
+# ---- argument helpers: each gives the C arguments of one logical input, to be spliced into a call
+def _packed(blobs):
+    """A list of byte strings as (arena or None, offset pointer)."""
+    arena, off = _pack([bytes(b) for b in blobs])
+    return arena or None, _ptr(off)
+
+
+def _names(names):
+    return _packed([n.encode() if isinstance(n, str) else n for n in names])
+
+
+def _merge_input(docs):
+    """Lists of updates per document in the packed form of a merge: arena, upd_off, upd_doc, n_docs."""
+    upd_doc = np.asarray([d for d, ups in enumerate(docs) for _ in ups], dtype=np.uint32)
+    return (*_pack([bytes(u) for ups in docs for u in ups]), upd_doc, len(docs))
+
+
 def _opts(opts, n):
-    """Per-document option bytes (YGM_DOC_NO_GC) from a bytes-like or a sequence of bools / ints; None: no options."""
+    """Per-document option bytes (YGM_DOC_NO_GC) from a bytes-like or a sequence of bools / ints, as a pointer to n
+    bytes; None (no options, or n = 0) is the C API's NULL."""
     if opts is None:
         return None
     if isinstance(opts, (bytes, bytearray, memoryview)):
@@ -219,7 +244,13 @@ def _opts(opts, n):
         a = np.ascontiguousarray(np.asarray([int(x) for x in opts], dtype=np.int64).astype(np.uint8))
     if len(a) != n:
         raise ValueError(f"{len(a)} option bytes for {n} documents")
-    return a
+    return _ptr(a) if n else None
+
+
+def _asks(ask_state):
+    """The ask -> state table of the shared forms as (u32 pointer or None, n_asks)."""
+    ask = np.ascontiguousarray(np.asarray(ask_state, dtype=np.int64).astype(np.uint32))
+    return _ptr(ask) if len(ask) else None, len(ask)
 
 
 TAIL_PAD = 64   # readable bytes the kernels need after a device arena (include/ygm.h, "Tail padding")
@@ -233,6 +264,18 @@ def _dptr(x, need=0):
             raise ValueError(f"device buffer of {nbytes} bytes: the engine reads {need} (arena + {TAIL_PAD} bytes of tail padding)")
         return x.data_ptr()
     return int(x)
+
+
+def _darena(d_arena, arena_bytes):
+    """A device arena as (pointer, byte count); a tensor must also hold the tail padding."""
+    return _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes
+
+
+def _dopt(d_opt, n):
+    """Device-resident option bytes: None / 0 is NULL, a tensor must hold n bytes."""
+    if d_opt is None or (not hasattr(d_opt, "data_ptr") and not d_opt):
+        return None
+    return _dptr(d_opt, n)
 
 
 @dataclass
@@ -252,9 +295,7 @@ class Engine:
     def __init__(self, device: int = 0, compat135: bool = False, force_seq: bool = False):
         flags = (F_COMPAT_135 if compat135 else 0) | (F_FORCE_SEQ if force_seq else 0)
         ctx = ctypes.c_void_p()
-        st = lib().ygm_open(device, flags, ctypes.byref(ctx))
-        if st != OK:
-            raise YjsError(st)
+        _check(lib().ygm_open(device, flags, ctypes.byref(ctx)))
         self._ctx = ctx
         self.device = device
 
@@ -271,6 +312,19 @@ class Engine:
 
     def __exit__(self, *a):
         self.close()
+
+    # ------------------------------------------------------------ the two call paths
+    def _host(self, fn, *args) -> _Result:
+        """A host-memory batch call fn(ctx, *args, &result): the context-owned result, valid until the next call."""
+        res = _Result()
+        _check(getattr(lib(), fn)(self._ctx, *args, ctypes.byref(res)))
+        return res
+
+    def _dev(self, fn, *args) -> DeviceResult:
+        """A device-resident call fn(ctx, *args, &result)."""
+        r = _DevResult()
+        _check(getattr(lib(), fn)(self._ctx, *args, ctypes.byref(r)))
+        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
 
     # ------------------------------------------------------------ results
     @staticmethod
@@ -292,30 +346,6 @@ class Engine:
                 out.append((st, None))
         return out
 
-    # ------------------------------------------------------------ batch API
-    def merge_updates_batch(self, docs):
-        """docs: list of lists of update bytes -> list of (status, merged bytes | None)."""
-        blobs, doc_ids = [], []
-        for d, ups in enumerate(docs):
-            for u in ups:
-                blobs.append(bytes(u))
-                doc_ids.append(d)
-        arena, off = _pack(blobs)
-        upd_doc = np.asarray(doc_ids, dtype=np.uint32)
-        res = _Result()
-        st = lib().ygm_merge_v1(self._ctx, arena or None, _ptr(off), _ptr(upd_doc), len(blobs), len(docs), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
-
-    def merge_packed(self, arena: np.ndarray, upd_off: np.ndarray, upd_doc: np.ndarray, n_docs: int):
-        """Packed host-array form of merge_updates_batch (arena uint8, upd_off uint64, upd_doc uint32)."""
-        res = _Result()
-        st = lib().ygm_merge_v1(self._ctx, _ptr(arena), _ptr(upd_off), _ptr(upd_doc), len(upd_doc), n_docs, ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
-
     @staticmethod
     def _raw(res: _Result):
         n = res.n_docs
@@ -324,178 +354,111 @@ class Engine:
         return (np.ctypeslib.as_array(res.status, shape=(n,)), np.ctypeslib.as_array(res.off, shape=(n,)),
                 np.ctypeslib.as_array(res.len, shape=(n,)), (ctypes.c_uint8 * max(res.data_bytes, 1)).from_address(ctypes.cast(res.data, ctypes.c_void_p).value))
 
+    def _or_error(self, res: _Result):
+        """Per document its bytes, or the YjsError of its refusal (the text / JSON calls)."""
+        return [b if s == OK else YjsError(s) for s, b in self._unpack(res)]
+
+    # ------------------------------------------------------------ batch API
+    def merge_updates_batch(self, docs):
+        """docs: list of lists of update bytes -> list of (status, merged bytes | None)."""
+        return self._unpack(self._merge_packed(*_merge_input(docs)))
+
+    def _merge_packed(self, arena, upd_off, upd_doc, n_docs, fn="ygm_merge_v1") -> _Result:
+        return self._host(fn, _ptr(arena), _ptr(upd_off), _ptr(upd_doc), len(upd_doc), n_docs)
+
+    def merge_packed(self, arena: np.ndarray, upd_off: np.ndarray, upd_doc: np.ndarray, n_docs: int):
+        """Packed host-array form of merge_updates_batch (arena uint8, upd_off uint64, upd_doc uint32)."""
+        return self._unpack(self._merge_packed(arena, upd_off, upd_doc, n_docs))
+
     def merge_packed_raw(self, arena: np.ndarray, upd_off: np.ndarray, upd_doc: np.ndarray, n_docs: int):
         """merge_packed without the per-document Python unpacking: (status, off, len, data) views of the
         context's pinned result buffers, valid until the next call on this engine."""
-        res = _Result()
-        st = lib().ygm_merge_v1(self._ctx, _ptr(arena), _ptr(upd_off), _ptr(upd_doc), len(upd_doc), n_docs, ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._raw(res)
+        return self._raw(self._merge_packed(arena, upd_off, upd_doc, n_docs))
+
+    def _doc_packed(self, op, arena, doc_off, sv_arena=None, sv_off=None) -> _Result:
+        n = len(doc_off) - 1
+        if op == "diff":
+            return self._host("ygm_diff_v1", _ptr(arena), _ptr(doc_off), _ptr(sv_arena), _ptr(sv_off), n)
+        return self._host("ygm_sv_from_update_v1", _ptr(arena), _ptr(doc_off), n)
 
     def doc_packed_raw(self, op: str, arena: np.ndarray, doc_off: np.ndarray, sv_arena=None, sv_off=None):
         """Host-array SV ("sv") / diff ("diff") batch; result views as merge_packed_raw."""
-        res = _Result()
-        n = len(doc_off) - 1
-        if op == "diff":
-            st = lib().ygm_diff_v1(self._ctx, _ptr(arena), _ptr(doc_off), _ptr(sv_arena), _ptr(sv_off), n, ctypes.byref(res))
-        else:
-            st = lib().ygm_sv_from_update_v1(self._ctx, _ptr(arena), _ptr(doc_off), n, ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._raw(res)
+        return self._raw(self._doc_packed(op, arena, doc_off, sv_arena, sv_off))
+
+    def _unary(self, fn, updates):
+        """fn over one list of byte strings -> list of (status, bytes | None)."""
+        return self._unpack(self._host(fn, *_packed(updates), len(updates)))
+
+    def _pair(self, fn, first, second):
+        """fn over two lists of byte strings, one pair per document -> list of (status, bytes | None)."""
+        return self._unpack(self._host(fn, *_packed(first), *_packed(second), len(first)))
 
     def diff_update_batch(self, updates, svs):
-        arena, off = _pack([bytes(u) for u in updates])
-        sva, svo = _pack([bytes(s) for s in svs])
-        res = _Result()
-        st = lib().ygm_diff_v1(self._ctx, arena or None, _ptr(off), sva or None, _ptr(svo), len(updates), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        return self._unpack(self._doc_packed("diff", *_pack([bytes(u) for u in updates]), *_pack([bytes(s) for s in svs])))
 
     def encode_state_vector_from_update_batch(self, updates):
-        arena, off = _pack([bytes(u) for u in updates])
-        res = _Result()
-        st = lib().ygm_sv_from_update_v1(self._ctx, arena or None, _ptr(off), len(updates), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        return self._unpack(self._doc_packed("sv", *_pack([bytes(u) for u in updates])))
 
     # ------------------------------------------------------------ update V2 (SURVEY.md §8f-4)
     def merge_updates_v2_batch(self, docs):
         """Y.mergeUpdatesV2 per document: docs = list of lists of V2 updates -> list of (status, V2 bytes | None)."""
-        blobs, doc_ids = [], []
-        for d, ups in enumerate(docs):
-            for u in ups:
-                blobs.append(bytes(u))
-                doc_ids.append(d)
-        arena, off = _pack(blobs)
-        upd_doc = np.asarray(doc_ids, dtype=np.uint32)
-        res = _Result()
-        st = lib().ygm_merge_v2(self._ctx, arena or None, _ptr(off), _ptr(upd_doc), len(blobs), len(docs), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        return self._unpack(self._merge_packed(*_merge_input(docs), fn="ygm_merge_v2"))
 
     def diff_update_v2_batch(self, updates, svs):
         """Y.diffUpdateV2(update, sv) per document (V2 updates, V1-format state vectors)."""
-        arena, off = _pack([bytes(u) for u in updates])
-        sva, svo = _pack([bytes(s) for s in svs])
-        res = _Result()
-        st = lib().ygm_diff_v2(self._ctx, arena or None, _ptr(off), sva or None, _ptr(svo), len(updates), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
-
-    def _unary_v2(self, fn, updates):
-        arena, off = _pack([bytes(u) for u in updates])
-        res = _Result()
-        st = getattr(lib(), fn)(self._ctx, arena or None, _ptr(off), len(updates), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        return self._pair("ygm_diff_v2", updates, svs)
 
     def _conv_packed(self, fn, arena, doc_off):
         """Packed host-array form of a unary V2 call (ygm_sv_from_update_v2 / ygm_convert_*): the raw _Result."""
-        res = _Result()
-        st = getattr(lib(), fn)(self._ctx, _ptr(arena), _ptr(doc_off), len(doc_off) - 1, ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return res
+        return self._host(fn, _ptr(arena), _ptr(doc_off), len(doc_off) - 1)
 
     def encode_state_vector_from_update_v2_batch(self, updates):
         """Y.encodeStateVectorFromUpdateV2 per update (the state vector is V1-encoded, as yjs's)."""
-        return self._unary_v2("ygm_sv_from_update_v2", updates)
+        return self._unary("ygm_sv_from_update_v2", updates)
 
     def convert_update_format_v1_to_v2_batch(self, updates):
         """yjs 13.6 Y.convertUpdateFormatV1ToV2 per update."""
-        return self._unary_v2("ygm_convert_v1_to_v2", updates)
+        return self._unary("ygm_convert_v1_to_v2", updates)
 
     def convert_update_format_v2_to_v1_batch(self, updates):
         """yjs 13.6 Y.convertUpdateFormatV2ToV1 per update."""
-        return self._unary_v2("ygm_convert_v2_to_v1", updates)
+        return self._unary("ygm_convert_v2_to_v1", updates)
 
     def merge_v2_device(self, d_arena, arena_bytes, d_upd_off, d_doc_upd, n_upd, n_docs, stream=0) -> "DeviceResult":
-        r = _DevResult()
-        st = lib().ygm_merge_v2_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_upd_off), _dptr(d_doc_upd),
-                                       n_upd, n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_merge_v2_device", *_darena(d_arena, arena_bytes), _dptr(d_upd_off), _dptr(d_doc_upd), n_upd, n_docs,
+                         stream or None)
 
     def doc_v2_device(self, op, d_arena, arena_bytes, d_doc_off, n_docs, d_sv=None, d_sv_off=None, stream=0) -> "DeviceResult":
         """op: "diff" (d_sv / d_sv_off), "sv", "v1_to_v2", "v2_to_v1" -- the device-resident V2 calls."""
-        r = _DevResult()
-        a = _dptr(d_arena, arena_bytes + TAIL_PAD)
+        a = _darena(d_arena, arena_bytes)
         if op == "diff":
-            st = lib().ygm_diff_v2_device(self._ctx, a, arena_bytes, _dptr(d_doc_off), _dptr(d_sv), _dptr(d_sv_off), n_docs, stream or None,
-                                          ctypes.byref(r))
-        else:
-            fn = {"sv": "ygm_sv_from_update_v2_device", "v1_to_v2": "ygm_convert_v1_to_v2_device",
-                  "v2_to_v1": "ygm_convert_v2_to_v1_device"}[op]
-            st = getattr(lib(), fn)(self._ctx, a, arena_bytes, _dptr(d_doc_off), n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+            return self._dev("ygm_diff_v2_device", *a, _dptr(d_doc_off), _dptr(d_sv), _dptr(d_sv_off), n_docs, stream or None)
+        fn = {"sv": "ygm_sv_from_update_v2_device", "v1_to_v2": "ygm_convert_v1_to_v2_device",
+              "v2_to_v1": "ygm_convert_v2_to_v1_device"}[op]
+        return self._dev(fn, *a, _dptr(d_doc_off), n_docs, stream or None)
 
     # ------------------------------------------------------------ yjs-shaped single calls
     def snapshot_batch(self, updates, opts=None):
         """Doc-normalized snapshots: Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), u)) per update
         (ygm_snapshot_v1) -> list of (status, bytes | None); UNSUPPORTED marks documents outside the envelope.
         opts: one option per update (bytes-like, or bools / ints): DOC_NO_GC / True marks a document created with
-        gc: false, whose snapshot is that of new Y.Doc({gc: false}) -- deleted content kept (ygm_snapshot_opts_v1)."""
-        arena, off = _pack([bytes(u) for u in updates])
-        res = _Result()
-        o = _opts(opts, len(updates))
-        if o is None:
-            st = lib().ygm_snapshot_v1(self._ctx, arena or None, _ptr(off), len(updates), ctypes.byref(res))
-        else:
-            st = lib().ygm_snapshot_opts_v1(self._ctx, arena or None, _ptr(off), _ptr(o) if len(o) else None, len(updates), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        gc: false, whose snapshot is that of new Y.Doc({gc: false}) -- deleted content kept (ygm_snapshot_opts_v1,
+        which without options is ygm_snapshot_v1)."""
+        return self._unpack(self._host("ygm_snapshot_opts_v1", *_packed(updates), _opts(opts, len(updates)), len(updates)))
 
     def sync_step2_batch(self, states, svs, opts=None):
         """SyncStep2 payloads of stored documents: Y.encodeStateAsUpdate(doc, sv) for doc = Y.applyUpdate(new Y.Doc(),
         state) (MessageReceiver.ts:137-138; ygm_sync_step2_v1) -> list of (status, bytes | None); UNSUPPORTED marks
         documents outside the snapshot envelope.  opts as snapshot_batch, one per state (ygm_sync_step2_opts_v1)."""
-        sa, so = _pack([bytes(s) for s in states])
-        va, vo = _pack([bytes(v) for v in svs])
-        res = _Result()
-        o = _opts(opts, len(states))
-        if o is None:
-            st = lib().ygm_sync_step2_v1(self._ctx, sa or None, _ptr(so), va or None, _ptr(vo), len(states), ctypes.byref(res))
-        else:
-            st = lib().ygm_sync_step2_opts_v1(self._ctx, sa or None, _ptr(so), _ptr(o) if len(o) else None, va or None, _ptr(vo),
-                                              len(states), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
-
-    def _shared(self, fn, states, ask_state, svs, opts=None):
-        if len(ask_state) != len(svs):
-            raise ValueError("one state index per state vector")
-        sa, so = _pack([bytes(s) for s in states])
-        va, vo = _pack([bytes(v) for v in svs])
-        ask = np.ascontiguousarray(np.asarray(ask_state, dtype=np.int64).astype(np.uint32))
-        res = _Result()
-        o = _opts(opts, len(states))
-        if o is None:
-            st = getattr(lib(), fn)(self._ctx, sa or None, _ptr(so), len(states), va or None, _ptr(vo),
-                                    _ptr(ask) if len(ask) else None, len(ask), ctypes.byref(res))
-        else:
-            st = getattr(lib(), fn)(self._ctx, sa or None, _ptr(so), _ptr(o) if len(o) else None, len(states), va or None, _ptr(vo),
-                                    _ptr(ask) if len(ask) else None, len(ask), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        return self._unpack(self._host("ygm_sync_step2_opts_v1", *_packed(states), _opts(opts, len(states)), *_packed(svs), len(states)))
 
     def diff_update_shared_batch(self, updates, ask_doc, svs):
         """Y.diffUpdate(updates[ask_doc[a]], svs[a]) per ask a (ygm_diff_shared_v1): many state vectors answered from
         one update, which is uploaded once and read in place.  ask_doc is non-decreasing, each entry below
         len(updates); anything else raises YjsError(EINVAL).  -> list of (status, bytes | None) per ask."""
-        return self._shared("ygm_diff_shared_v1", updates, ask_doc, svs)
+        if len(ask_doc) != len(svs):
+            raise ValueError("one state index per state vector")
+        return self._unpack(self._host("ygm_diff_shared_v1", *_packed(updates), len(updates), *_packed(svs), *_asks(ask_doc)))
 
     def sync_step2_shared_batch(self, states, ask_state, svs, opts=None):
         """SyncStep2 payloads of a reconnect storm (ygm_sync_step2_shared_v1): ask a is answered from
@@ -503,20 +466,15 @@ class Engine:
         is uploaded and snapshotted once however many asks name it.  ask_state as ask_doc in
         diff_update_shared_batch.  opts as snapshot_batch, one per state: a state's asks are all answered from its
         snapshot, so from its option (ygm_sync_step2_shared_opts_v1).  -> list of (status, bytes | None) per ask."""
-        if opts is None:
-            return self._shared("ygm_sync_step2_shared_v1", states, ask_state, svs)
-        return self._shared("ygm_sync_step2_shared_opts_v1", states, ask_state, svs, opts)
+        if len(ask_state) != len(svs):
+            raise ValueError("one state index per state vector")
+        return self._unpack(self._host("ygm_sync_step2_shared_opts_v1", *_packed(states), _opts(opts, len(states)), len(states),
+                                       *_packed(svs), *_asks(ask_state)))
 
     def contains_batch(self, states, updates):
         """Read-only SyncStep2: Y.snapshotContainsUpdate(Y.snapshot(doc), update) per pair, `states` being the
         documents' normalized states (snapshot_batch) -> list of (status, bool | None)."""
-        sa, so = _pack([bytes(s) for s in states])
-        ua, uo = _pack([bytes(u) for u in updates])
-        res = _Result()
-        st = lib().ygm_contains_v1(self._ctx, sa or None, _ptr(so), ua or None, _ptr(uo), len(states), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return [(s, None if s != OK else b == b"\x01") for s, b in self._unpack(res)]
+        return [(s, None if s != OK else b == b"\x01") for s, b in self._pair("ygm_contains_v1", states, updates)]
 
     # ------------------------------------------------------------ plain text
     def text_batch(self, states, names, deep=False):
@@ -526,25 +484,14 @@ class Engine:
         names: one root name per state (str or bytes).  A name the state has no root for gives b""."""
         if len(states) != len(names):
             raise ValueError("one root name per state")
-        sa, so = _pack([bytes(s) for s in states])
-        na, no = _pack([n.encode() if isinstance(n, str) else bytes(n) for n in names])
-        res = _Result()
-        st = lib().ygm_text_v1(self._ctx, sa or None, _ptr(so), na or None, _ptr(no), TEXT_DEEP if deep else TEXT_FLAT, len(states),
-                               ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return [b if s == OK else YjsError(s) for s, b in self._unpack(res)]
+        return self._or_error(self._host("ygm_text_v1", *_packed(states), *_names(names), TEXT_DEEP if deep else TEXT_FLAT, len(states)))
 
     def text_device(self, d_states, states_bytes, d_state_off, d_names, d_name_off, n_docs, deep=False, stream=0, mode=None) -> "DeviceResult":
         """Device-resident text batch (ygm_text_v1_device): the states arena followed by TAIL_PAD readable bytes;
         mode overrides deep (the raw YGM_TEXT_* value)."""
-        r = _DevResult()
         m = (TEXT_DEEP if deep else TEXT_FLAT) if mode is None else int(mode)
-        st = lib().ygm_text_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off), _dptr(d_names),
-                                      _dptr(d_name_off), m, n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_text_v1_device", *_darena(d_states, states_bytes), _dptr(d_state_off), _dptr(d_names), _dptr(d_name_off), m,
+                         n_docs, stream or None)
 
     # ------------------------------------------------------------ ProseMirror JSON
     def json_batch(self, states, names, kind=JSON_PROSEMIRROR):
@@ -555,22 +502,12 @@ class Engine:
         root for gives b'{"type":"doc","content":[]}'."""
         if len(states) != len(names):
             raise ValueError("one root name per state")
-        sa, so = _pack([bytes(s) for s in states])
-        na, no = _pack([n.encode() if isinstance(n, str) else bytes(n) for n in names])
-        res = _Result()
-        st = lib().ygm_json_v1(self._ctx, sa or None, _ptr(so), na or None, _ptr(no), int(kind), len(states), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return [b if s == OK else YjsError(s) for s, b in self._unpack(res)]
+        return self._or_error(self._host("ygm_json_v1", *_packed(states), *_names(names), int(kind), len(states)))
 
     def json_device(self, d_states, states_bytes, d_state_off, d_names, d_name_off, n_docs, kind=JSON_PROSEMIRROR, stream=0) -> "DeviceResult":
         """Device-resident JSON batch (ygm_json_v1_device): the states arena followed by TAIL_PAD readable bytes."""
-        r = _DevResult()
-        st = lib().ygm_json_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off), _dptr(d_names),
-                                      _dptr(d_name_off), int(kind), n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_json_v1_device", *_darena(d_states, states_bytes), _dptr(d_state_off), _dptr(d_names), _dptr(d_name_off),
+                         int(kind), n_docs, stream or None)
 
     def json_fields_batch(self, states, fields, kind=JSON_PROSEMIRROR):
         """Every asked field of stored documents as one JSON object (ygm_json_fields_v1): for
@@ -579,36 +516,22 @@ class Engine:
         None or [] (every key of doc.share) or a list of names (str or bytes); see encode_fields."""
         if len(states) != len(fields):
             raise ValueError("one field list per state")
-        sa, so = _pack([bytes(s) for s in states])
-        fa, fo = _pack([encode_fields(f) for f in fields])
-        res = _Result()
-        st = lib().ygm_json_fields_v1(self._ctx, sa or None, _ptr(so), fa or None, _ptr(fo), int(kind), len(states), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return [b if s == OK else YjsError(s) for s, b in self._unpack(res)]
+        return self._or_error(self._host("ygm_json_fields_v1", *_packed(states), *_packed([encode_fields(f) for f in fields]), int(kind),
+                                         len(states)))
 
     def json_fields_device(self, d_states, states_bytes, d_state_off, d_fields, d_field_off, n_docs, kind=JSON_PROSEMIRROR,
                            stream=0) -> "DeviceResult":
         """Device-resident form (ygm_json_fields_v1_device): the states arena followed by TAIL_PAD readable bytes; the
         field lists encoded as encode_fields does."""
-        r = _DevResult()
-        st = lib().ygm_json_fields_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off),
-                                             _dptr(d_fields), _dptr(d_field_off), int(kind), n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_json_fields_v1_device", *_darena(d_states, states_bytes), _dptr(d_state_off), _dptr(d_fields),
+                         _dptr(d_field_off), int(kind), n_docs, stream or None)
 
     # ------------------------------------------------------------ version history
     def take_version_batch(self, states):
         """Versions of stored documents: Y.encodeSnapshot(Y.snapshot(doc)) for doc = Y.applyUpdate(new Y.Doc(), state)
         (ygm_version_take_v1) -> list of (status, bytes | None).  A state with pending parts is seen through its
         integrated part, as Y.snapshot sees the store."""
-        arena, off = _pack([bytes(s) for s in states])
-        res = _Result()
-        st = lib().ygm_version_take_v1(self._ctx, arena or None, _ptr(off), len(states), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        return self._unary("ygm_version_take_v1", states)
 
     def restore_version_batch(self, states, versions, opts=None):
         """Old versions of gc: false documents: Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc,
@@ -618,15 +541,7 @@ class Engine:
         restore_version_shared_batch: here its state is staged and snapshotted once per version."""
         if len(states) != len(versions):
             raise ValueError("one version per state")
-        sa, so = _pack([bytes(s) for s in states])
-        va, vo = _pack([bytes(v) for v in versions])
-        res = _Result()
-        o = _opts(opts, len(states))
-        st = lib().ygm_version_restore_v1(self._ctx, sa or None, _ptr(so), va or None, _ptr(vo), _ptr(o) if o is not None and len(o) else None,
-                                          len(states), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        return self._unpack(self._host("ygm_version_restore_v1", *_packed(states), *_packed(versions), _opts(opts, len(states)), len(states)))
 
     def restore_version_shared_batch(self, states, ask_state, versions, opts=None):
         """Many versions restored from one stored state (ygm_version_restore_shared_v1): ask a restores versions[a] from
@@ -636,37 +551,19 @@ class Engine:
         -> list of (status, bytes | None) per ask."""
         if len(ask_state) != len(versions):
             raise ValueError("one state index per version")
-        sa, so = _pack([bytes(s) for s in states])
-        va, vo = _pack([bytes(v) for v in versions])
-        ask = np.ascontiguousarray(np.asarray(ask_state, dtype=np.int64).astype(np.uint32))
-        res = _Result()
-        o = _opts(opts, len(versions))
-        st = lib().ygm_version_restore_shared_v1(self._ctx, sa or None, _ptr(so), len(states), va or None, _ptr(vo),
-                                                 _ptr(ask) if len(ask) else None, _ptr(o) if o is not None and len(o) else None,
-                                                 len(ask), ctypes.byref(res))
-        if st != OK:
-            raise YjsError(st)
-        return self._unpack(res)
+        ask, n_asks = _asks(ask_state)
+        return self._unpack(self._host("ygm_version_restore_shared_v1", *_packed(states), len(states), *_packed(versions), ask,
+                                       _opts(opts, len(versions)), n_asks))
 
     def version_take_device(self, d_states, states_bytes, d_state_off, n_docs, stream=0) -> "DeviceResult":
         """Device-resident take batch (ygm_version_take_v1_device)."""
-        r = _DevResult()
-        st = lib().ygm_version_take_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off), n_docs,
-                                              stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_version_take_v1_device", *_darena(d_states, states_bytes), _dptr(d_state_off), n_docs, stream or None)
 
     def version_restore_device(self, d_states, d_state_off, d_versions, d_version_off, n_docs, stream=0, d_restored_opt=0) -> "DeviceResult":
         """Device-resident restore batch (ygm_version_restore_v1_device): both arenas followed by TAIL_PAD readable
         bytes, d_versions 16-byte aligned; d_restored_opt: a device pointer / tensor of n_docs option bytes (0: none)."""
-        r = _DevResult()
-        none = d_restored_opt is None or (not hasattr(d_restored_opt, "data_ptr") and not d_restored_opt)
-        st = lib().ygm_version_restore_v1_device(self._ctx, _dptr(d_states), _dptr(d_state_off), _dptr(d_versions), _dptr(d_version_off),
-                                                 None if none else _dptr(d_restored_opt, n_docs), n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_version_restore_v1_device", _dptr(d_states), _dptr(d_state_off), _dptr(d_versions), _dptr(d_version_off),
+                         _dopt(d_restored_opt, n_docs), n_docs, stream or None)
 
     def version_restore_shared_device(self, d_states, states_bytes, d_state_off, n_states, d_versions, d_version_off, d_ask_state, n_asks,
                                       stream=0, d_restored_opt=0) -> "DeviceResult":
@@ -674,105 +571,63 @@ class Engine:
         d_ask_state (u32) naming each ask's state; arenas as version_restore_device; d_restored_opt: a device pointer /
         tensor of n_asks option bytes (0: none).  Results are indexed by ask; an ask whose id is out of range or below
         its predecessor carries EINVAL."""
-        r = _DevResult()
-        none = d_restored_opt is None or (not hasattr(d_restored_opt, "data_ptr") and not d_restored_opt)
-        st = lib().ygm_version_restore_shared_v1_device(self._ctx, _dptr(d_states, states_bytes + TAIL_PAD), states_bytes, _dptr(d_state_off),
-                                                        n_states, _dptr(d_versions), _dptr(d_version_off), _dptr(d_ask_state),
-                                                        None if none else _dptr(d_restored_opt, n_asks), n_asks, stream or None,
-                                                        ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_version_restore_shared_v1_device", *_darena(d_states, states_bytes), _dptr(d_state_off), n_states,
+                         _dptr(d_versions), _dptr(d_version_off), _dptr(d_ask_state), _dopt(d_restored_opt, n_asks), n_asks, stream or None)
 
     def snapshot_device(self, d_arena, arena_bytes, d_doc_off, n_docs, stream=0, d_doc_opt=0) -> "DeviceResult":
         """Device-resident snapshot batch; d_doc_opt: a device pointer / tensor of n_docs option bytes (0: none)."""
-        r = _DevResult()
-        if d_doc_opt is None or (not hasattr(d_doc_opt, "data_ptr") and not d_doc_opt):
-            st = lib().ygm_snapshot_v1_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off), n_docs,
-                                              stream or None, ctypes.byref(r))
-        else:
-            st = lib().ygm_snapshot_opts_v1_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off),
-                                                   _dptr(d_doc_opt, n_docs), n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_snapshot_opts_v1_device", *_darena(d_arena, arena_bytes), _dptr(d_doc_off), _dopt(d_doc_opt, n_docs), n_docs,
+                         stream or None)
+
+    @staticmethod
+    def _one(results):
+        """The single-document form of a batch: its bytes, or the YjsError yjs would throw."""
+        st, out = results[0]
+        _check(st)
+        return out
 
     def merge_updates(self, updates):
-        st, out = self.merge_updates_batch([list(updates)])[0]
-        if st != OK:
-            raise YjsError(st)
-        return out
+        return self._one(self.merge_updates_batch([list(updates)]))
 
     def diff_update(self, update, sv):
-        st, out = self.diff_update_batch([update], [sv])[0]
-        if st != OK:
-            raise YjsError(st)
-        return out
+        return self._one(self.diff_update_batch([update], [sv]))
 
     def encode_state_vector_from_update(self, update):
-        st, out = self.encode_state_vector_from_update_batch([update])[0]
-        if st != OK:
-            raise YjsError(st)
-        return out
+        return self._one(self.encode_state_vector_from_update_batch([update]))
 
     # ------------------------------------------------------------ device-resident API
     def merge_device(self, d_arena: int, arena_bytes: int, d_upd_off: int, d_doc_upd: int, n_upd: int, n_docs: int,
                      stream: int = 0) -> DeviceResult:
-        r = _DevResult()
-        st = lib().ygm_merge_v1_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_upd_off), _dptr(d_doc_upd),
-                                       n_upd, n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_merge_v1_device", *_darena(d_arena, arena_bytes), _dptr(d_upd_off), _dptr(d_doc_upd), n_upd, n_docs,
+                         stream or None)
 
     def merge_device_async(self, d_arena: int, arena_bytes: int, d_upd_off: int, d_doc_upd: int, n_upd: int, n_docs: int,
                            stream: int = 0) -> None:
         """Enqueues a device-resident batch merge without waiting (ygm_merge_v1_device_async)."""
-        st = lib().ygm_merge_v1_device_async(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_upd_off),
-                                             _dptr(d_doc_upd), n_upd, n_docs, stream or None)
-        if st != OK:
-            raise YjsError(st)
+        _check(lib().ygm_merge_v1_device_async(self._ctx, *_darena(d_arena, arena_bytes), _dptr(d_upd_off), _dptr(d_doc_upd), n_upd, n_docs,
+                                               stream or None))
 
     def merge_device_lens(self, d_arena: int, arena_bytes: int, d_doc_off: int, d_upd_len: int, d_doc_upd: int, n_upd: int,
                           n_docs: int, stream: int = 0) -> DeviceResult:
         """The compact input form (ygm_merge_v1_device_lens): u64 offset per document, u16 length per update."""
-        r = _DevResult()
-        st = lib().ygm_merge_v1_device_lens(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off),
-                                            _dptr(d_upd_len), _dptr(d_doc_upd), n_upd, n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_merge_v1_device_lens", *_darena(d_arena, arena_bytes), _dptr(d_doc_off), _dptr(d_upd_len), _dptr(d_doc_upd),
+                         n_upd, n_docs, stream or None)
 
     def merge_device_lens_async(self, d_arena: int, arena_bytes: int, d_doc_off: int, d_upd_len: int, d_doc_upd: int, n_upd: int,
                                 n_docs: int, stream: int = 0) -> None:
-        st = lib().ygm_merge_v1_device_lens_async(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off),
-                                                  _dptr(d_upd_len), _dptr(d_doc_upd), n_upd, n_docs, stream or None)
-        if st != OK:
-            raise YjsError(st)
+        _check(lib().ygm_merge_v1_device_lens_async(self._ctx, *_darena(d_arena, arena_bytes), _dptr(d_doc_off), _dptr(d_upd_len),
+                                                    _dptr(d_doc_upd), n_upd, n_docs, stream or None))
 
     def merge_device_finish(self) -> DeviceResult:
         """Completes the last enqueued batch (sequential tier, fault check, payload) -- ygm_merge_v1_device_finish."""
-        r = _DevResult()
-        st = lib().ygm_merge_v1_device_finish(self._ctx, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_merge_v1_device_finish")
 
     def diff_device(self, d_arena, arena_bytes, d_doc_off, d_sv, d_sv_off, n_docs, stream=0) -> DeviceResult:
-        r = _DevResult()
-        st = lib().ygm_diff_v1_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off), _dptr(d_sv),
-                                      _dptr(d_sv_off), n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_diff_v1_device", *_darena(d_arena, arena_bytes), _dptr(d_doc_off), _dptr(d_sv), _dptr(d_sv_off), n_docs,
+                         stream or None)
 
     def sv_device(self, d_arena, arena_bytes, d_doc_off, n_docs, stream=0) -> DeviceResult:
-        r = _DevResult()
-        st = lib().ygm_sv_from_update_v1_device(self._ctx, _dptr(d_arena, arena_bytes + TAIL_PAD), arena_bytes, _dptr(d_doc_off),
-                                                n_docs, stream or None, ctypes.byref(r))
-        if st != OK:
-            raise YjsError(st)
-        return DeviceResult(r.data, r.off, r.len, r.status, r.data_bytes, r.payload_bytes)
+        return self._dev("ygm_sv_from_update_v1_device", *_darena(d_arena, arena_bytes), _dptr(d_doc_off), n_docs, stream or None)
 
     def stats(self) -> Stats:
         s = Stats()

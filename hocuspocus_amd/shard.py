@@ -70,19 +70,19 @@ class ShardedEngine:
     def encode_state_vector_from_update_batch(self, names, updates):
         return self._run(names, [updates], lambda e, u: e.encode_state_vector_from_update_batch(u))
 
+    def _run_opts(self, names, cols, opts, call):
+        """_run with the options (one per document) as a last column when there are any: they travel with their
+        documents, and call gets them as its last argument."""
+        if opts is not None:
+            cols = cols + [list(bytes(opts) if isinstance(opts, (bytes, bytearray, memoryview)) else opts)]
+        return self._run(names, cols, call)
+
     def snapshot_batch(self, names, updates, opts=None):
-        """Engine.snapshot_batch by shard; opts (one per document, DOC_NO_GC / True: a gc: false document) travel with
-        their documents."""
-        if opts is None:
-            return self._run(names, [updates], lambda e, u: e.snapshot_batch(u))
-        return self._run(names, [updates, list(bytes(opts) if isinstance(opts, (bytes, bytearray, memoryview)) else opts)],
-                         lambda e, u, o: e.snapshot_batch(u, o))
+        """Engine.snapshot_batch by shard; opts: DOC_NO_GC / True marks a gc: false document."""
+        return self._run_opts(names, [updates], opts, lambda e, *a: e.snapshot_batch(*a))
 
     def sync_step2_batch(self, names, states, svs, opts=None):
-        if opts is None:
-            return self._run(names, [states, svs], lambda e, s, v: e.sync_step2_batch(s, v))
-        return self._run(names, [states, svs, list(bytes(opts) if isinstance(opts, (bytes, bytearray, memoryview)) else opts)],
-                         lambda e, s, v, o: e.sync_step2_batch(s, v, o))
+        return self._run_opts(names, [states, svs], opts, lambda e, *a: e.sync_step2_batch(*a))
 
     def text_batch(self, doc_names, states, names, deep=False):
         """Engine.text_batch by shard: doc_names route the states, names are their root names."""

@@ -8,17 +8,14 @@
  * fs / dns / crypto).  Results come back as a Promise of
  * { status: Int32Array, outputs: (Uint8Array|null)[] }.
  *
- * JS surface (see ../index.d.ts):
- *   open(device, flags)                                  -> handle
- *   mergeMany(h, arena:Buffer, lens:Uint32Array, docs:Uint32Array, nDocs)  -> Promise
- *   diffMany(h, arena, lens, svArena, svLens)           -> Promise
- *   svMany(h, arena, lens)                              -> Promise
- *   stats(h) -> object ; close(h) ; strerror(code) -> string
+ * JS surface: the batch calls are the rows of OPS[] below (name, argument shape, trailing argument, C call), all
+ * parsed by js_batch; beside them open / openNull / sleep / close / stats / strerror.  Types: ../index.d.ts.
  * Input bytes are copied into native memory before the worker runs (JS owns its
  * typed arrays; SURVEY.md §8b "Ownership"); outputs are fresh Buffers.
  */
 #include <node_api.h>
 #include <pthread.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <stdint.h>
 #include <string.h>
@@ -42,14 +39,19 @@ typedef struct {
   int owners;                      /* the JS external and the threadsafe function: freed when both are finalized */
 } Handle;
 
+typedef struct Op Op;
 struct Job {
-  int op; /* 0 merge, 1 diff, 2 sv, ... 99 test sleep */
+  const Op *op;   /* the batch call's row of OPS[] */
+  int sleep;      /* instead: the threading test's sleep job */
   Handle *h;
   Job *next;
-  uint32_t sleep_ms; double t_start, t_end;   /* op 99 */
-  uint8_t *arena; uint64_t *off; uint32_t *docs; uint32_t n_upd, n_docs;
-  uint8_t *sv; uint64_t *sv_off;
-  uint8_t *opt;   /* per-document (per-state) option bytes, YGM_DOC_NO_GC; NULL: the plain entry points */
+  uint32_t sleep_ms; double t_start, t_end;   /* sleep */
+  uint8_t *arena; uint64_t *off;    /* the primary arena and its n_docs + 1 (merge: n_upd + 1) offsets */
+  uint32_t *docs;                   /* merge: the updates' document ids; shared: the asks' state ids */
+  uint32_t n_upd, n_docs;           /* n_docs: documents / states; n_upd: updates (merge) or asks (shared) */
+  uint8_t *sv; uint64_t *sv_off;    /* the second arena (state vectors, updates, versions, names, field lists) */
+  uint32_t mode;                    /* the required u32: ygm_text_v1's mode, ygm_json_v1's kind */
+  uint8_t *opt;   /* option bytes (YGM_DOC_NO_GC), one per document / state or per ask; NULL: none */
   int rc;
   /* copied results */
   uint8_t *data; uint64_t *roff, *rlen; int32_t *status; uint32_t rn;
@@ -268,37 +270,94 @@ static uint64_t *lens_to_off(const uint32_t *lens, uint32_t n) {
   return off;
 }
 
+/* ---- the batch calls: one row per JS-visible entry.  A row's shape says which arguments js_batch reads into the Job,
+   its tail what follows them, and its thunk is the C call.  A call with an options form always takes that form: a NULL
+   option pointer makes it the plain one (include/ygm.h). */
+typedef enum {
+  SHAPE_MERGE,    /* (handle, arena, lens, docs, nDocs): the arena Buffer is read in place */
+  SHAPE_UNARY,    /* (handle, arena, lens) */
+  SHAPE_PAIR,     /* (handle, a, aLens, b, bLens): one b per a */
+  SHAPE_SHARED    /* (handle, a, aLens, b, bLens, ask): one b and one state id per ask, n_upd asks over n_docs states */
+} Shape;
+typedef enum {
+  TAIL_NONE,
+  TAIL_OPT,       /* optional option bytes (Uint8Array / Buffer), one per primary entry (document, state or pair) */
+  TAIL_OPT_ASK,   /* optional option bytes, one per ask */
+  TAIL_U32        /* a required u32 (Job.mode) */
+} Tail;
+struct Op { const char *name; Shape shape; Tail tail; int (*run)(Job *j, ygm_result *r); };
+
+static int run_merge(Job *j, ygm_result *r) { return ygm_merge_v1(j->h->ctx, j->arena, j->off, j->docs, j->n_upd, j->n_docs, r); }
+static int run_merge_v2(Job *j, ygm_result *r) { return ygm_merge_v2(j->h->ctx, j->arena, j->off, j->docs, j->n_upd, j->n_docs, r); }
+static int run_sv(Job *j, ygm_result *r) { return ygm_sv_from_update_v1(j->h->ctx, j->arena, j->off, j->n_docs, r); }
+static int run_sv_v2(Job *j, ygm_result *r) { return ygm_sv_from_update_v2(j->h->ctx, j->arena, j->off, j->n_docs, r); }
+static int run_v1_to_v2(Job *j, ygm_result *r) { return ygm_convert_v1_to_v2(j->h->ctx, j->arena, j->off, j->n_docs, r); }
+static int run_v2_to_v1(Job *j, ygm_result *r) { return ygm_convert_v2_to_v1(j->h->ctx, j->arena, j->off, j->n_docs, r); }
+static int run_snapshot(Job *j, ygm_result *r) { return ygm_snapshot_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->n_docs, r); }
+static int run_take_version(Job *j, ygm_result *r) { return ygm_version_take_v1(j->h->ctx, j->arena, j->off, j->n_docs, r); }
+static int run_diff(Job *j, ygm_result *r) { return ygm_diff_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, r); }
+static int run_diff_v2(Job *j, ygm_result *r) { return ygm_diff_v2(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, r); }
+static int run_contains(Job *j, ygm_result *r) { return ygm_contains_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, r); }
+static int run_step2(Job *j, ygm_result *r) { return ygm_sync_step2_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->sv, j->sv_off, j->n_docs, r); }
+static int run_restore_version(Job *j, ygm_result *r) { return ygm_version_restore_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->opt, j->n_docs, r); }
+static int run_text(Job *j, ygm_result *r) { return ygm_text_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->mode, j->n_docs, r); }
+static int run_json(Job *j, ygm_result *r) { return ygm_json_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->mode, j->n_docs, r); }
+static int run_json_fields(Job *j, ygm_result *r) { return ygm_json_fields_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->mode, j->n_docs, r); }
+static int run_diff_shared(Job *j, ygm_result *r) { return ygm_diff_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, r); }
+static int run_step2_shared(Job *j, ygm_result *r) { return ygm_sync_step2_shared_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, r); }
+static int run_restore_version_shared(Job *j, ygm_result *r) { return ygm_version_restore_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->opt, j->n_upd, r); }
+
+static const Op OPS[] = {
+  { "mergeMany", SHAPE_MERGE, TAIL_NONE, run_merge },
+  { "diffMany", SHAPE_PAIR, TAIL_NONE, run_diff },
+  /* SyncStep2 of stored documents: encodeStateAsUpdate(applyUpdate(new Doc, state), sv) (MessageReceiver.ts:137-138);
+     option bytes: the states' (YGM_DOC_NO_GC for documents created with gc: false, Hocuspocus.ts:331-344) */
+  { "step2Many", SHAPE_PAIR, TAIL_OPT, run_step2 },
+  /* many state vectors answered from one state (a reconnect storm): diffUpdate / SyncStep2 per ask; step2Shared's
+     option bytes: one per state */
+  { "diffShared", SHAPE_SHARED, TAIL_NONE, run_diff_shared },
+  { "step2Shared", SHAPE_SHARED, TAIL_OPT, run_step2_shared },
+  { "svMany", SHAPE_UNARY, TAIL_NONE, run_sv },
+  /* Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), u)) per update; option bytes: YGM_DOC_NO_GC gives
+     new Y.Doc({gc: false}) for that one */
+  { "snapshotMany", SHAPE_UNARY, TAIL_OPT, run_snapshot },
+  /* snapshotContainsUpdate per (state, update) pair: one byte */
+  { "containsMany", SHAPE_PAIR, TAIL_NONE, run_contains },
+  /* update format V2 (yjs mergeUpdatesV2 / diffUpdateV2 / encodeStateVectorFromUpdateV2 / 13.6 convertUpdateFormat*) */
+  { "mergeManyV2", SHAPE_MERGE, TAIL_NONE, run_merge_v2 },
+  { "diffManyV2", SHAPE_PAIR, TAIL_NONE, run_diff_v2 },
+  { "svManyV2", SHAPE_UNARY, TAIL_NONE, run_sv_v2 },
+  { "convertManyV1ToV2", SHAPE_UNARY, TAIL_NONE, run_v1_to_v2 },
+  { "convertManyV2ToV1", SHAPE_UNARY, TAIL_NONE, run_v2_to_v1 },
+  /* version history: Y.encodeSnapshot(Y.snapshot(doc)) per state; Y.createDocFromSnapshot per (state, version)
+     [, option bytes of the restored documents] (ygm_version_take_v1 / ygm_version_restore_v1) */
+  { "takeVersionMany", SHAPE_UNARY, TAIL_NONE, run_take_version },
+  { "restoreVersionMany", SHAPE_PAIR, TAIL_OPT, run_restore_version },
+  /* many versions restored from one state: one result and one option byte per ask -- the option belongs to the
+     restored document */
+  { "restoreVersionShared", SHAPE_SHARED, TAIL_OPT_ASK, run_restore_version_shared },
+  /* plain text of stored documents: getText(name).toString() or the deep walk per (state, root name); the u32 is the
+     mode, YGM_TEXT_FLAT / YGM_TEXT_DEEP (ygm_text_v1) */
+  { "text", SHAPE_PAIR, TAIL_U32, run_text },
+  /* stored documents as ProseMirror / Tiptap JSON per (state, root name): transformer.fromYdoc(doc, name); the u32 is
+     the kind, YGM_JSON_PROSEMIRROR (ygm_json_v1) */
+  { "json", SHAPE_PAIR, TAIL_U32, run_json },
+  /* every asked field of stored documents as one JSON object per (state, field list): transformer.fromYdoc(doc) /
+     fromYdoc(doc, [names]) -- a list is lib0 varStrings back to back, none: every root (ygm_json_fields_v1) */
+  { "jsonFields", SHAPE_PAIR, TAIL_U32, run_json_fields },
+};
+#define N_OPS (sizeof OPS / sizeof OPS[0])
+
 static void job_execute(Job *j) {
   const double t0 = now_ms();
   ygm_result r; memset(&r, 0, sizeof r);
-  if (j->op == 99) {   /* threading test: occupy the worker */
+  if (j->sleep) {   /* threading test: occupy the worker */
     j->t_start = t0;
     struct timespec ts = { j->sleep_ms / 1000, (long)(j->sleep_ms % 1000) * 1000000L };
     nanosleep(&ts, NULL);
     j->t_end = now_ms(); j->rc = YGM_OK; return;
   }
-  if (j->op == 0) j->rc = ygm_merge_v1(j->h->ctx, j->arena, j->off, j->docs, j->n_upd, j->n_docs, &r);
-  else if (j->op == 1) j->rc = ygm_diff_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
-  else if (j->op == 3 && j->opt) j->rc = ygm_snapshot_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->n_docs, &r);
-  else if (j->op == 3) j->rc = ygm_snapshot_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
-  else if (j->op == 4) j->rc = ygm_contains_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
-  else if (j->op == 5 && j->opt) j->rc = ygm_sync_step2_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->sv, j->sv_off, j->n_docs, &r);
-  else if (j->op == 5) j->rc = ygm_sync_step2_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
-  else if (j->op == 6) j->rc = ygm_diff_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, &r);
-  else if (j->op == 7 && j->opt) j->rc = ygm_sync_step2_shared_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, &r);
-  else if (j->op == 7) j->rc = ygm_sync_step2_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, &r);
-  else if (j->op == 10) j->rc = ygm_merge_v2(j->h->ctx, j->arena, j->off, j->docs, j->n_upd, j->n_docs, &r);
-  else if (j->op == 11) j->rc = ygm_diff_v2(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_docs, &r);
-  else if (j->op == 12) j->rc = ygm_sv_from_update_v2(j->h->ctx, j->arena, j->off, j->n_docs, &r);
-  else if (j->op == 13) j->rc = ygm_convert_v1_to_v2(j->h->ctx, j->arena, j->off, j->n_docs, &r);
-  else if (j->op == 14) j->rc = ygm_convert_v2_to_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
-  else if (j->op == 15) j->rc = ygm_version_take_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
-  else if (j->op == 16) j->rc = ygm_version_restore_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->opt, j->n_docs, &r);
-  else if (j->op == 18) j->rc = ygm_text_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_upd, j->n_docs, &r);   /* (n_upd: the mode) */
-  else if (j->op == 19) j->rc = ygm_json_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_upd, j->n_docs, &r);   /* (n_upd: the kind) */
-  else if (j->op == 20) j->rc = ygm_json_fields_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->n_upd, j->n_docs, &r);   /* (sv: the field lists) */
-  else if (j->op == 17) j->rc = ygm_version_restore_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->opt, j->n_upd, &r);
-  else j->rc = ygm_sv_from_update_v1(j->h->ctx, j->arena, j->off, j->n_docs, &r);
+  j->rc = j->op->run(j, &r);
   if (j->rc != YGM_OK) return;
   /* results are context-owned: copy out before the next batch may reuse them */
   j->rn = r.n_docs;
@@ -328,7 +387,7 @@ static void job_complete(napi_env env, Job *j) {
   if (j->arena_ref) { napi_delete_reference(env, j->arena_ref); j->arena_ref = NULL; }
   if (j->handle_ref) { napi_delete_reference(env, j->handle_ref); j->handle_ref = NULL; }
   napi_value result = NULL, err = NULL;
-  if (j->op == 99) {
+  if (j->sleep) {
     napi_value a, b;
     napi_create_object(env, &result);
     napi_create_double(env, j->t_start, &a); napi_create_double(env, j->t_end, &b);
@@ -404,205 +463,96 @@ static napi_value js_sleep(napi_env env, napi_callback_info info) {
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   Handle *h = argc > 0 ? get_handle_any(env, argv[0]) : NULL;
   if (!h) return NULL;
-  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = 99; j->h = h;
+  Job *j = (Job *)calloc(1, sizeof(Job)); j->sleep = 1; j->h = h;
   if (argc > 1) napi_get_value_uint32(env, argv[1], &j->sleep_ms);
   return submit(env, j, argv[0]);
 }
 
-/* mergeMany(h, arena, lens, docs, nDocs) */
-static napi_value js_merge(napi_env env, napi_callback_info info) {
-  size_t argc = 5; napi_value argv[5];
-  void *opd = NULL;
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
-  if (argc < 5) { napi_throw_type_error(env, NULL, "mergeMany(handle, arena, lens, docs, nDocs)"); return NULL; }
-  Handle *h = get_handle(env, argv[0]);
-  if (!h) return NULL;
-  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = opd ? (int)(intptr_t)opd : 0; j->h = h;
-  size_t an = 0, ln, dn; void *lens = NULL;
+/* mergeMany's arena: a Buffer is read in place by the worker (the reference keeps it alive until the batch completes);
+   anything else is copied */
+static int borrow_or_copy(napi_env env, napi_value v, Job *j, size_t *len) {
   bool is_buf = false;
-  napi_is_buffer(env, argv[1], &is_buf);
-  if (is_buf && napi_get_buffer_info(env, argv[1], (void **)&j->arena, &an) == napi_ok &&
-      napi_create_reference(env, argv[1], 1, &j->arena_ref) == napi_ok) {
-    j->arena_borrowed = 1;   /* read in place by the worker; the reference keeps it alive */
-  } else if (get_bytes(env, argv[1], (void **)&j->arena, &an)) {
-    job_free(j); napi_throw_type_error(env, NULL, "mergeMany: expected Buffer / Uint32Array arguments"); return NULL;
+  napi_is_buffer(env, v, &is_buf);
+  if (is_buf && napi_get_buffer_info(env, v, (void **)&j->arena, len) == napi_ok && napi_create_reference(env, v, 1, &j->arena_ref) == napi_ok) {
+    j->arena_borrowed = 1;
+    return 0;
   }
-  if (get_bytes(env, argv[2], &lens, &ln) || get_bytes(env, argv[3], (void **)&j->docs, &dn)) {
-    if (j->arena_ref) napi_delete_reference(env, j->arena_ref);
-    free(lens); job_free(j); napi_throw_type_error(env, NULL, "mergeMany: expected Buffer / Uint32Array arguments"); return NULL;
-  }
-  napi_get_value_uint32(env, argv[4], &j->n_docs);
-  j->n_upd = (uint32_t)(ln / 4);
-  if (dn / 4 != j->n_upd) {
-    if (j->arena_ref) napi_delete_reference(env, j->arena_ref);
-    free(lens); job_free(j); napi_throw_range_error(env, NULL, "mergeMany: lens/docs length mismatch"); return NULL;
-  }
-  j->off = lens_to_off((const uint32_t *)lens, j->n_upd);
-  free(lens);
-  if (j->off[j->n_upd] != an) {
-    if (j->arena_ref) napi_delete_reference(env, j->arena_ref);
-    job_free(j); napi_throw_range_error(env, NULL, "mergeMany: sum(lens) != arena length"); return NULL;
-  }
-  return submit(env, j, argv[0]);
+  return get_bytes(env, v, (void **)&j->arena, len);
 }
 
-/* diffMany(h, arena, lens, svArena, svLens) */
-static napi_value js_diff(napi_env env, napi_callback_info info) {
-  size_t argc = 6; napi_value argv[6];   /* (step2Many: an optional sixth argument, the states' option bytes; restoreVersionMany: the restored documents') */
-  void *opd = NULL;
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
-  if (argc < 5) { napi_throw_type_error(env, NULL, "diffMany(handle, arena, lens, svArena, svLens)"); return NULL; }
+static const char *const SHAPE_ARGS[] = { "handle, arena, lens, docs, nDocs", "handle, arena, lens", "handle, a, aLens, b, bLens", "handle, a, aLens, b, bLens, ask" };
+static const size_t SHAPE_ARGC[] = { 5, 3, 5, 6 };
+
+/* every batch call: reads the arguments of the row's shape into a Job, then the row's trailing argument, and queues the
+   job.  Checks in order: argument count, handle, buffers, length agreement, trailing argument; every failure after the
+   Job exists leaves through `fail` */
+static napi_value js_batch(napi_env env, napi_callback_info info) {
+  size_t argc = 7; napi_value argv[7];
+  void *row = NULL;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &row));
+  const Op *op = (const Op *)row;
+  const Shape shape = op->shape;
+  const size_t fixed = SHAPE_ARGC[shape];   /* the trailing argument's index */
+  char msg[160];
+  if (argc < fixed) {
+    snprintf(msg, sizeof msg, "%s(%s)", op->name, SHAPE_ARGS[shape]);
+    napi_throw_type_error(env, NULL, msg); return NULL;
+  }
   Handle *h = get_handle(env, argv[0]);
   if (!h) return NULL;
-  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = opd ? (int)(intptr_t)opd : 1; j->h = h;
-  size_t an, ln, sn, sln; void *lens = NULL, *slens = NULL;
-  if (get_bytes(env, argv[1], (void **)&j->arena, &an) || get_bytes(env, argv[2], &lens, &ln) || get_bytes(env, argv[3], (void **)&j->sv, &sn) ||
-      get_bytes(env, argv[4], &slens, &sln) || ln != sln) {
-    free(lens); free(slens); job_free(j); napi_throw_type_error(env, NULL, "diffMany: bad arguments"); return NULL;
+  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = op; j->h = h;
+  void *lens = NULL, *slens = NULL;
+  size_t an = 0, ln = 0, sn = 0, sln = 0, kn = 0;   /* bytes of: the arena, its lens, the second arena, its lens, docs / ask */
+  const char *why = "expected Buffer / typed-array arguments"; int range = 0;
+
+  int bad = shape == SHAPE_MERGE ? borrow_or_copy(env, argv[1], j, &an) : get_bytes(env, argv[1], (void **)&j->arena, &an);
+  bad = bad || get_bytes(env, argv[2], &lens, &ln);
+  if (shape == SHAPE_MERGE) bad = bad || get_bytes(env, argv[3], (void **)&j->docs, &kn);
+  if (shape == SHAPE_PAIR || shape == SHAPE_SHARED) bad = bad || get_bytes(env, argv[3], (void **)&j->sv, &sn) || get_bytes(env, argv[4], &slens, &sln);
+  if (shape == SHAPE_SHARED) bad = bad || get_bytes(env, argv[5], (void **)&j->docs, &kn);
+  if (bad) goto fail;
+  if (shape == SHAPE_PAIR && ln != sln) { why = "one second entry per first entry"; goto fail; }
+  if (shape == SHAPE_SHARED && kn != sln) { why = "one ask entry per second entry"; goto fail; }
+
+  range = 1;
+  uint32_t n_first = (uint32_t)(ln / 4), n_second = (uint32_t)(sln / 4);   /* entries of the two length tables */
+  if (shape == SHAPE_MERGE) {
+    j->n_upd = n_first;
+    napi_get_value_uint32(env, argv[4], &j->n_docs);
+    if (kn / 4 != j->n_upd) { why = "lens/docs length mismatch"; goto fail; }
+  } else {
+    j->n_docs = n_first;
+    if (shape == SHAPE_SHARED) j->n_upd = n_second;
   }
-  j->n_docs = (uint32_t)(ln / 4);
-  j->off = lens_to_off((const uint32_t *)lens, j->n_docs);
-  j->sv_off = lens_to_off((const uint32_t *)slens, j->n_docs);
+  j->off = lens_to_off((const uint32_t *)lens, n_first);
+  if (slens) j->sv_off = lens_to_off((const uint32_t *)slens, n_second);
+  if (j->off[n_first] != an || (slens && j->sv_off[n_second] != sn)) { why = "lengths do not match arenas"; goto fail; }
+
+  if (op->tail == TAIL_U32 && (argc <= fixed || napi_get_value_uint32(env, argv[fixed], &j->mode) != napi_ok)) { range = 0; why = "a mode / kind number is required"; goto fail; }
+  if (op->tail == TAIL_OPT && get_opts(env, argc, argv, fixed, j->n_docs, &j->opt)) { why = "one option byte per document / state"; goto fail; }
+  if (op->tail == TAIL_OPT_ASK && get_opts(env, argc, argv, fixed, j->n_upd, &j->opt)) { why = "one option byte per ask"; goto fail; }
   free(lens); free(slens);
-  if (j->off[j->n_docs] != an || j->sv_off[j->n_docs] != sn) { job_free(j); napi_throw_range_error(env, NULL, "diffMany: lengths do not match arenas"); return NULL; }
-  if (j->op == 18) {   /* text(handle, states, stateLens, names, nameLens, mode): YGM_TEXT_FLAT / YGM_TEXT_DEEP, kept in n_upd */
-    if (argc < 6 || napi_get_value_uint32(env, argv[5], &j->n_upd) != napi_ok) { job_free(j); napi_throw_type_error(env, NULL, "text: mode (0 flat, 1 deep)"); return NULL; }
-  }
-  if (j->op == 19 || j->op == 20) {   /* json / jsonFields(handle, states, stateLens, names | field lists, their lens, kind): YGM_JSON_PROSEMIRROR, kept in n_upd */
-    if (argc < 6 || napi_get_value_uint32(env, argv[5], &j->n_upd) != napi_ok) { job_free(j); napi_throw_type_error(env, NULL, "json: kind (0 ProseMirror)"); return NULL; }
-  }
-  if ((j->op == 5 || j->op == 16) && get_opts(env, argc, argv, 5, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "step2Many / restoreVersionMany: one option byte per state"); return NULL; }
   return submit(env, j, argv[0]);
-}
 
-/* svMany(h, arena, lens) */
-static napi_value js_sv(napi_env env, napi_callback_info info) {
-  size_t argc = 3; napi_value argv[3];
-  void *opd = NULL;
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
-  if (argc < 3) { napi_throw_type_error(env, NULL, "svMany(handle, arena, lens)"); return NULL; }
-  Handle *h = get_handle(env, argv[0]);
-  if (!h) return NULL;
-  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = opd ? (int)(intptr_t)opd : 2; j->h = h;
-  size_t an, ln; void *lens = NULL;
-  if (get_bytes(env, argv[1], (void **)&j->arena, &an) || get_bytes(env, argv[2], &lens, &ln)) {
-    free(lens); job_free(j); napi_throw_type_error(env, NULL, "svMany: bad arguments"); return NULL;
-  }
-  j->n_docs = (uint32_t)(ln / 4);
-  j->off = lens_to_off((const uint32_t *)lens, j->n_docs);
-  free(lens);
-  if (j->off[j->n_docs] != an) { job_free(j); napi_throw_range_error(env, NULL, "svMany: sum(lens) != arena length"); return NULL; }
-  return submit(env, j, argv[0]);
-}
-
-/* containsMany(h, states, stateLens, updates, updateLens): snapshotContainsUpdate per pair (1 byte) */
-static napi_value js_contains(napi_env env, napi_callback_info info) {
-  size_t argc = 5; napi_value argv[5];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 5) { napi_throw_type_error(env, NULL, "containsMany(handle, states, lens, updates, lens)"); return NULL; }
-  Handle *h = get_handle(env, argv[0]);
-  if (!h) return NULL;
-  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = 4; j->h = h;
-  size_t an, ln, sn, sln; void *lens = NULL, *slens = NULL;
-  if (get_bytes(env, argv[1], (void **)&j->arena, &an) || get_bytes(env, argv[2], &lens, &ln) || get_bytes(env, argv[3], (void **)&j->sv, &sn) ||
-      get_bytes(env, argv[4], &slens, &sln) || ln != sln) {
-    free(lens); free(slens); job_free(j); napi_throw_type_error(env, NULL, "containsMany: bad arguments"); return NULL;
-  }
-  j->n_docs = (uint32_t)(ln / 4);
-  j->off = lens_to_off((const uint32_t *)lens, j->n_docs);
-  j->sv_off = lens_to_off((const uint32_t *)slens, j->n_docs);
+fail:
   free(lens); free(slens);
-  if (j->off[j->n_docs] != an || j->sv_off[j->n_docs] != sn) { job_free(j); napi_throw_range_error(env, NULL, "containsMany: lengths do not match arenas"); return NULL; }
-  return submit(env, j, argv[0]);
-}
-
-/* diffShared / step2Shared(h, states, stateLens, svArena, svLens, askState:Uint32Array): one result per ask (state
-   vector), ask a answered from state askState[a] (non-decreasing); n_docs = states, n_upd = asks, docs = askState.
-   restoreVersionShared(h, states, stateLens, versions, versionLens, askState[, opts]): the same shape with one version
-   per ask, and one option byte per ask -- the option belongs to the restored document (ygm_version_restore_shared_v1) */
-static napi_value js_shared(napi_env env, napi_callback_info info) {
-  size_t argc = 7; napi_value argv[7];   /* (an optional seventh argument: step2Shared, one option byte per state; restoreVersionShared, per ask) */
-  void *opd = NULL;
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, &opd));
-  if (argc < 6) { napi_throw_type_error(env, NULL, "step2Shared(handle, states, stateLens, svArena, svLens, askState)"); return NULL; }
-  Handle *h = get_handle(env, argv[0]);
-  if (!h) return NULL;
-  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = (int)(intptr_t)opd; j->h = h;
-  size_t an, ln, sn, sln, kn; void *lens = NULL, *slens = NULL;
-  if (get_bytes(env, argv[1], (void **)&j->arena, &an) || get_bytes(env, argv[2], &lens, &ln) || get_bytes(env, argv[3], (void **)&j->sv, &sn) ||
-      get_bytes(env, argv[4], &slens, &sln) || get_bytes(env, argv[5], (void **)&j->docs, &kn) || kn != sln) {
-    free(lens); free(slens); job_free(j); napi_throw_type_error(env, NULL, "step2Shared: bad arguments (one askState entry per state vector)"); return NULL;
-  }
-  j->n_docs = (uint32_t)(ln / 4);
-  j->n_upd = (uint32_t)(sln / 4);
-  j->off = lens_to_off((const uint32_t *)lens, j->n_docs);
-  j->sv_off = lens_to_off((const uint32_t *)slens, j->n_upd);
-  free(lens); free(slens);
-  if (j->off[j->n_docs] != an || j->sv_off[j->n_upd] != sn) { job_free(j); napi_throw_range_error(env, NULL, "step2Shared: lengths do not match arenas"); return NULL; }
-  if (j->op == 7 && get_opts(env, argc, argv, 6, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "step2Shared: one option byte per state"); return NULL; }
-  if (j->op == 17 && get_opts(env, argc, argv, 6, j->n_upd, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "restoreVersionShared: one option byte per version"); return NULL; }
-  return submit(env, j, argv[0]);
-}
-
-/* snapshotMany(h, arena, lens[, opts]): Y.encodeStateAsUpdate(Y.applyUpdate(new Y.Doc(), u)) per update; opts: one byte
-   per update, YGM_DOC_NO_GC: new Y.Doc({gc: false}) for that one (ygm_snapshot_opts_v1) */
-static napi_value js_snapshot(napi_env env, napi_callback_info info) {
-  size_t argc = 4; napi_value argv[4];
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 3) { napi_throw_type_error(env, NULL, "snapshotMany(handle, arena, lens)"); return NULL; }
-  Handle *h = get_handle(env, argv[0]);
-  if (!h) return NULL;
-  Job *j = (Job *)calloc(1, sizeof(Job)); j->op = 3; j->h = h;
-  size_t an, ln; void *lens = NULL;
-  if (get_bytes(env, argv[1], (void **)&j->arena, &an) || get_bytes(env, argv[2], &lens, &ln)) {
-    free(lens); job_free(j); napi_throw_type_error(env, NULL, "snapshotMany: bad arguments"); return NULL;
-  }
-  j->n_docs = (uint32_t)(ln / 4);
-  j->off = lens_to_off((const uint32_t *)lens, j->n_docs);
-  free(lens);
-  if (j->off[j->n_docs] != an) { job_free(j); napi_throw_range_error(env, NULL, "snapshotMany: sum(lens) != arena length"); return NULL; }
-  if (get_opts(env, argc, argv, 3, j->n_docs, &j->opt)) { job_free(j); napi_throw_range_error(env, NULL, "snapshotMany: one option byte per update"); return NULL; }
-  return submit(env, j, argv[0]);
+  if (j->arena_ref) napi_delete_reference(env, j->arena_ref);
+  job_free(j);
+  snprintf(msg, sizeof msg, "%s: %s", op->name, why);
+  if (range) napi_throw_range_error(env, NULL, msg); else napi_throw_type_error(env, NULL, msg);
+  return NULL;
 }
 
 static napi_value init(napi_env env, napi_value exports) {
-  napi_property_descriptor d[] = {
+  napi_property_descriptor d[6 + N_OPS] = {
     { "open", NULL, js_open, NULL, NULL, NULL, napi_default, NULL },
     { "openNull", NULL, js_open_null, NULL, NULL, NULL, napi_default, NULL },
     { "sleep", NULL, js_sleep, NULL, NULL, NULL, napi_default, NULL },
     { "close", NULL, js_close, NULL, NULL, NULL, napi_default, NULL },
-    { "mergeMany", NULL, js_merge, NULL, NULL, NULL, napi_default, NULL },
-    { "diffMany", NULL, js_diff, NULL, NULL, NULL, napi_default, NULL },
-    /* SyncStep2 of stored documents: encodeStateAsUpdate(applyUpdate(new Doc, state), sv) (MessageReceiver.ts:137-138) */
-    { "step2Many", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)5 },
-    /* many state vectors answered from one state (a reconnect storm): diffUpdate / SyncStep2 per ask */
-    { "diffShared", NULL, js_shared, NULL, NULL, NULL, napi_default, (void *)(intptr_t)6 },
-    { "step2Shared", NULL, js_shared, NULL, NULL, NULL, napi_default, (void *)(intptr_t)7 },
-    { "svMany", NULL, js_sv, NULL, NULL, NULL, napi_default, NULL },
-    { "snapshotMany", NULL, js_snapshot, NULL, NULL, NULL, napi_default, NULL },
-    { "containsMany", NULL, js_contains, NULL, NULL, NULL, napi_default, NULL },
-    /* update format V2 (yjs mergeUpdatesV2 / diffUpdateV2 / encodeStateVectorFromUpdateV2 / 13.6 convertUpdateFormat*) */
-    { "mergeManyV2", NULL, js_merge, NULL, NULL, NULL, napi_default, (void *)(intptr_t)10 },
-    { "diffManyV2", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)11 },
-    { "svManyV2", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)12 },
-    { "convertManyV1ToV2", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)13 },
-    { "convertManyV2ToV1", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)14 },
-    /* version history: Y.encodeSnapshot(Y.snapshot(doc)) per state; Y.createDocFromSnapshot per (state, version)
-       [, option bytes of the restored documents] (ygm_version_take_v1 / ygm_version_restore_v1) */
-    { "takeVersionMany", NULL, js_sv, NULL, NULL, NULL, napi_default, (void *)(intptr_t)15 },
-    { "restoreVersionMany", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)16 },
-    /* many versions restored from one state: one result and one option byte per ask */
-    { "restoreVersionShared", NULL, js_shared, NULL, NULL, NULL, napi_default, (void *)(intptr_t)17 },
-    /* plain text of stored documents: getText(name).toString() or the deep walk per (state, root name) (ygm_text_v1) */
-    { "text", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)18 },
-    /* stored documents as ProseMirror / Tiptap JSON per (state, root name): transformer.fromYdoc(doc, name) (ygm_json_v1) */
-    { "json", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)19 },
-    /* every asked field of stored documents as one JSON object per (state, field list): transformer.fromYdoc(doc) /
-       fromYdoc(doc, [names]) -- a list is lib0 varStrings back to back, none: every root (ygm_json_fields_v1) */
-    { "jsonFields", NULL, js_diff, NULL, NULL, NULL, napi_default, (void *)(intptr_t)20 },
     { "stats", NULL, js_stats, NULL, NULL, NULL, napi_default, NULL },
     { "strerror", NULL, js_strerror, NULL, NULL, NULL, napi_default, NULL },
   };
+  for (size_t i = 0; i < N_OPS; i++) d[6 + i] = (napi_property_descriptor){ OPS[i].name, NULL, js_batch, NULL, NULL, NULL, napi_default, (void *)&OPS[i] };
   napi_define_properties(env, exports, sizeof d / sizeof d[0], d);
   return exports;
 }

@@ -147,6 +147,35 @@ function optBytes (opts, n) {
   return out.some(b => b !== 0) ? out : undefined
 }
 
+// ---- the batched ops of GpuEngine._run: `native` is the addon function (a row of OPS[] in addon/ygm_napi.c), `pack`
+// turns the jobs into its arena arguments, `extra` gives its trailing argument, `timed` keeps the time split (_last)
+const arenas = (...blobLists) => blobLists.flatMap(blobs => { const p = packBlobs(blobs); return [p.arena, p.lens] })
+const packMerge = jobs => { const { arena, lens, docs } = packJobs(jobs); return [arena, lens, docs] }
+const packOne = jobs => arenas(jobs)                                           // a job is an update / a state
+const packPair = jobs => arenas(jobs.map(j => j[0]), jobs.map(j => j[1]))      // a job is [first, second(, option byte)]
+const pairOpts = jobs => optBytes(jobs.map(j => j[2] || 0), jobs.length)
+const OPS = {
+  merge: { native: 'mergeMany', pack: packMerge, extra: jobs => jobs.length, timed: true },
+  mergeV2: { native: 'mergeManyV2', pack: packMerge, extra: jobs => jobs.length, timed: true },
+  diff: { native: 'diffMany', pack: packPair },
+  diffV2: { native: 'diffManyV2', pack: packPair },
+  contains: { native: 'containsMany', pack: packPair },
+  step2: { native: 'step2Many', pack: packPair, extra: pairOpts },
+  restoreVersion: { native: 'restoreVersionMany', pack: packPair, extra: pairOpts },
+  text: { native: 'text', pack: packPair, extra: () => TEXT_FLAT },             // a job is [state, root name bytes]
+  textDeep: { native: 'text', pack: packPair, extra: () => TEXT_DEEP },
+  json: { native: 'json', pack: packPair, extra: () => JSON_PROSEMIRROR },
+  jsonFields: { native: 'jsonFields', pack: packPair, extra: () => JSON_PROSEMIRROR },   // a job is [state, encoded field list]
+  // a job is an update, or { update, opt } for one with an option byte: both kinds share a window
+  snapshot: { native: 'snapshotMany', pack: jobs => arenas(jobs.map(j => j instanceof Uint8Array ? j : j.update)),
+    extra: jobs => optBytes(jobs.map(j => j instanceof Uint8Array ? 0 : j.opt), jobs.length) },
+  takeVersion: { native: 'takeVersionMany', pack: packOne },
+  sv: { native: 'svMany', pack: packOne },
+  svV2: { native: 'svManyV2', pack: packOne },
+  v1ToV2: { native: 'convertManyV1ToV2', pack: packOne },
+  v2ToV1: { native: 'convertManyV2ToV1', pack: packOne }
+}
+
 class GpuEngine {
   /**
    * @param {{device?: number, compat135?: boolean, batchWindowMs?: number, maxBatchDocs?: number}} [opts]
@@ -165,55 +194,31 @@ class GpuEngine {
   }
 
   // one native batch at a time per handle (the addon enforces it; chain them here)
-  _run (op, jobs) {
-    const run = () => {
-      const a = loadAddon()
-      if (op === 'merge' || op === 'mergeV2') {
-        const t0 = now()
-        const { arena, lens, docs } = packJobs(jobs)
-        const t1 = now()
-        const s0 = this.stats()
-        const p = (op === 'merge' ? a.mergeMany : a.mergeManyV2)(this.handle, arena, lens, docs, jobs.length)
-        const t2 = now()
-        return p.then(r => {
-          const s1 = this.stats()
-          this._last = { pack_ms: t1 - t0, napi_in_ms: t2 - t1, native_ms: now() - t2, exec_ms: r.execMs, copy_out_ms: r.completeMs,
-            h2d_ms: s1.h2dMs - s0.h2dMs, kernel_ms: s1.kernelMs - s0.kernelMs, d2h_ms: s1.d2hMs - s0.d2hMs, bytes: arena.length }
-          return r
-        })
-      }
-      if (op === 'diff' || op === 'contains' || op === 'diffV2' || op === 'step2') {
-        const u = packBlobs(jobs.map(j => j[0])); const s = packBlobs(jobs.map(j => j[1]))
-        if (op === 'step2') return a.step2Many(this.handle, u.arena, u.lens, s.arena, s.lens, optBytes(jobs.map(j => j[2] || 0), jobs.length))
-        return ({ diff: a.diffMany, contains: a.containsMany, diffV2: a.diffManyV2 })[op](this.handle, u.arena, u.lens, s.arena, s.lens)
-      }
-      if (op === 'text' || op === 'textDeep') {   // a job is [state, root name bytes]
-        const u = packBlobs(jobs.map(j => j[0])); const n = packBlobs(jobs.map(j => j[1]))
-        return a.text(this.handle, u.arena, u.lens, n.arena, n.lens, op === 'textDeep' ? TEXT_DEEP : TEXT_FLAT)
-      }
-      if (op === 'json') {   // a job is [state, root name bytes]
-        const u = packBlobs(jobs.map(j => j[0])); const n = packBlobs(jobs.map(j => j[1]))
-        return a.json(this.handle, u.arena, u.lens, n.arena, n.lens, JSON_PROSEMIRROR)
-      }
-      if (op === 'jsonFields') {   // a job is [state, encoded field list]
-        const u = packBlobs(jobs.map(j => j[0])); const f = packBlobs(jobs.map(j => j[1]))
-        return a.jsonFields(this.handle, u.arena, u.lens, f.arena, f.lens, JSON_PROSEMIRROR)
-      }
-      if (op === 'restoreVersion') {   // a job is [state, version, option byte]
-        const u = packBlobs(jobs.map(j => j[0])); const v = packBlobs(jobs.map(j => j[1]))
-        return a.restoreVersionMany(this.handle, u.arena, u.lens, v.arena, v.lens, optBytes(jobs.map(j => j[2] || 0), jobs.length))
-      }
-      if (op === 'snapshot') {   // a job is an update, or { update, opt } for one with an option byte: both kinds share a window
-        const u = packBlobs(jobs.map(j => j instanceof Uint8Array ? j : j.update))
-        return a.snapshotMany(this.handle, u.arena, u.lens, optBytes(jobs.map(j => j instanceof Uint8Array ? 0 : j.opt), jobs.length))
-      }
-      const u = packBlobs(jobs)
-      const unary = { snapshot: a.snapshotMany, takeVersion: a.takeVersionMany, sv: a.svMany, svV2: a.svManyV2, v1ToV2: a.convertManyV1ToV2, v2ToV1: a.convertManyV2ToV1 }
-      return unary[op](this.handle, u.arena, u.lens)
-    }
+  _chain (run) {
     const p = this.chain.then(run, run)
     this.chain = p.catch(() => {})
     return p
+  }
+
+  // one batch of `op` (a row of OPS): pack the jobs, call the row's addon function with the row's trailing value
+  _run (op, jobs) {
+    const { native, pack, extra, timed } = OPS[op]
+    return this._chain(() => {
+      const t0 = now()
+      const args = pack(jobs)
+      const t1 = now()
+      if (extra) args.push(extra(jobs))
+      if (!timed) return loadAddon()[native](this.handle, ...args)
+      const s0 = this.stats()
+      const p = loadAddon()[native](this.handle, ...args)
+      const t2 = now()
+      return p.then(r => {
+        const s1 = this.stats()
+        this._last = { pack_ms: t1 - t0, napi_in_ms: t2 - t1, native_ms: now() - t2, exec_ms: r.execMs, copy_out_ms: r.completeMs,
+          h2d_ms: s1.h2dMs - s0.h2dMs, kernel_ms: s1.kernelMs - s0.kernelMs, d2h_ms: s1.d2hMs - s0.d2hMs, bytes: args[0].length }
+        return r
+      })
+    })
   }
 
   /** Y.mergeUpdates(updates), batched with concurrent callers. */
@@ -268,14 +273,10 @@ class GpuEngine {
       if (!Number.isInteger(askState[a]) || askState[a] < 0 || askState[a] >= states.length) throw new YgmError(8, loadAddon().strerror(8))
     }
     const order = Array.from({ length: n }, (_, a) => a).sort((x, y) => askState[x] - askState[y] || x - y)
-    const run = () => {
-      const u = packBlobs(states); const v = packBlobs(order.map(a => svs[a]))
+    const r = unpack(await this._chain(() => {
       const o = opt && optPerAsk ? Uint8Array.from(order, a => opt[a]) : opt   // (per-ask bytes travel with their asks)
-      return loadAddon()[op](this.handle, u.arena, u.lens, v.arena, v.lens, Uint32Array.from(order, a => askState[a]), o)
-    }
-    const p = this.chain.then(run, run)
-    this.chain = p.catch(() => {})
-    const r = unpack(await p)
+      return loadAddon()[op](this.handle, ...arenas(states, order.map(a => svs[a])), Uint32Array.from(order, a => askState[a]), o)
+    }))
     const out = new Array(n)
     order.forEach((a, k) => { out[a] = r[k] })
     return out
@@ -321,10 +322,7 @@ class GpuEngine {
    * ends in one (ygm_text_v1).  names: strings or UTF-8 bytes.  A name the state has no root for gives ''.
    */
   async textMany (states, names, { deep = false } = {}) {
-    if (names.length !== states.length) throw new YgmError(8, 'one root name per state')
-    const jobs = states.map((s, i) => [s, names[i] instanceof Uint8Array ? names[i] : Buffer.from(String(names[i]), 'utf8')])
-    const r = await this._run(deep ? 'textDeep' : 'text', jobs)
-    return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
+    return unpackUtf8(await this._run(deep ? 'textDeep' : 'text', rootJobs(states, names)))
   }
 
   /**
@@ -335,10 +333,7 @@ class GpuEngine {
    * is no XmlFragment of elements and texts, a float, ...) gives a YgmError in its place.
    */
   async jsonMany (states, names) {
-    if (names.length !== states.length) throw new YgmError(8, 'one root name per state')
-    const jobs = states.map((s, i) => [s, names[i] instanceof Uint8Array ? names[i] : Buffer.from(String(names[i]), 'utf8')])
-    const r = await this._run('json', jobs)
-    return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
+    return unpackUtf8(await this._run('json', rootJobs(states, names)))
   }
 
   /**
@@ -351,9 +346,7 @@ class GpuEngine {
    */
   async jsonFieldsMany (states, fields) {
     if (fields.length !== states.length) throw new YgmError(8, 'one field list per state')
-    const jobs = states.map((s, i) => [s, encodeFields(fields[i])])
-    const r = await this._run('jsonFields', jobs)
-    return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
+    return unpackUtf8(await this._run('jsonFields', states.map((s, i) => [s, encodeFields(fields[i])])))
   }
 
   /** update format V2 (yjs providers other than Hocuspocus's V1 path): Y.mergeUpdatesV2 / Y.diffUpdateV2 /
@@ -370,6 +363,14 @@ class GpuEngine {
 
 function unpack (r) {
   return Array.from(r.status, (st, i) => st === 0 ? r.outputs[i] : new YgmError(st, loadAddon().strerror(st)))
+}
+// the text / JSON calls: jobs of [state, root name bytes] (names: strings or UTF-8 bytes); each output as a string
+function rootJobs (states, names) {
+  if (names.length !== states.length) throw new YgmError(8, 'one root name per state')
+  return states.map((s, i) => [s, names[i] instanceof Uint8Array ? names[i] : Buffer.from(String(names[i]), 'utf8')])
+}
+function unpackUtf8 (r) {
+  return unpack(r).map(x => x instanceof Error ? x : Buffer.from(x.buffer, x.byteOffset, x.length).toString('utf8'))
 }
 
 const FNV_OFFSET = BigInt('0xcbf29ce484222325')

@@ -674,6 +674,14 @@ test('update V2 batches match yjs mergeUpdatesV2 / diffUpdateV2 / encodeStateVec
   const peer = logs.map(l => Y.encodeStateVectorFromUpdateV2(Y.mergeUpdatesV2(l.slice(0, 2))))
   const diffs = await engine.diffManyV2(merged, peer)
   merged.forEach((m, i) => assert.strictEqual(Buffer.from(diffs[i]).toString('hex'), Buffer.from(Y.diffUpdateV2(m, peer[i])).toString('hex')))
+  if (mode === 'gpu') {   // the format converters (the CPU double has none): V2 -> V1 -> V2 is the identity, and the V1 form has the same state vector
+    const v1 = await engine.convertManyV2ToV1(merged)
+    const back = await engine.convertManyV1ToV2(v1)
+    merged.forEach((m, i) => {
+      assert.strictEqual(Buffer.from(back[i]).toString('hex'), Buffer.from(m).toString('hex'))
+      assert.strictEqual(Buffer.from(Y.encodeStateVectorFromUpdate(v1[i])).toString('hex'), Buffer.from(svs[i]).toString('hex'))
+    })
+  }
 })
 
 async function main () {

@@ -22,6 +22,47 @@ def test_header_declares_the_boundary():
     assert set(fns) == set(eng.EXPORTS)
 
 
+def header_prototypes():
+    """name -> (result kind, argument kinds) of every prototype in include/ygm.h, in the kinds of eng.SIGNATURES."""
+    src = open(os.path.join(ROOT, "include", "ygm.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"\b(int|void|const\s+char\s*\*)\s*(ygm_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
+        ret = {"int": "int", "void": "void"}.get(ret, "str")
+        params = [" ".join(p.split()) for p in params.split(",")]
+        protos[name] = (ret, () if params == ["void"] else tuple(param_kind(p) for p in params))
+    return protos
+
+
+def param_kind(p):
+    for struct, kind in (("ygm_result *", "res"), ("ygm_device_result *", "dres"), ("ygm_stats_t *", "stats"), ("ygm_ctx **", "ctxp")):
+        if p.startswith(struct):
+            return kind
+    if "*" in p:
+        return "p"
+    return {"uint64_t": "u64", "uint32_t": "u32", "int": "int"}[p.split()[0]]
+
+
+def test_signature_table_matches_the_header():
+    protos = header_prototypes()
+    assert list(protos) == list(eng.SIGNATURES) and set(protos) == set(header_functions())   # names, in the header's order
+    for name, (ret, args) in protos.items():
+        assert eng.SIGNATURES[name] == (args, ret), name
+    assert eng.EXPORTS == tuple(eng.SIGNATURES)
+
+
+def test_lib_sets_every_signature_from_the_table():
+    L = eng.lib()
+    for name, (args, ret) in eng.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.argtypes == [eng._KIND[k] for k in args], name
+        assert fn.restype is eng._RET[ret], name
+    assert eng._KIND["u64"] is ctypes.c_uint64 and eng._KIND["u32"] is ctypes.c_uint32 and eng._KIND["int"] is ctypes.c_int
+    assert eng._KIND["p"] is ctypes.c_void_p and eng._RET == {"int": ctypes.c_int, "void": None, "str": ctypes.c_char_p}
+    assert eng._KIND["res"]._type_ is eng._Result and eng._KIND["dres"]._type_ is eng._DevResult
+    assert eng._KIND["stats"]._type_ is eng.Stats and eng._KIND["ctxp"]._type_ is ctypes.c_void_p
+
+
 def test_library_exports_every_declared_symbol():
     L = ctypes.CDLL(eng.LIB_PATH)
     for f in header_functions():

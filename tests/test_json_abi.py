@@ -33,5 +33,6 @@ def test_engine_binds_them():
     assert "ygm_json_v1" in eng.EXPORTS and "ygm_json_v1_device" in eng.EXPORTS
     assert eng.JSON_PROSEMIRROR == 0
     assert callable(eng.Engine.json_batch) and callable(eng.Engine.json_device)
-    src = open(eng.__file__).read()
-    assert "L.ygm_json_v1.argtypes" in src and "L.ygm_json_v1_device.argtypes" in src
+    # their signatures, from the table lib() sets every argtypes / restype from (tests/test_abi.py holds it to the header)
+    assert eng.SIGNATURES["ygm_json_v1"] == (("p", "p", "p", "p", "p", "u32", "u32", "res"), "int")
+    assert eng.SIGNATURES["ygm_json_v1_device"] == (("p", "p", "u64", "p", "p", "p", "u32", "u32", "p", "dres"), "int")

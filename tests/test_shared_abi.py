@@ -46,6 +46,15 @@ def test_null_context_is_einval():
         st = getattr(L, f)(None, state, ctypes.cast(off, ctypes.c_void_p), 1, b"\x00", ctypes.cast(sv_off, ctypes.c_void_p),
                            ctypes.cast(ask, ctypes.c_void_p), 1, ctypes.byref(res))
         assert st == eng.EINVAL, f
+    # the plain forms of the calls that have an options form: the bindings reach them only through that form (with a
+    # null option pointer), so they are called here -- a null context returns before any device work
+    st_off, sv = ctypes.cast(off, ctypes.c_void_p), ctypes.cast(sv_off, ctypes.c_void_p)
+    assert L.ygm_snapshot_v1(None, state, st_off, 1, ctypes.byref(res)) == eng.EINVAL
+    assert L.ygm_sync_step2_v1(None, state, st_off, b"\x00", sv, 1, ctypes.byref(res)) == eng.EINVAL
+    dres = eng._DevResult()
+    assert L.ygm_snapshot_v1_device(None, None, 0, None, 0, None, ctypes.byref(dres)) == eng.EINVAL
+    assert L.ygm_sync_step2_v1_device(None, None, 0, None, None, None, 0, None, ctypes.byref(dres)) == eng.EINVAL
+    assert L.ygm_sync_step2_shared_v1_device(None, None, 0, None, 0, None, None, None, 0, None, ctypes.byref(dres)) == eng.EINVAL
 
 
 def test_stats_mirror_ends_with_docs_snapshot():
