@@ -26,7 +26,12 @@ static __device__ unsigned long long ygm_diag_sw[16384 * 2];
 #define DIAGSW_T0 unsigned long long _sw = 0; const unsigned long long _sl = __builtin_amdgcn_s_memtime();
 #define DIAGSW_WAIT do { const unsigned long long _a = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0x0F70); _sw += __builtin_amdgcn_s_memtime() - _a; } while (0)
 #define DIAGSW_END do { if (threadIdx.x == 0) { ygm_diag_sw[(blockIdx.x & 16383u) * 2] = _sw; ygm_diag_sw[(blockIdx.x & 16383u) * 2 + 1] = __builtin_amdgcn_s_memtime() - _sl; } } while (0)
+// narrow lean kernel: documents that reached the fast parse [0], and of them those that took it with the five-byte
+// client id built in [1] (tools/diag_idlen.py sets the counts against the corpus)
+static __device__ unsigned long long ygm_diag_id5[2];
+#define DIAG_ID5(on) do { if (threadIdx.x == 0) { atomicAdd(&ygm_diag_id5[0], 1ull); if (on) atomicAdd(&ygm_diag_id5[1], 1ull); } } while (0)
 #else
+#define DIAG_ID5(on)
 #define DIAGSW_T0
 #define DIAGSW_WAIT
 #define DIAGSW_END

@@ -91,6 +91,7 @@ struct PinBuf {
 struct ygm_ctx {
   int device = 0;
   uint32_t flags = 0;
+  uint32_t lean_flags = 0;   // bits for the narrow lean kernel alone (LN_F_NO_IDLEN: YGM_LN_NO_IDLEN, read at ygm_open)
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;   // the large-document tier's 16-wave launch, beside the mid size's on `stream`
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
@@ -173,6 +174,8 @@ int ygm_open(int device, uint32_t flags, ygm_ctx** out) {
   if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return YGM_EDEVICE;
   ygm_ctx* c = new ygm_ctx();
   c->device = device; c->flags = flags;
+  // YGM_LN_NO_IDLEN (A/B runs and tests inside one build): every document takes the narrow lean kernel's generic parse
+  c->lean_flags = getenv("YGM_LN_NO_IDLEN") != nullptr ? ygm_k_lean_no_idlen_flag() : 0u;
   // stream2 (the large-document tier's 16-wave size) is created at the high priority on first use: a queue of its own
   // (a process with more streams than hardware queues shares them, and two streams on one queue run their kernels
   // one after the other); contexts that never run that size (the host API's stage contexts, most pool members) do
@@ -304,7 +307,7 @@ static int merge_async(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes,
                                      c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), meta, meta_next,
                                      c->defer_w_list.as<uint32_t>(), out_cap, d_upd_len, s))
       return YGM_EDEVICE;
-  } else if (ygm_k_launch_merge_lean(d_arena, d_upd_off, d_doc_upd, n_docs, c->flags, c->out.as<uint8_t>(), c->out_off.as<uint64_t>(),
+  } else if (ygm_k_launch_merge_lean(d_arena, d_upd_off, d_doc_upd, n_docs, c->flags | c->lean_flags, c->out.as<uint8_t>(), c->out_off.as<uint64_t>(),
                                      c->out_len.as<uint64_t>(), c->status.as<int32_t>(), meta, meta_next, c->defer_list.as<uint32_t>(), out_cap, s,
                                      d_doc_off, d_upd_len))
     return YGM_EDEVICE;

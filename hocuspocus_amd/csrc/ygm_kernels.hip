@@ -1177,16 +1177,41 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
         LFastIn F[YGM_LN_FASTGROUP];
 #pragma unroll
         for (int q = g; q < g + YGM_LN_FASTGROUP; q++) lean_fast_load(lin, lout, us[q], un[q], F[q - g]);
+        // the client id's length, decided once for the document (all four rows loaded together): no update with
+        // structs whose id is not five bytes -- one ballot, a second for a document that fails the first -- and every
+        // row takes the parse with that length built in
+        bool id5 = false;
+#if YGM_LN_FASTGROUP == 4   // (the test needs all four rows loaded together)
+        if ((flags & LN_F_NO_IDLEN) == 0u) {
+          // first the lane's four updates at once, every lane: bytes 2 .. 5 with the top bit in all four (the `and` of
+          // the masks), byte 6 without it in all four (their `or`).  A lane without an update holds the document's
+          // first update again and changes nothing.  Only a document that fails this is asked again update by update,
+          // leaving out the delete-set-only ones
+          const uint32_t ha = F[0].H & F[1].H & F[2].H & F[3].H, ho = F[0].H | F[1].H | F[2].H | F[3].H;
+          id5 = __ballot(((ha & 0x3Cu) | (ho & 0x40u)) != 0x3Cu) == 0;
+          if (!id5) {
+            bool wit = false;
 #pragma unroll
-        for (int q = g; q < g + YGM_LN_FASTGROUP; q++) {
-          const bool valid = ln_owns(l, q, k);
-          bool hd;
-          const bool fast = q == 0 ? lean_parse_fast<true>(F[q - g], us[q], un[q], valid, rec[q], hd)
-                                   : lean_parse_fast<false>(F[q - g], us[q], un[q], valid, rec[q], hd);
-          slow[q] = !fast && valid;
-          hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
-          hasd[q] = valid && hd;
+            for (int q = 0; q < YGM_LN_FASTGROUP; q++) wit |= ln_owns(l, q, k) && !lean_id5_ok(F[q]);
+            id5 = __ballot(wit) == 0;
+          }
         }
+#endif
+        auto rows = [&](auto id5_c) {
+          constexpr bool ID5 = decltype(id5_c)::value;
+#pragma unroll
+          for (int q = g; q < g + YGM_LN_FASTGROUP; q++) {
+            const bool valid = ln_owns(l, q, k);
+            bool hd;
+            const bool fast = q == 0 ? lean_parse_fast<true, ID5>(F[q - g], us[q], un[q], valid, rec[q], hd)
+                                     : lean_parse_fast<false, ID5>(F[q - g], us[q], un[q], valid, rec[q], hd);
+            slow[q] = !fast && valid;
+            hs[q] = valid && (rec[q].span & 0xFF00u) != 0u;
+            hasd[q] = valid && hd;
+          }
+        };
+        DIAG_ID5(id5);
+        if (id5) rows(std::true_type()); else rows(std::false_type());
       }
 #pragma unroll
       for (int q = 0; q < LN_ROWS; q++) {
@@ -1348,7 +1373,10 @@ __global__ __launch_bounds__(WAVE, WIDE ? 3 : YGM_LN_OCC) void k_merge_lean(cons
           // block headers, lane c = block c; their lengths to scalars (four blocks: no scan)
           uint32_t hlen = 0;
           if (l < nC) {
-            hcnt = (cA >> (8u * (l & 3u))) & 0xFFu; hfc = fcl;
+            // (the lane's bit offset from lane_opaque: from threadIdx.x it is hoisted out of the persistent loop and spilled.
+            // This branch is the log-order placement's, compiled for the narrow kernel alone: `sighted` is false at
+            // compile time in the wide one, whose instructions do not change)
+            hcnt = (cA >> (8u * (lane_opaque() & 3u))) & 0xFFu; hfc = fcl;
             hlen = vlen32(hcnt) + vlen32(ctl) + vlen32(hfc);
           }
           const uint32_t h0 = rdlane(hlen, 0), h1 = rdlane(hlen, 1), h2 = rdlane(hlen, 2), h3 = rdlane(hlen, 3);
@@ -3446,6 +3474,11 @@ int ygm_diag_ds_read(unsigned long long* out, int reset) {   // 4 delete-set uni
   if (reset) { unsigned long long z[4] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(ygm_diag_ds), z, sizeof z); }
   return 0;
 }
+int ygm_diag_id5_read(unsigned long long* out, int reset) {   // 2 counts: documents fast-parsed by the narrow lean kernel, of them with the id length built in
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ygm_diag_id5), sizeof(unsigned long long) * 2) != hipSuccess) return -1;
+  if (reset) { unsigned long long z[2] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(ygm_diag_id5), z, sizeof z); }
+  return 0;
+}
 int ygm_diag_read(unsigned long long* out, int reset) {   // 32 sums: k_merge_fast's, k_merge_wave's, k_merge_big's (ygm_diag.hpp)
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ygm_diag), sizeof(unsigned long long) * 32) != hipSuccess) return -1;
   if (reset) { unsigned long long z[32] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(ygm_diag), z, sizeof z); }
@@ -3668,6 +3701,7 @@ static uint32_t resident_blocks(K kernel, int threads, uint32_t fallback) {
 
 
 uint32_t ygm_k_lean_stage_bytes() { return (uint32_t)LN_IN; }   // input bytes the narrow lean kernel stages per document
+uint32_t ygm_k_lean_no_idlen_flag() { return LN_F_NO_IDLEN; }
 // doc_off / upd_len non-null: the compact input form (ygm_merge_v1_device_lens); upd_off is then unused
 int ygm_k_launch_merge_lean(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, uint32_t flags,
                             uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, void* meta_next,

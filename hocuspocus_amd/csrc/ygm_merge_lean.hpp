@@ -29,7 +29,9 @@
 //           the update's 32 bits of either staged mask (one ds_read2_b32 and one v_alignbit each) and its
 //           last three bytes, with no read that depends on the window; only a row holding another shape
 //           runs lean_parse, the generic grammar (multi-struct, parents, ContentDeleted, longer strings),
-//           on a 32-byte window and masks of its own, whose dependent byte reads cost an LDS round trip each
+//           on a 32-byte window and masks of its own, whose dependent byte reads cost an LDS round trip each.  A
+//           document whose every update with structs has a five-byte client id (lean_id5_ok: one or two ballots)
+//           takes lean_parse_fast with that length built in
 //   clients distinct clients by wave vote, in descending order (one wave max per client).  Narrow kernel, every row
 //           fast: the vote by first sight -- the candidate is the client of the first unassigned record in log
 //           order (one ballot, two readlanes: the second brings that record's clock, the block's first clock), a
@@ -177,6 +179,12 @@ struct LRec {
 // against the ladder, every x at every length)
 YDEV uint32_t pext28(uint32_t x, uint32_t n) {
   const uint32_t m = __builtin_amdgcn_ubfe(x, 0u, min(8u * n, 31u)) & 0x7f7f7f7fu;
+  const uint32_t lo = __builtin_amdgcn_udot4(m, 0x00008001u, 0u, false), hi = __builtin_amdgcn_udot4(m, 0x80010000u, 0u, false);
+  return lo | (hi << 14);
+}
+// the same of a varuint known to have four bytes or more: no length cut (the 0x7f mask drops bit 31 as the 31-bit cut does)
+YDEV uint32_t pext28_full(uint32_t x) {
+  const uint32_t m = x & 0x7f7f7f7fu;
   const uint32_t lo = __builtin_amdgcn_udot4(m, 0x00008001u, 0u, false), hi = __builtin_amdgcn_udot4(m, 0x80010000u, 0u, false);
   return lo | (hi << 14);
 }
@@ -348,7 +356,8 @@ YDEV LRec lean_parse(LB8* in, uint32_t s, uint32_t n) {
 // address is known from (s, n) alone: the loads of every row are issued before the first is used.  A
 // lane that is not fast proves nothing: its row runs lean_parse.  A fast lane's record is lean_parse's.
 #ifndef YGM_LN_FASTGROUP
-#define YGM_LN_FASTGROUP 4    // rows whose loads are issued together (1, 2 or 4)
+#define YGM_LN_FASTGROUP 4    // rows whose loads are issued together (1, 2 or 4).  Only 4 decides the client id's length per
+                              // document (the test needs every row's mask): a build with 1 or 2 takes the generic parse always
 #endif
 // The fast parse's two byte masks -- H: top bit set, Z: zero byte ("haszero": may also flag a 0x01 right above a zero byte) -- are
 // properties of the staged bytes, not of an update, so they are made once per staged 16-byte chunk, from the prefetch
@@ -385,12 +394,32 @@ YDEV void lean_fast_load(LB8* in, LB8* masks, uint32_t s, uint32_t n, LFastIn& F
   const uint32_t t = s + (n > 3u ? n : 3u);
   F.tl = in[t - 3u]; F.td = in[t - 1u];
 }
+// a bit of the narrow kernel's `flags` (above the context flags of include/ygm.h; set by YGM_LN_NO_IDLEN, A/B runs and
+// tests): no document takes the five-byte-id parse
+constexpr uint32_t LN_F_NO_IDLEN = 0x100u;
+// The client id's length decided once per document.  Yjs draws client ids as random uint32: fifteen of sixteen are
+// >= 2^28 and take five bytes, so in most documents every update's id does -- and then the client's end (byte 6), the
+// clock's position (byte 7), the funnel shift that brings the clock's window and the length cut of the id's value are
+// constants, where the generic parse derives each from a ctz of the terminator mask, at the head of its dependent
+// chain.  true: the update is no witness against that -- it has no structs (its block count is 0: a delete set only),
+// or bytes 2 .. 5 carry the top bit and byte 6 does not.  For an update that passes, lean_parse_fast<., true> returns
+// exactly what lean_parse_fast<., false> returns: with seven bytes or more the generic one computes e = 6 from the
+// same bits (bits 2 .. 6 of its terminator mask are 10000b); a shorter one, whose bits 2 .. 6 belong to its
+// successor, is no item under either -- no shape of nine bytes or more fits its length -- and the rest of the answer
+// does not depend on the id.  tools/idlen_check.cpp holds the check on the CPU, at every update length.  (Taken from
+// H, not from the parse's masks: sharing V, T and HV of the four rows between the test and the parses costs two more
+// live registers per row, and the kernel then spills)
+YDEV bool lean_id5_ok(const LFastIn& F) {
+  return (F.d[0] & 0xFFu) == 0u || ((F.H >> 2) & 0x1Fu) == 0x0Fu;
+}
 // true: R is the update's record (R.ok) and hasd whether its delete set is non-empty.
 // Called by the whole wave, one row at a time (valid: the lane's slot of this row holds an update).  The parent-ykey
 // shape is evaluated only for a row that has a valid lane with neither origin -- one ballot and one scalar branch
 // per row: in a debounce log that is update 0 alone, slot 0 of lane 0.  KEYROW (row 0) evaluates it without asking.
-// A lane the branch skips is not the parent-ykey shape (it has an origin, or it is not valid: n == 0, no shape fits)
-template <bool KEYROW>
+// A lane the branch skips is not the parent-ykey shape (it has an origin, or it is not valid: n == 0, no shape fits).
+// ID5: the document passed lean_id5_ok in every lane -- the client id is bytes 2 .. 6.  (A lane without an update
+// or without structs is no item under either instantiation: n == 0 fits no shape, a block count of 0 is `bad`)
+template <bool KEYROW, bool ID5 = false>
 YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, LRec& R, bool& hasd) {
   const uint32_t (&d)[4] = F.d;
   const uint32_t H = F.H, Z = F.Z;
@@ -406,20 +435,23 @@ YDEV bool lean_parse_fast(const LFastIn& F, uint32_t s, uint32_t n, bool valid, 
   bad |= (b0 ^ 1u) | (b1 ^ 1u);                // one block of one struct
   // client (bytes 2..e) and clock (bytes p..e): ends from the terminator mask.  A varuint that runs out
   // of the window ends at >= 31, which the length test below (the structs end at n - 1 <= 31) refuses
-  uint32_t e = 2u + lnctz(T >> 2);
+  uint32_t e = ID5 ? 6u : 2u + lnctz(T >> 2);
   const uint32_t cl_n = e - 1u;
   // the fifth byte, taken once where the varuint has one: its low four bits are the value's top bits, a bit of 0x70
   // is past a uint32; six bytes and more are refused by arithmetic on the length (1 .. 32 here; a clock length that
   // wraps has p > 31: a client of thirty bytes, refused already)
-  const uint32_t cl_y = cl_n >= 5u ? (d[1] >> 16) & 0xFFu : 0u;
-  const uint32_t client = pext28(__builtin_amdgcn_alignbyte(d[1], d[0], 2u), cl_n) | (cl_y << 28);
-  bad |= lean_vu_over5(cl_n) | (cl_y & 0x70u);
+  const uint32_t cl_y = ID5 || cl_n >= 5u ? (d[1] >> 16) & 0xFFu : 0u;
+  const uint32_t cl_x = __builtin_amdgcn_alignbyte(d[1], d[0], 2u);
+  const uint32_t client = (ID5 ? pext28_full(cl_x) : pext28(cl_x, cl_n)) | (cl_y << 28);
+  bad |= (ID5 ? 0u : lean_vu_over5(cl_n)) | (cl_y & 0x70u);
   const uint32_t p = e + 1u;                   // 3..7 when the client is good
   const uint32_t pc = p < 31u ? p : 31u;
   e = pc + lnctz(T >> pc);
   const uint32_t ck_n = e - p + 1u;
   const uint64_t U01 = ((uint64_t)d[1] << 32) | d[0], U23 = ((uint64_t)d[3] << 32) | d[2];
-  const uint64_t cw = (U01 >> (8u * (p & 7u))) | (p & 7u ? (U23 << (64u - 8u * (p & 7u))) : 0ull);   // bytes p..p+7
+  // bytes p..p+7; at p = 7 two funnels with a constant count
+  const uint64_t cw = ID5 ? ((uint64_t)__builtin_amdgcn_alignbyte(d[3], d[2], 3u) << 32) | __builtin_amdgcn_alignbyte(d[2], d[1], 3u)
+                          : (U01 >> (8u * (p & 7u))) | (p & 7u ? (U23 << (64u - 8u * (p & 7u))) : 0ull);
   const uint32_t ck_y = ck_n >= 5u ? (uint32_t)(cw >> 32) & 0xFFu : 0u;
   const uint32_t clock = pext28((uint32_t)cw, ck_n) | (ck_y << 28);
   bad |= lean_vu_over5(ck_n) | (ck_y & 0x70u);
