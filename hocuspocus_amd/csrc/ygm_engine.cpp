@@ -794,9 +794,13 @@ int ygm_text_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_byte
 // buffer grows by that region (the workspaces, which hold the other documents' outputs, are kept) and k_json runs
 // again for the listed documents alone -- one more host wait.  fields: the second arena holds a field list per
 // document (ygm_json_fields_v1): the same batch, k_json's fields instantiation in both launches.
+// tojson: ygm_tojson_v1 -- the same batch with k_tojson in both launches, its kind one of YGM_TOJSON_*; the load is
+// the snapshot's (counted in docs_snapshot).
 static int json_dev(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, const uint8_t* d_names,
-                    const uint64_t* d_name_off, uint32_t kind, uint32_t n_docs, void* stream, ygm_device_result* out, int fields) {
-  if (!c || !out || kind != YGM_JSON_PROSEMIRROR || (n_docs && (!d_state_off || !d_name_off))) return YGM_EINVAL;
+                    const uint64_t* d_name_off, uint32_t kind, uint32_t n_docs, void* stream, ygm_device_result* out, int fields,
+                    int tojson = 0) {
+  if (!c || !out || (tojson ? kind > YGM_TOJSON_TEXT : kind != YGM_JSON_PROSEMIRROR) || (n_docs && (!d_state_off || !d_name_off)))
+    return YGM_EINVAL;
   (void)hipSetDevice(c->device);
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const uint32_t fl = c->flags;
@@ -811,6 +815,10 @@ static int json_dev(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, 
   if (n_docs) {
     if ((e = ws_plan(B, d_states, d_state_off, fl))) return e;
     auto launch = [&](uint32_t n_list, int again) {
+      if (tojson)
+        return ygm_k_launch_tojson(d_states, d_state_off, d_names, d_name_off, n_docs, fl, kind, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
+                                   c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.meta,
+                                   0, B.total, c->sn_pend.as<uint32_t>(), n_list, again, s);
       return ygm_k_launch_json(d_states, d_state_off, d_names, d_name_off, n_docs, fl, kind, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
                                c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.meta, 0,
                                B.total, c->sn_pend.as<uint32_t>(), n_list, again, fields, s);
@@ -825,7 +833,9 @@ static int json_dev(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, 
     }
   }
   if (getenv("YGM_TIER_COUNTS"))   // (testing knob, as the text's line)
-    fprintf(stderr, "ygm json tiers: docs %u general %u overflow %u overflow_bytes %llu\n", n_docs, n_docs, reran, (unsigned long long)ovf);
+    fprintf(stderr, "ygm %s tiers: docs %u general %u overflow %u overflow_bytes %llu\n", tojson ? "tojson" : "json", n_docs, n_docs, reran,
+            (unsigned long long)ovf);
+  if (tojson) c->stats.docs_snapshot += n_docs;
   return ws_finish(B, states_bytes, c->sn_ws.as<uint8_t>(), B.total + ovf, m.payload, out);
 }
 int ygm_json_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, const uint8_t* d_names,
@@ -835,6 +845,10 @@ int ygm_json_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_byte
 int ygm_json_fields_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, const uint8_t* d_fields,
                               const uint64_t* d_field_off, uint32_t kind, uint32_t n_docs, void* stream, ygm_device_result* out) {
   return json_dev(c, d_states, states_bytes, d_state_off, d_fields, d_field_off, kind, n_docs, stream, out, 1);
+}
+int ygm_tojson_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, const uint64_t* d_state_off, const uint8_t* d_names,
+                         const uint64_t* d_name_off, uint32_t kind, uint32_t n_docs, void* stream, ygm_device_result* out) {
+  return json_dev(c, d_states, states_bytes, d_state_off, d_names, d_name_off, kind, n_docs, stream, out, 0, 1);
 }
 // a snapshot batch's outputs packed into one arena on the device (k_pack_*: offsets n + 1, the total at [n]) with its
 // statuses, for kernels that read documents by offsets (step2's diff, contains)
@@ -1372,7 +1386,7 @@ namespace {
 // The host API's operations; OPS below holds one row per operation, in this order.
 enum class Op : uint8_t {
   Sv, Diff, Merge, Snapshot, Contains, MergeV2, DiffV2, SvV2, V1ToV2, V2ToV1, Step2, DiffShared, Step2Shared, VersionTake,
-  VersionRestore, VersionRestoreShared, Text, Json, JsonFields, Count
+  VersionRestore, VersionRestoreShared, Text, Json, JsonFields, ToJson, Count
 };
 enum class Primary : uint8_t { Docs, Updates, States };   // what the first arena's offsets count
 enum class OptOf : uint8_t { None, Doc, State, Ask };     // whose option bytes travel with a chunk
@@ -1384,7 +1398,7 @@ struct HostCall {
   const uint32_t* link = nullptr;   // merge: each update's document; shared: each ask's state
   const uint8_t* arena2 = nullptr; const uint64_t* off2 = nullptr;   // the second arena, one entry per result (OpRow::second)
   const uint8_t* opt = nullptr;     // option bytes (OpRow::opt says whose), null: none; each chunk stages its slice
-  uint32_t text_mode = 0;           // Op::Text: YGM_TEXT_FLAT / YGM_TEXT_DEEP; Op::Json, Op::JsonFields: the kind (YGM_JSON_PROSEMIRROR)
+  uint32_t text_mode = 0;           // Op::Text: YGM_TEXT_FLAT / YGM_TEXT_DEEP; Op::Json, Op::JsonFields, Op::ToJson: the kind
 };
 // a chunk's inputs on its stage context, as the device entry points take them
 struct Staged {
@@ -1468,6 +1482,9 @@ static int run_json(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
 static int run_json_fields(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
   return ygm_json_fields_v1_device(k, S.arena, S.bytes, S.off, S.arena2, S.off2, S.text_mode, S.n_res, nullptr, dr);
 }
+static int run_tojson(ygm_ctx* k, const Staged& S, ygm_device_result* dr) {
+  return ygm_tojson_v1_device(k, S.arena, S.bytes, S.off, S.arena2, S.off2, S.text_mode, S.n_res, nullptr, dr);
+}
 
 constexpr OpRow OPS[] = {
     {Op::Sv, Primary::Docs, false, OptOf::None, run_sv, nullptr},
@@ -1489,6 +1506,7 @@ constexpr OpRow OPS[] = {
     {Op::Text, Primary::Docs, true, OptOf::None, run_text, nullptr},
     {Op::Json, Primary::Docs, true, OptOf::None, run_json, nullptr},
     {Op::JsonFields, Primary::Docs, true, OptOf::None, run_json_fields, nullptr},
+    {Op::ToJson, Primary::Docs, true, OptOf::None, run_tojson, nullptr},
 };
 constexpr bool ops_in_order() {
   for (size_t i = 0; i < sizeof(OPS) / sizeof(OPS[0]); i++) if (OPS[i].op != (Op)i) return false;
@@ -1821,6 +1839,16 @@ int ygm_json_fields_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_
   static const uint8_t no_fields[1] = {0};   // (every list empty: the arena may be NULL)
   if (n_docs && !fields) { if (field_off[n_docs] != field_off[0]) return YGM_EINVAL; fields = no_fields; }   // (no byte of it is read)
   HostCall H{Op::JsonFields, states, n_docs ? state_off : ZERO_OFF, n_docs, n_docs, nullptr, fields, n_docs ? field_off : ZERO_OFF};
+  H.text_mode = kind;
+  return host_call(c, H, out);
+}
+int ygm_tojson_v1(ygm_ctx* c, const uint8_t* states, const uint64_t* state_off, const uint8_t* names, const uint64_t* name_off, uint32_t kind,
+                  uint32_t n_docs, ygm_result* out) {
+  if (!c || !out || kind > YGM_TOJSON_TEXT || (n_docs && (!states || !state_off || !name_off))) return YGM_EINVAL;
+  for (uint32_t d = 0; d < n_docs; d++) if (state_off[d + 1] < state_off[d] || name_off[d + 1] < name_off[d]) return YGM_EINVAL;
+  static const uint8_t no_names[1] = {0};   // (every name empty: the arena may be NULL)
+  if (n_docs && !names) { if (name_off[n_docs] != name_off[0]) return YGM_EINVAL; names = no_names; }   // (no byte of it is read)
+  HostCall H{Op::ToJson, states, n_docs ? state_off : ZERO_OFF, n_docs, n_docs, nullptr, names, n_docs ? name_off : ZERO_OFF};
   H.text_mode = kind;
   return host_call(c, H, out);
 }

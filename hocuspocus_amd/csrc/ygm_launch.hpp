@@ -54,6 +54,10 @@ int ygm_k_launch_json(const uint8_t* arena, const uint64_t* doc_off, const uint8
                       uint32_t flags, uint32_t kind, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
                       uint64_t* out_len, int32_t* status, void* meta, uint64_t base, uint64_t ovf_base, uint32_t* list, uint32_t n_list,
                       int again, int fields, hipStream_t s);
+int ygm_k_launch_tojson(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
+                        uint32_t flags, uint32_t kind, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
+                        uint64_t* out_len, int32_t* status, void* meta, uint64_t base, uint64_t ovf_base, uint32_t* list, uint32_t n_list,
+                        int again, hipStream_t s);
 int ygm_k_launch_cont_plan(const uint8_t* st_arena, const uint64_t* st_off, uint32_t n_docs, uint32_t flags, uint64_t* ws_off, uint64_t* bs,
                            hipStream_t s);
 int ygm_k_launch_cont(const uint8_t* st_arena, const uint64_t* st_off, const uint8_t* up_arena, const uint64_t* up_off, uint32_t n_docs,

@@ -1,0 +1,97 @@
+// ygm_tojson.hip -- toJSON of stored documents' Map, Array and Text roots (ygm_tojson_v1; ygm_tojson.hpp for the
+// semantics):
+//   k_tojson : k_json's batch with another walker -- a wave's documents staged in LDS, dpw per wave (staging, lane
+//              prologue and epilogue: ygm_docstage.hpp), workspaces from the snapshot's count and scan launches
+//              (ygm_k_launch_snap_plan), the JSON in the workspace's output region.
+// A kernel of its own, in a file of its own: k_json's two instantiations carry none of this walker and stay what they
+// were.  The JSON is not bounded by Caps::out (a control character is written as six bytes): the overflow route is
+// k_json's -- a document whose JSON does not fit records the needed length, claims that many bytes of the overflow
+// region after the workspaces with the launch's atomic cursor and puts itself on a list; the engine grows the buffer
+// and launches k_tojson again for the listed documents alone (again = 1: one per lane, parsed again, unstaged), each
+// into its claimed region.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "ygm_common.hpp"
+#include "ygm_docmeta.hpp"
+#include "ygm_tojson.hpp"
+#include "ygm_docstage.hpp"
+#include "ygm_launch.hpp"
+
+namespace ygm {
+
+using docstage::Lane;
+
+// again == 0: documents [0, n_docs), dpw per wave.  again == 1: the n_list documents of list[], the lanes of a wave
+// taking consecutive entries; document d writes out_len[d] bytes (the length its first run recorded) at out_off[d].
+// ovf_base: where the overflow region starts in ws (after the workspaces).
+__global__ __launch_bounds__(docstage::NT) void k_tojson(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
+                                                 const uint8_t* __restrict__ names, const uint64_t* __restrict__ name_off, uint32_t n_docs,
+                                                 uint32_t flags, uint32_t kind, const uint4* __restrict__ cnt, const uint64_t* __restrict__ ws_off,
+                                                 uint8_t* __restrict__ ws, uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_len,
+                                                 int32_t* __restrict__ status, DocMeta* __restrict__ meta, uint32_t dpw, uint64_t base,
+                                                 uint64_t ovf_base, uint32_t* __restrict__ list, uint32_t n_list, uint32_t again) {
+  __shared__ __attribute__((aligned(16))) uint8_t stg[docstage::STAGE + 16];
+  uint64_t mine = 0;
+  if (!again) {
+    const Lane L = docstage::lane_doc(stg, arena, doc_off, n_docs, dpw);
+    const uint32_t d = L.d;
+    if (L.on) {
+      const uint4 c = cnt[d];
+      const uint64_t a = doc_off[d], b = doc_off[d + 1], na = name_off[d], nb = name_off[d + 1];
+      uint32_t oo = 0, ol = 0;
+      snap::Caps k;
+      int st = docstage::lane_caps(nb >= na && nb - na < (1ull << 30), a, b, c, k);
+      if (st == ST_OK) st = tojson::tojson_doc(L.in, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, oo, ol);
+      if (st == json::ST_JSON_MORE) {   // ol: the length needed
+        const uint32_t i = atomicAdd(&meta->fb_count, 1u);
+        const unsigned long long at = atomicAdd(&meta->cursor, (unsigned long long)snap::al16(ol));
+        list[i] = d;   // (i < n_docs: a document lists itself once)
+        out_off[d] = ovf_base + at;
+        out_len[d] = ol;
+        status[d] = st;
+      } else mine = docstage::put(d, out_off, out_len, status, base + ws_off[d] + oo, st == ST_OK ? ol : 0u, st);
+    }
+  } else {
+    const uint32_t i = blockIdx.x * dpw + threadIdx.x;
+    if (threadIdx.x < dpw && i < n_list) {
+      const uint32_t d = list[i];
+      const uint4 c = cnt[d];
+      const uint64_t a = doc_off[d], na = name_off[d], nb = name_off[d + 1];
+      const uint32_t need = (uint32_t)out_len[d];
+      const snap::Caps k = snap::caps_of(c.x, c.y, c.z, c.w);
+      uint32_t ol = 0;
+      int st = tojson::tojson_run(arena + a, c.w, flags, ws + base + ws_off[d], k, names + na, (uint32_t)(nb - na), kind, ws + out_off[d], need, ol);
+      if (st == json::ST_JSON_MORE || (st == ST_OK && ol != need)) st = ST_NOMEM;   // (cannot happen: the same walk twice)
+      out_len[d] = st == ST_OK ? ol : 0u;   // (out_off[d]: the place the first run claimed)
+      status[d] = st;
+      mine = st == ST_OK ? ol : 0u;
+    }
+  }
+  docstage::add_payload(mine, &meta->payload);
+}
+
+}  // namespace ygm
+
+using namespace ygm;
+
+extern "C" {
+
+// as ygm_k_launch_json: over the workspaces ygm_k_launch_snap_plan sized (cnt, ws_off); again: the listed documents'
+// second run (n_list of them).  kind: YGM_TOJSON_MAP / _ARRAY / _TEXT (checked by the engine)
+int ygm_k_launch_tojson(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
+                        uint32_t flags, uint32_t kind, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
+                        uint64_t* out_len, int32_t* status, void* meta, uint64_t base, uint64_t ovf_base, uint32_t* list, uint32_t n_list,
+                        int again, hipStream_t s) {
+  const uint32_t n = again ? n_list : n_docs;
+  if (n == 0) return 0;
+  const uint32_t dpw = docstage::docs_per_wave(0);
+  const uint32_t g = (n + dpw - 1) / dpw;
+  hipLaunchKernelGGL(k_tojson, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off,
+                     ws, out_off, out_len, status, (DocMeta*)meta, dpw, base, ovf_base, list, n_list, again ? 1u : 0u);
+  return ygm_launch_rc(__func__);
+}
+
+}  // extern "C"

@@ -174,21 +174,52 @@ YDEV void js_quote(O& o, const uint8_t* s, uint32_t n) {
 // one canonical Any (validated) as JSON.stringify writes it; numbers other than varInt integers, undefined and
 // Uint8Array are refused (ST_NONCANON), a BigInt throws in JSON.stringify (ST_MALFORMED).  O: the writer (Out here,
 // snap::OutCap for ygm_json_v1)
-template <class O>
+// TOJSON (ygm_tojson_v1 alone; a compile-time option, so the other callers compile to what they were): JSON.stringify
+// of a value an application stored, not of one a conversion must reproduce -- an undefined object member is dropped
+// and an undefined array element (or the value itself) is null; a float32 / float64 tag that is not finite is null,
+// an integer of magnitude <= 2^53 its decimal digits (negative zero: 0), anything else ST_NONCANON (its shortest
+// round-trip decimal is not built); a Uint8Array (stringify writes an index-keyed object) is YGM_EUNSUPPORTED.
+constexpr int ST_ANY_UNSUP = 9;   // YGM_EUNSUPPORTED
+template <class O, bool TOJSON = false>
 YDEV_NI int any_json(Cur& c, O& o) {
   uint32_t rem[MAX_DEPTH + 1]; uint8_t obj[MAX_DEPTH + 1]; uint8_t first[MAX_DEPTH + 1];
   int d = 0; rem[0] = 1; obj[0] = 2; first[0] = 1;
   while (!c.err) {
     if (rem[d] == 0) { if (d == 0) break; o.b(obj[d] == 1 ? '}' : ']'); d--; continue; }
     rem[d]--;
-    if (obj[d] != 2) { if (!first[d]) o.b(','); first[d] = 0; }
-    if (obj[d] == 1) {
-      uint32_t kl; const uint32_t ks = c.buf(kl); if (c.err) break;
-      js_quote(o, c.p + ks, kl); o.b(':');
-      if (c.pos < c.end && c.p[c.pos] == 127) return ST_NONCANON;   // an undefined member: dropped by stringify
+    if constexpr (TOJSON) {
+      if (obj[d] == 1) {
+        uint32_t kl; const uint32_t ks = c.buf(kl); if (c.err) break;
+        if (c.pos < c.end && c.p[c.pos] == 127) { c.pos++; continue; }   // an undefined member: dropped by stringify
+        if (!first[d]) o.b(',');
+        first[d] = 0;
+        js_quote(o, c.p + ks, kl); o.b(':');
+      } else if (obj[d] == 0) { if (!first[d]) o.b(','); first[d] = 0; }
+    } else {
+      if (obj[d] != 2) { if (!first[d]) o.b(','); first[d] = 0; }
+      if (obj[d] == 1) {
+        uint32_t kl; const uint32_t ks = c.buf(kl); if (c.err) break;
+        js_quote(o, c.p + ks, kl); o.b(':');
+        if (c.pos < c.end && c.p[c.pos] == 127) return ST_NONCANON;   // an undefined member: dropped by stringify
+      }
     }
     const uint8_t tag = c.u8();
     if (c.err) break;
+    if constexpr (TOJSON) {
+      if (tag == 127) { o.b('n'); o.b('u'); o.b('l'); o.b('l'); continue; }
+      if (tag == 116) return ST_ANY_UNSUP;
+      if (tag == 124 || tag == 123) {
+        const uint32_t nb = tag == 124 ? 4u : 8u;
+        if (c.end - c.pos < nb) return ST_MALFORMED;
+        const double x = tag == 124 ? (double)be_f32(c.p + c.pos) : be_f64(c.p + c.pos);
+        c.pos += nb;
+        if (isnan(x) || isinf(x)) { o.b('n'); o.b('u'); o.b('l'); o.b('l'); continue; }
+        if (!(x == floor(x)) || fabs(x) > 9007199254740992.0) return ST_NONCANON;
+        if (x < 0) o.b('-');
+        uint8_t t[20]; const uint32_t k = dec_digits((uint64_t)fabs(x), t); o.copy(t, k);
+        continue;
+      }
+    }
     switch (tag) {
       case 126: o.b('n'); o.b('u'); o.b('l'); o.b('l'); break;
       case 120: o.b('t'); o.b('r'); o.b('u'); o.b('e'); break;

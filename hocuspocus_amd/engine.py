@@ -31,6 +31,7 @@ F_FORCE_SEQ = 2
 DOC_NO_GC = 1   # YGM_DOC_NO_GC: a document's option byte, the document is a Y.Doc({gc: false})
 TEXT_FLAT, TEXT_DEEP = 0, 1   # YGM_TEXT_FLAT / YGM_TEXT_DEEP: the modes of ygm_text_v1
 JSON_PROSEMIRROR = 0          # YGM_JSON_PROSEMIRROR: the one kind of ygm_json_v1
+TOJSON_MAP, TOJSON_ARRAY, TOJSON_TEXT = 0, 1, 2   # YGM_TOJSON_MAP / _ARRAY / _TEXT: the kinds of ygm_tojson_v1
 
 
 class YjsError(Exception):
@@ -109,6 +110,7 @@ SIGNATURES = {
     "ygm_text_v1": PAIR_U32,
     "ygm_json_v1": PAIR_U32,
     "ygm_json_fields_v1": PAIR_U32,
+    "ygm_tojson_v1": PAIR_U32,
     "ygm_sync_step2_v1": PAIR,
     "ygm_sync_step2_opts_v1": PAIR_OPT,
     "ygm_version_take_v1": UNARY,
@@ -135,6 +137,7 @@ SIGNATURES = {
     "ygm_text_v1_device": _dev_sig(PAIR_U32),
     "ygm_json_v1_device": _dev_sig(PAIR_U32),
     "ygm_json_fields_v1_device": _dev_sig(PAIR_U32),
+    "ygm_tojson_v1_device": _dev_sig(PAIR_U32),
     "ygm_sync_step2_v1_device": _dev_sig(PAIR),
     "ygm_sync_step2_opts_v1_device": _dev_sig(PAIR_OPT),
     "ygm_version_take_v1_device": _dev_sig(UNARY),
@@ -525,6 +528,22 @@ class Engine:
         field lists encoded as encode_fields does."""
         return self._dev("ygm_json_fields_v1_device", *_darena(d_states, states_bytes), _dptr(d_state_off), _dptr(d_fields),
                          _dptr(d_field_off), int(kind), n_docs, stream or None)
+
+    # ------------------------------------------------------------ toJSON of Map / Array / Text roots
+    def tojson_batch(self, states, names, kind):
+        """toJSON of stored documents' Map, Array or Text roots (ygm_tojson_v1): for doc = Y.applyUpdate(new Y.Doc(),
+        state), the UTF-8 of JSON.stringify(doc.getMap(name).toJSON()) (kind TOJSON_MAP), of getArray (TOJSON_ARRAY) or
+        of getText (TOJSON_TEXT) -> list of bytes, or a YjsError for a refused document (the caller keeps its yjs path
+        for it).  names: one root name per state (str or bytes).  A name the state has no root for gives b"{}", b"[]"
+        or b'""'."""
+        if len(states) != len(names):
+            raise ValueError("one root name per state")
+        return self._or_error(self._host("ygm_tojson_v1", *_packed(states), *_names(names), int(kind), len(states)))
+
+    def tojson_device(self, d_states, states_bytes, d_state_off, d_names, d_name_off, n_docs, kind, stream=0) -> "DeviceResult":
+        """Device-resident toJSON batch (ygm_tojson_v1_device): the states arena followed by TAIL_PAD readable bytes."""
+        return self._dev("ygm_tojson_v1_device", *_darena(d_states, states_bytes), _dptr(d_state_off), _dptr(d_names), _dptr(d_name_off),
+                         int(kind), n_docs, stream or None)
 
     # ------------------------------------------------------------ version history
     def take_version_batch(self, states):

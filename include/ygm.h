@@ -104,7 +104,8 @@ typedef struct {
                                           inside ygm_contains_v1 / ygm_sync_step2_v1 / the shared-state forms: there one
                                           per state and chunk, not one per ask; one per document of
                                           ygm_version_take_v1, two per document of ygm_version_restore_v1, one per state
-                                          and chunk plus one per ask of ygm_version_restore_shared_v1) */
+                                          and chunk plus one per ask of ygm_version_restore_shared_v1, one per document
+                                          of ygm_tojson_v1) */
 } ygm_stats_t;
 
 /* Opens the engine on HIP device `device` (one context per GPU; contexts are
@@ -230,7 +231,7 @@ int ygm_text_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, 
  * that does not fit its workspace is neither cut nor refused -- the documents concerned run a second time into a
  * region sized from their recorded lengths, at the cost of one more host wait (ygm_stats_t.host_syncs).
  * states / state_off / names / name_off, tail padding, packing and the other statuses as ygm_text_v1.  A kind other
- * than YGM_JSON_PROSEMIRROR is YGM_EINVAL for the call (room for toJSON of Map and Array roots).  No options form:
+ * than YGM_JSON_PROSEMIRROR is YGM_EINVAL for the call (toJSON of Map and Array roots: ygm_tojson_v1).  No options form:
  * the JSON depends neither on YGM_F_COMPAT_135 nor on garbage collection.
  * (Replaces packages/transformer/src/Prosemirror.ts:26: transformer.fromYdoc(document, fieldName) with one field
  * name, what a REST read of one field sends.  The body of a change webhook is ygm_json_fields_v1 below.) */
@@ -271,6 +272,60 @@ int ygm_json_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, 
  * transformer.fromYdoc(data.document) -- and packages/transformer/src/Prosemirror.ts:29-39.) */
 int ygm_json_fields_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *fields,
                        const uint64_t *field_off, uint32_t kind, uint32_t n_docs, ygm_result *out);
+/* ---- toJSON of stored Map, Array and Text roots -------------------------------
+ * What a stored document holds when it is not a rich-text document: boards, forms, whiteboards, notebook models keep
+ * their state in Y.Map / Y.Array / Y.Text roots.  For doc = Y.applyUpdate(new Y.Doc(), state) and a root name (UTF-8
+ * bytes, compared bytewise, as in ygm_text_v1), document d's output is the UTF-8 of
+ *   YGM_TOJSON_MAP    JSON.stringify(doc.getMap(name).toJSON())
+ *   YGM_TOJSON_ARRAY  JSON.stringify(doc.getArray(name).toJSON())
+ *   YGM_TOJSON_TEXT   JSON.stringify(doc.getText(name).toJSON())
+ * with yjs 13.5.16's toJSON.  The asked kind decides how the root is read (an update does not say what a root is); a
+ * nested type is read by its typeRef (0 Array, 1 Map, 2 Text).
+ *   Map    the type's map entries whose current item is not deleted; the value is the last element of the item's
+ *          content.  Keys follow JavaScript's own-property order: canonical array-index keys ascending, then the
+ *          order in which the keys were first set (a key set again keeps its place).  A value that is undefined drops
+ *          its key.  An empty or absent root gives {}.  The root's list items are ignored.
+ *   Array  the list's live countable items, every content element in turn; an undefined element is null; map entries
+ *          on the same root are ignored.  An absent root gives [].
+ *   Text   toString() -- YGM_TEXT_FLAT's walk: live countable ContentStrings only, U+FFFD on both sides of a cut
+ *          surrogate pair -- as one JSON string.  An absent root gives "".
+ * Contents: a ContentType recurses by its typeRef; every element of a ContentAny is written as below; every element
+ * of a ContentJSON (canonical JSON text in V1) is copied, the word undefined counting as undefined, with the float
+ * refusal ygm_json_v1 applies to embed values.  Any values are written as the V2 -> V1 conversion writes them, with two
+ * additions: inside an Any an undefined object member is dropped and an undefined array element is null; a float32
+ * or float64 that is not finite is null, one that is an integer of magnitude at most 2^53 is its decimal digits
+ * (Date.now() timestamps and 4294967296 travel this way; negative zero is 0).  Strings and keys are escaped as in
+ * ygm_json_v1.
+ * Refusals affect only their own document (length 0); the state's own parse or integration status comes first, as in
+ * ygm_json_v1; in the asked root's subtree:
+ *   a nested XmlElement / XmlFragment / XmlHook / XmlText (typeRef 3-6: their toJSON is an XML string, not built
+ *   here) or an unknown typeRef                                                           YGM_EUNSUPPORTED
+ *   a ContentBinary, or a Uint8Array anywhere in an Any (JSON.stringify writes an index-keyed object)
+ *                                                                                         YGM_EUNSUPPORTED
+ *   a ContentDoc                                                                          YGM_EUNSUPPORTED
+ *   a live ContentString or ContentEmbed in an Array's list                               YGM_EUNSUPPORTED
+ *   a live Map entry that is not ContentAny / ContentJSON / ContentType                   YGM_EUNSUPPORTED
+ *   a Y.Map key __proto__ with a live entry (the assignment sets the prototype and the key vanishes, as in
+ *   ygm_json_fields_v1)                                                                   YGM_EUNSUPPORTED
+ *   a finite non-integer number, or an integer above 2^53                                 YGM_ENONCANON
+ *   a BigInt (JSON.stringify throws)                                                      YGM_EMALFORMED
+ *   nesting past the walk stack                                                           YGM_ENOMEM, as ygm_json_v1
+ *   a JSON of 2^31 bytes or more                                                          YGM_ENOMEM
+ * A state with pending structs / a pending delete set is read through its integrated part with YGM_OK.  A JSON has no
+ * bound in its state's size (a control character is written as six bytes): the second run of ygm_json_v1 covers it
+ * in the same way, at the cost of one more host wait (ygm_stats_t.host_syncs).  ygm_stats_t.docs_snapshot grows by
+ * n_docs.  states / state_off / names / name_off, tail padding, packing and the other statuses as ygm_json_v1.  A kind
+ * other than the three is YGM_EINVAL for the call.  No options form: neither YGM_F_COMPAT_135 nor garbage collection
+ * changes the result.
+ * Out of scope: the shortest-round-trip decimal of non-integer doubles; XML strings of nested Xml types; toDelta; a
+ * multi-root object form.
+ * (Replaces no single reference interface: the batched form of a custom webhook transformer's `fromYdoc`,
+ * extension-webhook/src/index.ts:27-31,119.) */
+#define YGM_TOJSON_MAP 0u   /* JSON.stringify(doc.getMap(name).toJSON())   */
+#define YGM_TOJSON_ARRAY 1u /* JSON.stringify(doc.getArray(name).toJSON()) */
+#define YGM_TOJSON_TEXT 2u  /* JSON.stringify(doc.getText(name).toJSON())  */
+int ygm_tojson_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *names,
+                  const uint64_t *name_off, uint32_t kind, uint32_t n_docs, ygm_result *out);
 /* SyncStep2 payload of a stored document: Y.encodeStateAsUpdate(doc, sv) for doc = Y.applyUpdate(new Y.Doc(), state)
  * -- what the reference sends in reply to a SyncStep1 (packages/server/src/MessageReceiver.ts:137-138) for a
  * document loaded from stored bytes (extension-database Database.ts:44-50).  Computed as the doc-normalized
@@ -483,6 +538,13 @@ int ygm_json_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_by
 int ygm_json_fields_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                               const uint8_t *d_fields, const uint64_t *d_field_off, uint32_t kind, uint32_t n_docs,
                               void *stream, ygm_device_result *out);
+/* ygm_tojson_v1, device-resident: tail padding, the unpacked result (a document's JSON lies in its workspace's output
+ * region, or in the overflow region after the workspaces when it ran a second time) and payload_bytes as
+ * ygm_json_v1_device.
+ * (Replaces no single reference interface, as ygm_tojson_v1.) */
+int ygm_tojson_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
+                         const uint8_t *d_names, const uint64_t *d_name_off, uint32_t kind, uint32_t n_docs, void *stream,
+                         ygm_device_result *out);
 int ygm_sync_step2_v1_device(ygm_ctx *ctx, const uint8_t *d_states, uint64_t states_bytes, const uint64_t *d_state_off,
                              const uint8_t *d_sv_arena, const uint64_t *d_sv_off, uint32_t n_docs, void *stream,
                              ygm_device_result *out);

@@ -50,7 +50,7 @@ struct Job {
   uint32_t *docs;                   /* merge: the updates' document ids; shared: the asks' state ids */
   uint32_t n_upd, n_docs;           /* n_docs: documents / states; n_upd: updates (merge) or asks (shared) */
   uint8_t *sv; uint64_t *sv_off;    /* the second arena (state vectors, updates, versions, names, field lists) */
-  uint32_t mode;                    /* the required u32: ygm_text_v1's mode, ygm_json_v1's kind */
+  uint32_t mode;                    /* the required u32: ygm_text_v1's mode, ygm_json_v1's / ygm_tojson_v1's kind */
   uint8_t *opt;   /* option bytes (YGM_DOC_NO_GC), one per document / state or per ask; NULL: none */
   int rc;
   /* copied results */
@@ -303,6 +303,7 @@ static int run_restore_version(Job *j, ygm_result *r) { return ygm_version_resto
 static int run_text(Job *j, ygm_result *r) { return ygm_text_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->mode, j->n_docs, r); }
 static int run_json(Job *j, ygm_result *r) { return ygm_json_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->mode, j->n_docs, r); }
 static int run_json_fields(Job *j, ygm_result *r) { return ygm_json_fields_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->mode, j->n_docs, r); }
+static int run_tojson(Job *j, ygm_result *r) { return ygm_tojson_v1(j->h->ctx, j->arena, j->off, j->sv, j->sv_off, j->mode, j->n_docs, r); }
 static int run_diff_shared(Job *j, ygm_result *r) { return ygm_diff_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, r); }
 static int run_step2_shared(Job *j, ygm_result *r) { return ygm_sync_step2_shared_opts_v1(j->h->ctx, j->arena, j->off, j->opt, j->n_docs, j->sv, j->sv_off, j->docs, j->n_upd, r); }
 static int run_restore_version_shared(Job *j, ygm_result *r) { return ygm_version_restore_shared_v1(j->h->ctx, j->arena, j->off, j->n_docs, j->sv, j->sv_off, j->docs, j->opt, j->n_upd, r); }
@@ -345,6 +346,9 @@ static const Op OPS[] = {
   /* every asked field of stored documents as one JSON object per (state, field list): transformer.fromYdoc(doc) /
      fromYdoc(doc, [names]) -- a list is lib0 varStrings back to back, none: every root (ygm_json_fields_v1) */
   { "jsonFields", SHAPE_PAIR, TAIL_U32, run_json_fields },
+  /* toJSON of stored documents' Map / Array / Text roots per (state, root name): doc.getMap(name).toJSON() and its
+     kin, stringified; the u32 is the kind, YGM_TOJSON_MAP / _ARRAY / _TEXT (ygm_tojson_v1) */
+  { "toJson", SHAPE_PAIR, TAIL_U32, run_tojson },
 };
 #define N_OPS (sizeof OPS / sizeof OPS[0])
 

@@ -58,6 +58,10 @@ export declare class GpuEngine {
    *  doc = Y.applyUpdate(new Y.Doc(), states[i]) -- a change webhook's `document`; fields[i]: null / [] for every key of
    *  doc.share, or the names; one load of a state serves all its fields; a refusing field or one named __proto__ gives a YgmError */
   jsonFieldsMany (states: Uint8Array[], fields: (FieldList)[]): Promise<(string | YgmError)[]>
+  /** toJSON of stored Map / Array / Text roots: JSON.stringify(doc.getMap(names[i]).toJSON()) (kind TOJSON_MAP), getArray
+   *  (TOJSON_ARRAY) or getText (TOJSON_TEXT) of doc = Y.applyUpdate(new Y.Doc(), states[i]); one kind per batch; a document
+   *  outside the envelope (a nested Xml type, binary content, a non-integer number) gives a YgmError in its place */
+  toJsonMany (states: Uint8Array[], names: (string | Uint8Array)[], kind: 0 | 1 | 2): Promise<(string | YgmError)[]>
   /** Y.encodeStateAsUpdate(Y.createDocFromSnapshot(doc, Y.decodeSnapshot(version), new Y.Doc(opts))) of doc =
    *  Y.applyUpdate(new Y.Doc({ gc: false }), state); several versions of one document: restoreVersionShared */
   restoreVersion (state: Uint8Array, version: Uint8Array, opts?: DocOptions): Promise<Uint8Array>
@@ -100,6 +104,8 @@ export declare class GpuEnginePool {
   jsonMany (docNames: string[], states: Uint8Array[], names: (string | Uint8Array)[]): Promise<(string | YgmError)[]>
   /** docNames[i] routes states[i]; fields[i] is its field list */
   jsonFieldsMany (docNames: string[], states: Uint8Array[], fields: (FieldList)[]): Promise<(string | YgmError)[]>
+  /** docNames[i] routes states[i]; names[i] is its root name; kind as GpuEngine.toJsonMany's */
+  toJsonMany (docNames: string[], states: Uint8Array[], names: (string | Uint8Array)[], kind: 0 | 1 | 2): Promise<(string | YgmError)[]>
   restoreVersionMany (names: string[], states: Uint8Array[], versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
   /** names[i] naming states[i], routed as step2Shared; opts: one option per ask */
   restoreVersionShared (names: string[], states: Uint8Array[], askState: ArrayLike<number>, versions: Uint8Array[], opts?: DocOptionList): Promise<(Uint8Array | YgmError)[]>
@@ -187,7 +193,13 @@ export declare class GpuMerge implements Extension {
   jsonOf (names: string[], opts?: { field?: string | FieldList, parse?: boolean }): Promise<Map<string, string | object>>
   /** restoreVersions followed by one JSON batch over the fulfilled results, settled per entry; field as jsonOf's */
   versionJson (entries: { documentName: string, version: Uint8Array, gc?: boolean }[], opts?: { field?: string | FieldList, parse?: boolean }): Promise<({ status: 'fulfilled', value: string | object } | { status: 'rejected', reason: Error })[]>
-  /** documents whose JSON the engine refused in jsonOf / versionJson: the caller keeps its yjs path (transformer.fromYdoc) for them */
+  /** what each loaded document's Map / Array / Text root is, in one GPU batch: JSON.stringify(document.getMap(root).toJSON())
+   *  (type 'map', the default), getArray ('array') or getText ('text'), or the parsed value with parse: true; unloaded
+   *  documents are left out, refused ones left out and named in `unserialized`. */
+  sharedJsonOf (names: string[], opts?: { root?: string, type?: 'map' | 'array' | 'text', parse?: boolean }): Promise<Map<string, string | object>>
+  /** restoreVersions followed by one toJSON batch over the fulfilled results, settled per entry; root, type as sharedJsonOf's */
+  versionSharedJson (entries: { documentName: string, version: Uint8Array, gc?: boolean }[], opts?: { root?: string, type?: 'map' | 'array' | 'text', parse?: boolean }): Promise<({ status: 'fulfilled', value: string | object } | { status: 'rejected', reason: Error })[]>
+  /** documents whose JSON the engine refused in jsonOf / versionJson / sharedJsonOf / versionSharedJson: the caller keeps its yjs path (transformer.fromYdoc) for them */
   unserialized: { documentName: string, code: string }[]
   /** batched SyncStep1 responder over the captured state (snapshot + updates since) */
   syncResponder (): SyncResponder

@@ -120,6 +120,8 @@ const DOC_NO_GC = 1
 const TEXT_FLAT = 0; const TEXT_DEEP = 1
 /** YGM_JSON_PROSEMIRROR: the one kind of ygm_json_v1 */
 const JSON_PROSEMIRROR = 0
+/** YGM_TOJSON_MAP / YGM_TOJSON_ARRAY / YGM_TOJSON_TEXT: the kinds of ygm_tojson_v1 */
+const TOJSON_MAP = 0; const TOJSON_ARRAY = 1; const TOJSON_TEXT = 2
 /**
  * A document's field list for ygm_json_fields_v1: null, undefined or [] give no bytes (every key of doc.share); names
  * (strings or UTF-8 bytes) give their lib0 varStrings back to back -- a varuint byte length, then the bytes.
@@ -166,6 +168,7 @@ const OPS = {
   textDeep: { native: 'text', pack: packPair, extra: () => TEXT_DEEP },
   json: { native: 'json', pack: packPair, extra: () => JSON_PROSEMIRROR },
   jsonFields: { native: 'jsonFields', pack: packPair, extra: () => JSON_PROSEMIRROR },   // a job is [state, encoded field list]
+  toJson: { native: 'toJson', pack: packPair, extra: jobs => jobs.length ? jobs[0][2] : TOJSON_MAP },   // a job is [state, root name bytes, the batch's kind]
   // a job is an update, or { update, opt } for one with an option byte: both kinds share a window
   snapshot: { native: 'snapshotMany', pack: jobs => arenas(jobs.map(j => j instanceof Uint8Array ? j : j.update)),
     extra: jobs => optBytes(jobs.map(j => j instanceof Uint8Array ? 0 : j.opt), jobs.length) },
@@ -349,6 +352,18 @@ class GpuEngine {
     return unpackUtf8(await this._run('jsonFields', states.map((s, i) => [s, encodeFields(fields[i])])))
   }
 
+  /**
+   * toJSON of stored documents' Map, Array or Text roots, as an explicit batch: for doc = Y.applyUpdate(new Y.Doc(),
+   * states[i]) the string JSON.stringify(doc.getMap(names[i]).toJSON()) (kind TOJSON_MAP), of getArray (TOJSON_ARRAY)
+   * or of getText (TOJSON_TEXT) -- what a custom webhook transformer's fromYdoc returns, stringified (ygm_tojson_v1).
+   * One kind per batch.  A name the state has no root for gives '{}', '[]' or '""'; a document outside the envelope (a
+   * nested Xml type, binary content, a non-integer number, ...) gives a YgmError in its place.
+   */
+  async toJsonMany (states, names, kind) {
+    if (kind !== TOJSON_MAP && kind !== TOJSON_ARRAY && kind !== TOJSON_TEXT) throw new YgmError(8, loadAddon().strerror(8))
+    return unpackUtf8(await this._run('toJson', rootJobs(states, names).map(j => [j[0], j[1], kind])))
+  }
+
   /** update format V2 (yjs providers other than Hocuspocus's V1 path): Y.mergeUpdatesV2 / Y.diffUpdateV2 /
    *  Y.encodeStateVectorFromUpdateV2 / yjs 13.6 Y.convertUpdateFormatV1ToV2 / V2ToV1, as explicit batches */
   async mergeManyV2 (docs) { const r = await this._run('mergeV2', docs); return unpack(r) }
@@ -475,6 +490,8 @@ class GpuEnginePool {
   jsonMany (docNames, states, names) { return this._many(docNames, [states, names], (e, a, b) => e.jsonMany(a, b)) }
   /** jsonFieldsMany with one document name per state (the shard), beside its field list */
   jsonFieldsMany (docNames, states, fields) { return this._many(docNames, [states, fields], (e, a, b) => e.jsonFieldsMany(a, b)) }
+  /** toJsonMany with one document name per state (the shard), beside its root name */
+  toJsonMany (docNames, states, names, kind) { return this._many(docNames, [states, names], (e, a, b) => e.toJsonMany(a, b, kind)) }
   stats () { return this.engines.map(e => e.stats()) }
   /**
    * Node-wide totals (the reference's server-wide counters, Hocuspocus.ts:138-160): every numeric field of the
@@ -489,4 +506,4 @@ class GpuEnginePool {
   close () { this.engines.forEach(e => e.close()) }
 }
 
-module.exports = { packJobs, GpuEngine, GpuEnginePool, fnv1a64, YgmError, STATUS, loadAddon, DOC_NO_GC, TEXT_FLAT, TEXT_DEEP, optBytes, encodeFields }
+module.exports = { packJobs, GpuEngine, GpuEnginePool, fnv1a64, YgmError, STATUS, loadAddon, DOC_NO_GC, TEXT_FLAT, TEXT_DEEP, TOJSON_MAP, TOJSON_ARRAY, TOJSON_TEXT, optBytes, encodeFields }

@@ -96,7 +96,7 @@ class GpuMerge {
     this.refused = []
     /** normalize: stores that kept the merged bytes (snapshot outside the kernel's envelope) */
     this.unnormalized = []
-    /** jsonOf / versionJson: documents whose JSON the engine refused (outside ygm_json_v1's envelope: the caller keeps
+    /** jsonOf / versionJson / sharedJsonOf / versionSharedJson: documents whose JSON the engine refused (outside ygm_json_v1's envelope: the caller keeps
      *  its yjs path, transformer.fromYdoc, for them) */
     this.unserialized = []
   }
@@ -302,6 +302,55 @@ class GpuMerge {
     const ok = out.map((r, i) => r.status === 'fulfilled' ? i : -1).filter(i => i >= 0)
     if (!ok.length) return out
     const res = await this._jsonMany(ok.map(i => entries[i].documentName), ok.map(i => out[i].value), field)
+    ok.forEach((i, k) => {
+      if (res[k] instanceof Error) {
+        this.unserialized.push({ documentName: entries[i].documentName, code: res[k].code || String(res[k]) })
+        out[i] = { status: 'rejected', reason: res[k] }
+      } else out[i] = { status: 'fulfilled', value: parse ? JSON.parse(res[k]) : res[k] }
+    })
+    return out
+  }
+
+  /**
+   * toJSON of shared types that are not rich text (INTEGRATION.md "Map / Array / Text documents").
+   * sharedJsonOf(names, { root, type, parse }): what each loaded document's root is --
+   * JSON.stringify(document.getMap(root).toJSON()) for type 'map' (the default), getArray for 'array', getText for 'text':
+   * the fromYdoc of a custom webhook transformer -- in one GPU batch over the captured states -> Map name -> JSON
+   * string, or the parsed value with parse: true.  A document that is not loaded is left out; one the engine refuses
+   * (a nested Xml type, binary content, a non-integer number, ...) is left out and named in `unserialized`: the caller
+   * keeps its yjs path for it.
+   */
+  async sharedJsonOf (names, { root = 'default', type = 'map', parse = false } = {}) {
+    const states = await this._statesOf(names)
+    const idx = names.map((_, i) => i).filter(i => states[i] && !(states[i] instanceof Error))
+    const res = !idx.length ? [] : await this._toJsonMany(idx.map(i => names[i]), idx.map(i => states[i]), root, type)
+    const out = new Map()
+    idx.forEach((i, k) => {
+      if (res[k] instanceof Error) this.unserialized.push({ documentName: names[i], code: res[k].code || String(res[k]) })
+      else out.set(names[i], parse ? JSON.parse(res[k]) : res[k])
+    })
+    return out
+  }
+
+  // one toJSON batch over states (ygm_tojson_v1); docNames shard the batch over a pool's engines
+  _toJsonMany (docNames, states, root, type) {
+    const kind = ['map', 'array', 'text'].indexOf(type)
+    if (kind < 0 || typeof root !== 'string') throw new TypeError("root: a root name; type: 'map', 'array' or 'text'")
+    const eng = this._engine()
+    const roots = states.map(() => root)
+    return typeof eng.shardOf === 'function' ? eng.toJsonMany(docNames, states, roots, kind) : eng.toJsonMany(states, roots, kind)
+  }
+
+  /**
+   * versionSharedJson(entries, { root, type, parse }): restoreVersions(entries) followed by one toJSON batch over the
+   * fulfilled results, settled per entry as versionJson is (a refused version is rejected with the engine's error and
+   * named in `unserialized`).  root, type: as sharedJsonOf's.
+   */
+  async versionSharedJson (entries, { root = 'default', type = 'map', parse = false } = {}) {
+    const out = await this.restoreVersions(entries)
+    const ok = out.map((r, i) => r.status === 'fulfilled' ? i : -1).filter(i => i >= 0)
+    if (!ok.length) return out
+    const res = await this._toJsonMany(ok.map(i => entries[i].documentName), ok.map(i => out[i].value), root, type)
     ok.forEach((i, k) => {
       if (res[k] instanceof Error) {
         this.unserialized.push({ documentName: entries[i].documentName, code: res[k].code || String(res[k]) })

@@ -1,0 +1,66 @@
+// Development harness (tooling, never shipped): the host twin of ygm_tojson_v1 (ygm_tojson.hpp: the sequential code of
+// k_tojson) over a file of asks, so the JSON can be checked against the yjs bundle without a GPU.  Input and output
+// as jsondev.cpp's plus the kind: u32 count, then per ask (u32 len, state bytes), (u32 len, root name bytes), u32 kind.
+// Output per ask: i32 status, u32 reran, u32 len, bytes.  The overflow protocol is the engine's: a first run into an
+// output region of Caps::out bytes (an allocation of its own, of exactly that size), or of `cap` bytes when a cap is
+// forced; a document whose JSON does not fit (ST_JSON_MORE) runs again over a fresh workspace into a region of exactly
+// the recorded length (reran = 1), and must then give that length.
+//     tojsondev in.bin out.bin [flags [cap]]   (flags: 1 = 13.5 compat; the JSON does not depend on it.  cap > 0: the
+//                                               first run's region is min(cap, Caps::out) bytes)
+// A sanitizer build of this program (g++ -fsanitize=address,undefined) over the whole fixture is where the walk's
+// bounds are checked.
+#define YGM_HOST_BUILD 1
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <algorithm>
+#include <vector>
+#include "../../hocuspocus_amd/csrc/ygm_tojson.hpp"
+
+static bool rd(FILE* f, std::vector<uint8_t>& v, uint32_t pad) {
+  uint32_t len;
+  if (fread(&len, 4, 1, f) != 1) return false;
+  v.assign((size_t)len + pad, 0);
+  if (len && fread(v.data(), 1, len, f) != len) return false;
+  return true;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 3) { fprintf(stderr, "usage: tojsondev in.bin out.bin [flags [cap]]\n"); return 2; }
+  const uint32_t flags = argc > 3 ? (uint32_t)atoi(argv[3]) : 0u;
+  const uint32_t cap = argc > 4 ? (uint32_t)atoi(argv[4]) : 0u;
+  FILE* f = fopen(argv[1], "rb"); FILE* g = fopen(argv[2], "wb");
+  if (!f || !g) return 1;
+  uint32_t n = 0; if (fread(&n, 4, 1, f) != 1) return 1;
+  std::vector<uint8_t> st, name;
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t kind = 0;
+    if (!rd(f, st, 64) || !rd(f, name, 0) || fread(&kind, 4, 1, f) != 1) return 1;
+    const uint32_t len = (uint32_t)st.size() - 64u, nl = (uint32_t)name.size();
+    int32_t gs = 1; uint32_t ol = 0, reran = 0;   // (an empty update: ST_MALFORMED, as k_tojson)
+    std::vector<uint8_t> res;
+    if (len) {
+      uint32_t S, Dn, C; ygm::snap::count_doc(st.data(), len, flags, S, Dn, C);
+      const ygm::snap::Caps k = ygm::snap::caps_of(S, Dn, C, len);
+      const uint32_t oc = cap && cap < k.out ? cap : k.out;
+      // (fresh allocations per ask, each of its exact size: no capacity left over from a larger document)
+      std::vector<uint8_t> ws((size_t)ygm::snap::ws_core_bytes(k), 0), first((size_t)oc, 0), big;
+      gs = ygm::tojson::tojson_run(st.data(), len, flags, ws.data(), k, name.data(), nl, kind, first.data(), oc, ol);
+      if (gs == 0) res.assign(first.begin(), first.begin() + ol);
+      if (gs == ygm::json::ST_JSON_MORE) {
+        const uint32_t need = ol;
+        reran = 1;
+        big.assign((size_t)need, 0);   // (exactly the recorded length: a sanitizer sees one byte more)
+        std::fill(ws.begin(), ws.end(), 0);
+        gs = ygm::tojson::tojson_run(st.data(), len, flags, ws.data(), k, name.data(), nl, kind, big.data(), need, ol);
+        if (gs != 0 || ol != need) { fprintf(stderr, "ask %u: the rerun gave status %d, %u bytes for %u recorded\n", i, gs, ol, need); return 1; }
+        res = big;
+      }
+    }
+    const uint32_t gl = gs == 0 ? ol : 0u;
+    fwrite(&gs, 4, 1, g); fwrite(&reran, 4, 1, g); fwrite(&gl, 4, 1, g);
+    if (gl) fwrite(res.data(), 1, gl, g);
+  }
+  fclose(f); fclose(g);
+  return 0;
+}
