@@ -99,6 +99,10 @@ struct ygm_ctx {
   DevBuf arena, offs, docs, sv_arena, sv_offs, opt;   // (opt: the chunk's per-document option bytes, *_opts_v1)
   // device outputs + state
   DevBuf out, out_off, out_len, status, lb, meta, fb_list, defer_list, defer2_list, defer_w_list, route_list;
+  // where a call's results go: the output buffers as prep_outputs left them, the slot region's and the arena's size
+  ygm_results results(uint64_t slot_total, uint64_t out_cap) const {
+    return {out.as<uint8_t>(), out_off.as<uint64_t>(), out_len.as<uint64_t>(), status.as<int32_t>(), slot_total, out_cap};
+  }
   Meta* h_meta = nullptr;  // pinned read-back of the per-launch counters
   int mslot = 0;           // counter slot of the next merge launch
   void* meta_slot(int i) const { return (uint8_t*)meta.p + (size_t)i * sizeof(Meta); }
@@ -132,12 +136,12 @@ struct ygm_ctx {
   struct Pending {
     bool live = false;
     hipStream_t s = nullptr;
-    const uint8_t* arena = nullptr; const uint64_t* upd_off = nullptr; const uint32_t* doc_upd = nullptr;
-    uint64_t arena_bytes = 0, slot_total = 0, out_cap = 0;
+    ygm_merge_in in{};   // what every tier reads (in.meta: the counter slot of the launch)
+    ygm_results res{};   // where every tier writes
+    uint64_t arena_bytes = 0;
     uint32_t n_upd = 0, n_docs = 0;
-    void* meta = nullptr;   // counter slot of the launch
     bool wide_route = false;   // the launch was the wide lean kernel over the whole batch
-    // the compact input form (ygm_merge_v1_device_lens): upd_off is the context's table, built for deferred documents
+    // the compact input form (ygm_merge_v1_device_lens): in.upd_off is the context's table, built for deferred documents
     const uint64_t* doc_off = nullptr; const uint16_t* upd_len = nullptr;
   } pend;
   DevBuf lens_off;   // update-offset table of a compact-form batch (entries of the documents the lean kernel defers)
@@ -265,15 +269,12 @@ static uint64_t read_u64(ygm_ctx* c, hipStream_t s, const uint64_t* d_p, int& e)
 }
 
 static void fill_dev_result(ygm_ctx* c, uint64_t data_bytes, ygm_device_result* out) {
-  out->data = c->out.as<uint8_t>();
-  out->off = c->out_off.as<uint64_t>();
-  out->len = c->out_len.as<uint64_t>();
-  out->status = c->status.as<int32_t>();
+  const ygm_results r = c->results(0, 0);
+  out->data = r.out; out->off = r.out_off; out->len = r.out_len; out->status = r.status;
   out->data_bytes = data_bytes;
   out->payload_bytes = data_bytes;
 }
 
-// offsets of the DocMeta counters the tier kernels read as device-side counts
 static int merge_async(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_upd_off, const uint32_t* d_doc_upd,
                        uint32_t n_upd, uint32_t n_docs, void* stream, const uint64_t* d_doc_off, const uint16_t* d_upd_len) {
   if (!c) return YGM_EINVAL;
@@ -300,24 +301,20 @@ static int merge_async(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes,
   // last -- per-launch event pairs between back-to-back launches cost ~8 us of stream time each.
   if (c->lean_span_n == 0) HIPCHK(hipEventRecord(c->e0, s));
   c->lean_span_n++;
-  void* meta = c->meta_slot(c->mslot);
+  const ygm_merge_in in{d_arena, d_upd_off, d_doc_upd, c->flags, c->meta_slot(c->mslot)};
+  const ygm_results res = c->results(slot_total, out_cap);
   void* meta_next = c->meta_slot(1 - c->mslot);   // zeroed by this launch for the next one
   if (wide_route) {
-    if (ygm_k_launch_merge_lean_wide(d_arena, d_upd_off, d_doc_upd, n_docs, nullptr, n_docs, c->flags, c->out.as<uint8_t>(),
-                                     c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), meta, meta_next,
-                                     c->defer_w_list.as<uint32_t>(), out_cap, d_upd_len, s))
+    if (ygm_k_launch_merge_lean_wide(&in, &res, n_docs, nullptr, n_docs, meta_next, c->defer_w_list.as<uint32_t>(), d_upd_len, s))
       return YGM_EDEVICE;
-  } else if (ygm_k_launch_merge_lean(d_arena, d_upd_off, d_doc_upd, n_docs, c->flags | c->lean_flags, c->out.as<uint8_t>(), c->out_off.as<uint64_t>(),
-                                     c->out_len.as<uint64_t>(), c->status.as<int32_t>(), meta, meta_next, c->defer_list.as<uint32_t>(), out_cap, s,
-                                     d_doc_off, d_upd_len))
+  } else if (ygm_k_launch_merge_lean(&in, &res, n_docs, c->lean_flags, meta_next, c->defer_list.as<uint32_t>(), d_doc_off, d_upd_len, s))
     return YGM_EDEVICE;
-  c->pend.wide_route = wide_route;
+  ygm_ctx::Pending& P = c->pend;
+  P.wide_route = wide_route;
   if (n_docs) c->mslot = 1 - c->mslot;   // (an empty batch launches nothing: the slot stays current)
-  c->pend.live = true; c->pend.s = s;
-  c->pend.arena = d_arena; c->pend.upd_off = d_upd_off; c->pend.doc_upd = d_doc_upd;
-  c->pend.arena_bytes = arena_bytes; c->pend.slot_total = slot_total; c->pend.out_cap = out_cap;
-  c->pend.n_upd = n_upd; c->pend.n_docs = n_docs; c->pend.meta = meta;
-  c->pend.doc_off = wide_route ? nullptr : d_doc_off; c->pend.upd_len = d_upd_len;   // (wide route: the table is whole)
+  P.live = true; P.s = s; P.in = in; P.res = res;
+  P.arena_bytes = arena_bytes; P.n_upd = n_upd; P.n_docs = n_docs;
+  P.doc_off = wide_route ? nullptr : d_doc_off; P.upd_len = d_upd_len;   // (wide route: the table is whole)
   return YGM_OK;
 }
 int ygm_merge_v1_device_async(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* d_upd_off,
@@ -330,147 +327,144 @@ int ygm_merge_v1_device_lens_async(ygm_ctx* c, const uint8_t* d_arena, uint64_t 
   return merge_async(c, d_arena, arena_bytes, nullptr, d_doc_upd, n_upd, n_docs, stream, d_doc_off, d_upd_len);
 }
 
-int ygm_merge_v1_device_finish(ygm_ctx* c, ygm_device_result* out) {
-  if (!c || !out || !c->pend.live) return YGM_EINVAL;
-  ygm_ctx::Pending& P = c->pend;
-  P.live = false;
-  hipStream_t s = P.s;
-  (void)hipSetDevice(c->device);
+// ---- ygm_merge_v1_device_finish: the tiers after the lean launch, a step each.  A step enqueues its kernels on the
+// call's stream between the events e0 and e1, reads the counters back (one host wait) and leaves them to the next.
+struct MergeRun {
+  ygm_ctx* c;
+  hipStream_t s;
+  const ygm_ctx::Pending& P;
+  Meta m{};             // the call's counters as last read
+  uint32_t n_gen = 0;   // documents the lean kernels left to the general tiers
+  uint32_t n_seq = 0;   // documents the large-document tier left to the sequential replay
+  unsigned long long cnt[5] = {0, 0, 0, 0, 0};   // tier 4: the scan's counters ([4], the slow queue's entries: the YGM_TIER_COUNTS line's only)
+  int reread() {        // the counters after a step; a kernel's fault ends the call
+    const int e = read_meta(c, s, m, P.in.meta);
+    return e ? e : m.fault ? YGM_EDEVICE : YGM_OK;
+  }
+  void add_span() {     // e0 .. e1 into the kernel time (after the wait that follows e1)
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
+  }
+  int lean_span(), general(), large(), seq();
+  void report(ygm_device_result* out);
+};
+// the lean span (every lean launch since the last finish, e0 .. e1) and the counters its last launch left
+int MergeRun::lean_span() {
   HIPCHK(hipEventRecord(c->e1, s));
-  Meta m;
-  int e = read_meta(c, s, m, P.meta);
-  if (e) return e;
-  if (m.fault) return YGM_EDEVICE;
-  float ms0 = 0;
-  if (c->lean_span_n && hipEventElapsedTime(&ms0, c->e0, c->e1) == hipSuccess) { c->stats.kernel_ms += ms0; c->stats.lean_ms += ms0; }
+  if (const int e = reread()) return e;
+  float ms = 0;
+  if (c->lean_span_n && hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) { c->stats.kernel_ms += ms; c->stats.lean_ms += ms; }
   c->stats.lean_launches += c->lean_span_n;
   c->lean_span_n = 0;
-  uint32_t n_gen = 0;   // documents for the general tiers
-  // The general tiers are chained on the device: the wide lean kernel (host count: the narrow kernel's deferrals),
-  // then the wave and workgroup kernels, each reading its count from the counter the kernel before it wrote (stream
-  // order; the host count is only the bound that sizes the persistent grid) -- one host wait for all three.
-  const unsigned int* d_wide_defer = (const unsigned int*)((const char*)P.meta + offsetof(Meta, wide_defer));
-  const unsigned int* d_defer_count = (const unsigned int*)((const char*)P.meta + offsetof(Meta, defer_count));
-  const unsigned int* d_route_n = (const unsigned int*)((const char*)P.meta + offsetof(Meta, route_n));
-  // the large-document tier's documents leave the chain before the wave kernel (k_route_big): the rest go on to it
-  auto route = [&](const uint32_t* list, const unsigned int* n_dev, uint32_t n) {
-    return ygm_k_launch_route_big(P.upd_off, P.doc_upd, list, n_dev, n, c->flags, c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
-                                  c->status.as<int32_t>(), P.meta, c->fb_list.as<uint32_t>(), c->route_list.as<uint32_t>(), s);
-  };
-  uint32_t bound = 0;   // documents the chain may see (0: no chain)
+  return YGM_OK;
+}
+// The general tiers, chained on the device: the wide lean kernel (tier 1b: updates <= 64 bytes, documents <= 7 KB),
+// the routing pass that takes the large-document tier's documents out (k_route_big), the wave kernel (tier 2) and the
+// workgroup kernel (tier 3: documents over the wave class).  Each reads its count from the counter the kernel before
+// it wrote (stream order; the host's `bound` only sizes the persistent grid) -- one host wait for all of them.
+// On the wide route the wide kernel took the whole batch at the launch (async): it does not run here, the routing
+// pass takes the host's count of its deferrals, and the documents it was given are the batch.
+int MergeRun::general() {
+  // the DocMeta counters the tier kernels read as the device-side counts of their lists
+  const unsigned int* d_wide_defer = (const unsigned int*)((const char*)P.in.meta + offsetof(Meta, wide_defer));
+  const unsigned int* d_defer_count = (const unsigned int*)((const char*)P.in.meta + offsetof(Meta, defer_count));
+  const unsigned int* d_route_n = (const unsigned int*)((const char*)P.in.meta + offsetof(Meta, route_n));
+  uint32_t *narrow_left = c->defer_list.as<uint32_t>(), *wide_left = c->defer_w_list.as<uint32_t>(), *routed = c->route_list.as<uint32_t>(),
+           *wave_left = c->defer2_list.as<uint32_t>(), *to_large = c->fb_list.as<uint32_t>();
+  const uint32_t wide_in = P.wide_route ? P.n_docs : m.lean_defer;      // documents given to the wide kernel
+  const uint32_t bound = P.wide_route ? m.wide_defer : m.lean_defer;    // documents the chain may see (0: no chain)
+  n_gen = P.wide_route ? m.wide_defer : 0;
   HIPCHK(hipEventRecord(c->e0, s));
-  if (P.wide_route) {  // the wide kernel took the whole batch (async): its deferrals go on
-    n_gen = bound = m.wide_defer;
-    c->stats.docs_lean_wide += P.n_docs - m.wide_defer;
-    if (n_gen && route(c->defer_w_list.as<uint32_t>(), nullptr, n_gen)) return YGM_EDEVICE;
-    if (n_gen && ygm_k_launch_merge_wave(P.arena, P.upd_off, P.doc_upd, c->route_list.as<uint32_t>(), d_route_n, n_gen, c->flags,
-                                         c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                                         P.meta, c->defer2_list.as<uint32_t>(), c->fb_list.as<uint32_t>(), P.out_cap, s))
-      return YGM_EDEVICE;
-  } else if (m.lean_defer) {  // tier 1b: the wide lean kernel (updates <= 64 bytes, documents <= 7 KB) over tier 1's deferred list
-    bound = m.lean_defer;
-    if (P.doc_off && ygm_k_launch_build_off(P.doc_off, P.upd_len, P.doc_upd, c->defer_list.as<uint32_t>(), m.lean_defer,
-                                            const_cast<uint64_t*>(P.upd_off), s))   // (compact form: the deferred documents' offsets)
-      return YGM_EDEVICE;
-    if (ygm_k_launch_merge_lean_wide(P.arena, P.upd_off, P.doc_upd, P.n_docs, c->defer_list.as<uint32_t>(), m.lean_defer, c->flags,
-                                     c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                                     P.meta, nullptr, c->defer_w_list.as<uint32_t>(), P.out_cap, P.upd_len, s))
-      return YGM_EDEVICE;
-    // tier 2: the general wave-per-document kernel over the lean kernels' deferred list, after the routing pass
-    if (route(c->defer_w_list.as<uint32_t>(), d_wide_defer, bound)) return YGM_EDEVICE;
-    if (ygm_k_launch_merge_wave(P.arena, P.upd_off, P.doc_upd, c->route_list.as<uint32_t>(), d_route_n, bound, c->flags,
-                                c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                                P.meta, c->defer2_list.as<uint32_t>(), c->fb_list.as<uint32_t>(), P.out_cap, s))
-      return YGM_EDEVICE;
-  }
-  if (bound) {  // tier 3: documents over the wave class, one workgroup per document
-    if (ygm_k_launch_merge_fast(P.arena, P.upd_off, P.doc_upd, c->defer2_list.as<uint32_t>(), d_defer_count, bound, c->flags,
-                                c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                                P.slot_total, P.meta, c->fb_list.as<uint32_t>(), P.out_cap, s))
+  if (bound) {
+    if (!P.wide_route) {
+      if (P.doc_off && ygm_k_launch_build_off(P.doc_off, P.upd_len, P.in.doc_upd, narrow_left, bound, const_cast<uint64_t*>(P.in.upd_off), s))
+        return YGM_EDEVICE;   // (compact form: the deferred documents' offsets)
+      if (ygm_k_launch_merge_lean_wide(&P.in, &P.res, P.n_docs, narrow_left, bound, nullptr, wide_left, P.upd_len, s)) return YGM_EDEVICE;
+    }
+    if (ygm_k_launch_route_big(&P.in, &P.res, wide_left, P.wide_route ? nullptr : d_wide_defer, bound, to_large, routed, s) ||
+        ygm_k_launch_merge_wave(&P.in, &P.res, routed, d_route_n, bound, wave_left, to_large, s) ||
+        ygm_k_launch_merge_fast(&P.in, &P.res, wave_left, d_defer_count, bound, to_large, s))
       return YGM_EDEVICE;
     HIPCHK(hipEventRecord(c->e1, s));
-    const uint32_t lean_defer = m.lean_defer;
-    if ((e = read_meta(c, s, m, P.meta))) return e;
-    if (m.fault) return YGM_EDEVICE;
-    if (hipEventElapsedTime(&ms0, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms0;
-    if (!P.wide_route) { n_gen = m.wide_defer; c->stats.docs_lean_wide += lean_defer - m.wide_defer; }
+    if (const int e = reread()) return e;
+    add_span();
+    if (!P.wide_route) n_gen = m.wide_defer;
   }
-  uint32_t n_seq = 0;
-  unsigned long long cnt[5] = {0, 0, 0, 0, 0};   // tier 4: the scan's counters ([4], the slow queue's entries: the YGM_TIER_COUNTS line's only)
-  if (m.fb_count) {  // tier 4: large [snapshot, ...log] documents, one wave each; the rest go on to tier 5
-    const uint64_t blk_cap = m.fb_bytes / 4 + 2ull * m.fb_count + 16, rec_cap = m.fb_bytes + 2ull * m.fb_count + 16;
-    if (!c->big_blk.ensure(blk_cap * ygm_k_big_blk_bytes()) || !c->big_rec.ensure(rec_cap * ygm_k_big_rec_bytes()) ||
-        !c->big_list.ensure((size_t)m.fb_count * 4 + 4) || !c->big_up.ensure((size_t)m.fb_count * 4 + 4) ||
-        !c->big_scan.ensure(ygm_k_big_scan_bytes(m.fb_count, m.fb_bytes)))
-      return YGM_ENOMEM;
-    HIPCHK(hipEventRecord(c->e0, s));
-    // the snapshot scan; then documents with a snapshot over BIG_MID_U0 on the 16-wave size (stream2) beside the mid
-    // size over the rest (stream); a log over the mid size's LDS goes on to the 16-wave size after it
-    if (ygm_k_launch_big_scan(P.arena, P.upd_off, P.doc_upd, c->fb_list.as<uint32_t>(), m.fb_count, c->flags, c->big_scan.p, m.fb_bytes, s))
-      return YGM_EDEVICE;
-    unsigned long long* d_cnt; uint32_t *llist, *mlist;
-    ygm_k_big_lists(c->big_scan.p, m.fb_count, m.fb_bytes, &d_cnt, &llist, &mlist);
-    c->stats.host_syncs++;
-    HIPCHK(hipMemcpyAsync(c->h_meta, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    memcpy(cnt, c->h_meta, sizeof cnt);
-    auto launch = [&](int large, const uint32_t* list, uint32_t n, hipStream_t st) {
-      return ygm_k_launch_merge_big(large, P.arena, P.upd_off, P.doc_upd, c->fb_list.as<uint32_t>(), m.fb_count, list, n,
-                                    c->big_up.as<uint32_t>(), c->flags, c->out.as<uint8_t>(), c->out_off.as<uint64_t>(),
-                                    c->out_len.as<uint64_t>(), c->status.as<int32_t>(), P.meta, c->big_list.as<uint32_t>(), c->big_blk.p,
-                                    blk_cap, c->big_rec.p, rec_cap, P.slot_total, P.out_cap, c->big_scan.p, m.fb_bytes, st);
-    };
-    // once the 16-wave size runs on stream2, every exit waits for it: its kernels write the outputs, the counters
-    // and the tier's scratch, which the next call on this context reuses on `stream`
-    struct Join2 {
-      hipStream_t st = nullptr;
-      ~Join2() { if (st) (void)hipStreamSynchronize(st); }
-    } join2;
-    if (cnt[2]) {
-      if (!c->stream2) {   // created on first use, only on contexts that run the 16-wave size
-        int prio_lo = 0, prio_hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+  c->stats.docs_lean_wide += wide_in - n_gen;
+  return YGM_OK;
+}
+// Tier 4: large [snapshot, ...log] documents, one workgroup each; what it cannot finish goes on to tier 5 (n_seq).
+// The snapshot scan; then documents with a snapshot over BIG_MID_U0 on the 16-wave size (stream2) beside the mid size
+// over the rest (stream); a log over the mid size's LDS goes on to the 16-wave size after it.
+int MergeRun::large() {
+  const uint64_t blk_cap = m.fb_bytes / 4 + 2ull * m.fb_count + 16, rec_cap = m.fb_bytes + 2ull * m.fb_count + 16;
+  if (!c->big_blk.ensure(blk_cap * ygm_k_big_blk_bytes()) || !c->big_rec.ensure(rec_cap * ygm_k_big_rec_bytes()) ||
+      !c->big_list.ensure((size_t)m.fb_count * 4 + 4) || !c->big_up.ensure((size_t)m.fb_count * 4 + 4) ||
+      !c->big_scan.ensure(ygm_k_big_scan_bytes(m.fb_count, m.fb_bytes)))
+    return YGM_ENOMEM;
+  const ygm_big_tier big{c->fb_list.as<uint32_t>(), m.fb_count, m.fb_bytes, c->big_scan.p, c->big_blk.p, blk_cap, c->big_rec.p, rec_cap,
+                         c->big_up.as<uint32_t>(), c->big_list.as<uint32_t>()};
+  HIPCHK(hipEventRecord(c->e0, s));
+  if (ygm_k_launch_big_scan(&P.in, &big, s)) return YGM_EDEVICE;
+  unsigned long long* d_cnt; uint32_t *llist, *mlist;
+  ygm_k_big_lists(big.scan, big.n_fb, big.fb_bytes, &d_cnt, &llist, &mlist);
+  c->stats.host_syncs++;
+  HIPCHK(hipMemcpyAsync(c->h_meta, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  memcpy(cnt, c->h_meta, sizeof cnt);
+  const uint32_t n_wide = (uint32_t)cnt[2], n_mid = (uint32_t)cnt[3];   // documents that start on the 16-wave / the mid size
+  // once the 16-wave size runs on stream2, every exit waits for it: its kernels write the outputs, the counters
+  // and the tier's scratch, which the next call on this context reuses on `stream`
+  struct Join2 {
+    hipStream_t st = nullptr;
+    ~Join2() { if (st) (void)hipStreamSynchronize(st); }
+  } join2;
+  if (n_wide) {
+    if (!c->stream2) {   // created on first use, only on contexts that run the 16-wave size
+      int prio_lo = 0, prio_hi = 0;
+      HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
 #ifndef YGM_S2_PRIO
 #define YGM_S2_PRIO 1
 #endif
-        HIPCHK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, YGM_S2_PRIO ? prio_hi : prio_lo));
-      }
-      HIPCHK(hipEventRecord(c->e2, s));
-      HIPCHK(hipStreamWaitEvent(c->stream2, c->e2, 0));
-      join2.st = c->stream2;
-      if (launch(1, llist, (uint32_t)cnt[2], c->stream2)) return YGM_EDEVICE;
-      HIPCHK(hipEventRecord(c->e3, c->stream2));
-      if (cnt[3] && ygm_k_launch_big_wait(P.meta, (uint32_t)cnt[2], s)) return YGM_EDEVICE;   // (their workgroups resident first)
+      HIPCHK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, YGM_S2_PRIO ? prio_hi : prio_lo));
     }
-    if (launch(0, mlist, (uint32_t)cnt[3], s)) return YGM_EDEVICE;
-    if ((e = read_meta(c, s, m, P.meta))) return e;
-    if (m.fault) return YGM_EDEVICE;
-    if (m.mid_defer && launch(1, c->big_up.as<uint32_t>(), m.mid_defer, s)) return YGM_EDEVICE;
-    if (cnt[2]) { HIPCHK(hipStreamWaitEvent(s, c->e3, 0)); join2.st = nullptr; }
-    HIPCHK(hipEventRecord(c->e1, s));
-    if ((e = read_meta(c, s, m, P.meta))) return e;
-    if (m.fault) return YGM_EDEVICE;
-    if (hipEventElapsedTime(&ms0, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms0;
-    c->stats.docs_big += m.fb_count - m.big_defer;
-    n_seq = m.big_defer;
+    HIPCHK(hipEventRecord(c->e2, s));
+    HIPCHK(hipStreamWaitEvent(c->stream2, c->e2, 0));
+    join2.st = c->stream2;
+    if (ygm_k_launch_merge_big(1, &P.in, &P.res, &big, llist, n_wide, c->stream2)) return YGM_EDEVICE;
+    HIPCHK(hipEventRecord(c->e3, c->stream2));
+    if (n_mid && ygm_k_launch_big_wait(P.in.meta, n_wide, s)) return YGM_EDEVICE;   // (their workgroups resident first)
   }
-  if (n_seq) {  // tier 5: the exact sequential replay (scratch sized from the tier-4 counters: an upper bound)
-    const uint64_t upd_cap = m.fb_upds + 1, byte_cap = m.fb_bytes + 8ull * m.fb_count + 8;
-    if (!c->s_readers.ensure(upd_cap * ygm_k_seq_reader_bytes()) || !c->s_order.ensure(upd_cap * 4) || !c->s_tmp.ensure(upd_cap * 4) ||
-        !c->s_ubase.ensure(upd_cap * 8) || !c->s_ulen.ensure(upd_cap * 4) || !c->s_cnt.ensure(byte_cap * 4) ||
-        !c->s_drec.ensure((byte_cap / 2 + 1) * ygm_k_drec_bytes()))
-      return YGM_ENOMEM;
-    HIPCHK(hipEventRecord(c->e0, s));
-    if (ygm_k_launch_merge_seq(P.arena, P.upd_off, P.doc_upd, c->big_list.as<uint32_t>(), n_seq, c->flags, c->out.as<uint8_t>(),
-                               c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), P.meta,
-                               c->s_readers.p, c->s_order.as<int>(), c->s_tmp.as<int>(), c->s_ubase.as<const uint8_t*>(),
-                               c->s_ulen.as<uint32_t>(), upd_cap, c->s_cnt.as<uint32_t>(), c->s_drec.p, byte_cap, P.slot_total, P.out_cap, s))
-      return YGM_EDEVICE;
-    HIPCHK(hipEventRecord(c->e1, s));
-    if ((e = read_meta(c, s, m, P.meta))) return e;
-    if (hipEventElapsedTime(&ms0, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms0;
-    c->stats.docs_seq += n_seq;
-  }
+  if (ygm_k_launch_merge_big(0, &P.in, &P.res, &big, mlist, n_mid, s)) return YGM_EDEVICE;
+  if (const int e = reread()) return e;
+  if (m.mid_defer && ygm_k_launch_merge_big(1, &P.in, &P.res, &big, big.up_list, m.mid_defer, s)) return YGM_EDEVICE;
+  if (n_wide) { HIPCHK(hipStreamWaitEvent(s, c->e3, 0)); join2.st = nullptr; }
+  HIPCHK(hipEventRecord(c->e1, s));
+  if (const int e = reread()) return e;
+  add_span();
+  c->stats.docs_big += m.fb_count - m.big_defer;
+  n_seq = m.big_defer;
+  return YGM_OK;
+}
+// Tier 5: the exact sequential replay of the documents tier 4 left (scratch sized from its counters: an upper bound)
+int MergeRun::seq() {
+  const uint64_t upd_cap = m.fb_upds + 1, byte_cap = m.fb_bytes + 8ull * m.fb_count + 8;
+  if (!c->s_readers.ensure(upd_cap * ygm_k_seq_reader_bytes()) || !c->s_order.ensure(upd_cap * 4) || !c->s_tmp.ensure(upd_cap * 4) ||
+      !c->s_ubase.ensure(upd_cap * 8) || !c->s_ulen.ensure(upd_cap * 4) || !c->s_cnt.ensure(byte_cap * 4) ||
+      !c->s_drec.ensure((byte_cap / 2 + 1) * ygm_k_drec_bytes()))
+    return YGM_ENOMEM;
+  const ygm_seq_scratch scr{c->s_readers.p, c->s_order.as<int>(), c->s_tmp.as<int>(), c->s_ubase.as<const uint8_t*>(), c->s_ulen.as<uint32_t>(),
+                            c->s_cnt.as<uint32_t>(), c->s_drec.p, upd_cap, byte_cap};
+  HIPCHK(hipEventRecord(c->e0, s));
+  if (ygm_k_launch_merge_seq(&P.in, &P.res, c->big_list.as<uint32_t>(), n_seq, &scr, s)) return YGM_EDEVICE;
+  HIPCHK(hipEventRecord(c->e1, s));
+  if (const int e = read_meta(c, s, m, P.in.meta)) return e;
+  add_span();
+  c->stats.docs_seq += n_seq;
+  return YGM_OK;
+}
+// the tier lines, the call's statistics and its result
+void MergeRun::report(ygm_device_result* out) {
   // YGM_TIER_COUNTS (testing knob): the call's raw tier counters, one stderr line (all 0 when the chain did not run)
   if (getenv("YGM_TIER_COUNTS"))
     fprintf(stderr, "ygm merge tiers: docs %u lean_defer %u wide_defer %u to_wave %u to_workgroup %u to_large %u to_seq %u\n", P.n_docs,
@@ -479,13 +473,24 @@ int ygm_merge_v1_device_finish(ygm_ctx* c, ygm_device_result* out) {
   if (m.fb_count && getenv("YGM_TIER_COUNTS"))
     fprintf(stderr, "ygm large tiers: docs %u positions %llu tasks %llu slow_queue %llu wide_first %llu mid_first %llu mid_to_wide %u to_seq %u\n",
             m.fb_count, cnt[0], cnt[1], cnt[4], cnt[2], cnt[3], m.mid_defer, m.big_defer);
-  const uint64_t extent = P.slot_total + m.cursor;
   c->stats.calls++; c->stats.docs += P.n_docs; c->stats.updates += P.n_upd;
   c->stats.docs_fast += n_gen - m.fb_count;   // finished by the wave / workgroup tiers (tier 4 counted above)
   c->stats.docs_lean += P.n_docs - n_gen;      // finished by the lean kernels (narrow + wide)
   c->stats.bytes_in += P.arena_bytes; c->stats.bytes_out += payload_total(m);
-  fill_dev_result(c, extent, out);
+  fill_dev_result(c, P.res.slot_total + m.cursor, out);
   out->payload_bytes = payload_total(m);
+}
+
+int ygm_merge_v1_device_finish(ygm_ctx* c, ygm_device_result* out) {
+  if (!c || !out || !c->pend.live) return YGM_EINVAL;
+  c->pend.live = false;
+  (void)hipSetDevice(c->device);
+  MergeRun R{c, c->pend.s, c->pend};
+  int e;
+  if ((e = R.lean_span()) || (e = R.general())) return e;
+  if (R.m.fb_count && (e = R.large())) return e;
+  if (R.n_seq && (e = R.seq())) return e;
+  R.report(out);
   return YGM_OK;
 }
 
@@ -540,17 +545,16 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
   e = prep_outputs(c, n_docs, out_cap, s, true);
   if (e) return e;
   void* meta = c->meta_slot(2);
+  const ygm_results res = c->results(slot_total, out_cap);
   if (mode == DOC_DIFF && (!c->sv_tbl.ensure(ygm_k_sv_table_bytes(n_docs)) || !c->sv_tn.ensure(4ull * n_docs + 4))) return YGM_ENOMEM;
   HIPCHK(hipEventRecord(c->e0, s));
   if (gather) {
-    if (ygm_k_launch_doc_lean_gather(d_arena, d_doc_off, d_sv, d_sv_off, c->ask_ix.as<uint32_t>(), c->ask_base.as<uint64_t>(), n_asks,
-                                     c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                                     meta, c->defer_list.as<uint32_t>(), out_cap, c->sv_tbl.as<uint8_t>(), c->sv_tn.as<uint32_t>(), s))
+    if (ygm_k_launch_doc_lean_gather(d_arena, d_doc_off, d_sv, d_sv_off, c->ask_ix.as<uint32_t>(), c->ask_base.as<uint64_t>(), n_asks, &res,
+                                     meta, c->defer_list.as<uint32_t>(), c->sv_tbl.as<uint8_t>(), c->sv_tn.as<uint32_t>(), s))
       return YGM_EDEVICE;
   } else
-  if (ygm_k_launch_doc_lean(mode, d_arena, arena_bytes, d_doc_off, d_sv, sv_bytes, d_sv_off, n_docs, flags, c->out.as<uint8_t>(),
-                            c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), meta,
-                            c->defer_list.as<uint32_t>(), out_cap, c->sv_tbl.as<uint8_t>(), c->sv_tn.as<uint32_t>(), s))
+  if (ygm_k_launch_doc_lean(mode, d_arena, arena_bytes, d_doc_off, d_sv, sv_bytes, d_sv_off, n_docs, flags, &res, meta,
+                            c->defer_list.as<uint32_t>(), c->sv_tbl.as<uint8_t>(), c->sv_tn.as<uint32_t>(), s))
     return YGM_EDEVICE;
   HIPCHK(hipEventRecord(c->e1, s));
   Meta m;
@@ -565,14 +569,12 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
   if (m.lean_defer) {   // the exact per-document kernel over the deferred list, packed after the slots
     HIPCHK(hipEventRecord(c->e0, s));
     if (gather) {
-      if (ygm_k_launch_doc_gather(d_arena, d_doc_off, d_sv, d_sv_off, c->defer_list.as<uint32_t>(), c->ask_ix.as<uint32_t>(), slot_total,
-                                  m.lean_defer, flags, c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
-                                  c->status.as<int32_t>(), c->lb.as<unsigned long long>(), meta, out_cap, s))
+      if (ygm_k_launch_doc_gather(d_arena, d_doc_off, d_sv, d_sv_off, c->defer_list.as<uint32_t>(), c->ask_ix.as<uint32_t>(), m.lean_defer,
+                                  flags, &res, c->lb.as<unsigned long long>(), meta, s))
         return YGM_EDEVICE;
     } else
-    if (ygm_k_launch_doc(mode, d_arena, d_doc_off, d_sv, d_sv_off, c->defer_list.as<uint32_t>(), slot_total, m.lean_defer, flags,
-                         c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(),
-                         c->lb.as<unsigned long long>(), meta, out_cap, s))
+    if (ygm_k_launch_doc(mode, d_arena, d_doc_off, d_sv, d_sv_off, c->defer_list.as<uint32_t>(), m.lean_defer, flags, &res,
+                         c->lb.as<unsigned long long>(), meta, s))
       return YGM_EDEVICE;
     HIPCHK(hipEventRecord(c->e1, s));
     if ((e = read_meta(c, s, m, meta))) return e;
@@ -580,7 +582,7 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
     if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
   }
   // gather: an ask of a refused state id carries YGM_EINVAL (whatever the kernels left there)
-  if (gather && ygm_k_launch_ask_status(c->ask_ix.as<uint32_t>(), n_asks, nullptr, c->status.as<int32_t>(), c->out_len.as<uint64_t>(), s))
+  if (gather && ygm_k_launch_ask_status(c->ask_ix.as<uint32_t>(), n_asks, nullptr, res.status, res.out_len, s))
     return YGM_EDEVICE;
   const uint64_t payload = payload_total(m) + m.fast_total;
   c->stats.calls++; c->stats.docs += n_docs; c->stats.docs_fast += m.lean_defer; c->stats.docs_lean += n_docs - m.lean_defer;

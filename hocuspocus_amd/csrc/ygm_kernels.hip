@@ -3513,21 +3513,20 @@ void ygm_k_big_lists(void* scan, uint32_t n_fb, uint64_t fb_bytes, unsigned long
 }
 static uint32_t grid_knob(const char* name);   // (the launchers' testing knobs, below)
 size_t ygm_k_big_scan_bytes(uint32_t n_fb, uint64_t fb_bytes) { BigScan S; size_t t; big_scan_layout(n_fb, fb_bytes, S, nullptr, t); return t; }
-int ygm_k_launch_big_scan(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list,
-                          uint32_t n_fb, uint32_t flags, void* scan, uint64_t fb_bytes, hipStream_t s) {
-  if (n_fb == 0) return 0;
+int ygm_k_launch_big_scan(const ygm_merge_in* in, const ygm_big_tier* big, hipStream_t s) {
+  if (big->n_fb == 0) return 0;
   BigScan S; size_t total;
-  big_scan_layout(n_fb, fb_bytes, S, (uint8_t*)scan, total);
+  big_scan_layout(big->n_fb, big->fb_bytes, S, (uint8_t*)big->scan, total);
   if (hipMemsetAsync(S.cnt, 0, 64, s) != hipSuccess) return ygm_launch_rc(__func__);
-  hipLaunchKernelGGL(k_big_pick, dim3((n_fb + 15) / 16), dim3(1024), 0, s, arena, upd_off, doc_upd, fb_list, n_fb, S);
+  hipLaunchKernelGGL(k_big_pick, dim3((big->n_fb + 15) / 16), dim3(1024), 0, s, in->arena, in->upd_off, in->doc_upd, big->fb_list, big->n_fb, S);
   // the scan: a persistent grid over the tasks (at most 16 workgroups per CU; the task count is on the device)
   // YGM_BIG_SCAN_GRID (testing knob, as YGM_WAVE_GRID): a positive value replaces both grids, so a workgroup takes
   // many tasks / queue blocks in turn through the same LDS (s_q and s_b; k_big_val's s_cnt and s_ix)
   const uint32_t env = grid_knob("YGM_BIG_SCAN_GRID");
   const uint64_t g = env ? env : S.ntask_cap < 16ull * device_cus() ? S.ntask_cap : 16ull * device_cus();
-  hipLaunchKernelGGL(k_big_scan, dim3((uint32_t)g), dim3(256), 0, s, arena, upd_off, doc_upd, fb_list, flags, S);
+  hipLaunchKernelGGL(k_big_scan, dim3((uint32_t)g), dim3(256), 0, s, in->arena, in->upd_off, in->doc_upd, big->fb_list, in->flags, S);
   const uint64_t gv = env ? env : S.vq_cap / 256 + 1 < 8ull * device_cus() ? S.vq_cap / 256 + 1 : 8ull * device_cus();
-  hipLaunchKernelGGL(k_big_val, dim3((uint32_t)gv), dim3(256), 0, s, arena, upd_off, doc_upd, fb_list, flags, S);
+  hipLaunchKernelGGL(k_big_val, dim3((uint32_t)gv), dim3(256), 0, s, in->arena, in->upd_off, in->doc_upd, big->fb_list, in->flags, S);
   return ygm_launch_rc(__func__);
 }
 // The mid size starts after the 16-wave size's workgroups are resident: a 16-wave workgroup needs a whole CU (its LDS),
@@ -3554,22 +3553,15 @@ int ygm_k_launch_big_wait(void* meta, uint32_t n_large, hipStream_t s) {
 }
 // large = 0: the mid size, large = 1: the 16-wave size, over the fb_list indices in fbx[0, n) (the mid size sends a
 // document whose log exceeds its LDS to up_list, meta->mid_defer)
-int ygm_k_launch_merge_big(int large, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list,
-                           uint32_t n_fb, const uint32_t* fbx, uint32_t n, uint32_t* up_list, uint32_t flags, uint8_t* out,
-                           uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, uint32_t* fb2_list, void* blk,
-                           uint64_t blk_cap, void* rec, uint64_t rec_cap, uint64_t slot_total, uint64_t out_cap, void* scan,
-                           uint64_t fb_bytes, hipStream_t s) {
+int ygm_k_launch_merge_big(int large, const ygm_merge_in* in, const ygm_results* r, const ygm_big_tier* big, const uint32_t* fbx, uint32_t n,
+                           hipStream_t s) {
   if (n == 0) return 0;
   BigScan S; size_t total;
-  big_scan_layout(n_fb, fb_bytes, S, (uint8_t*)scan, total);
-  if (large)
-    hipLaunchKernelGGL(k_merge_big<BigCfgL>, dim3(n), dim3(BigCfgL::THREADS), 0, s, arena, upd_off, doc_upd, fb_list, flags, out, out_off,
-                       out_len, status, (DocMeta*)meta, fb2_list, (BigBlk*)blk, blk_cap, (BigRec*)rec, rec_cap, slot_total, out_cap, S,
-                       fbx, up_list);
-  else
-    hipLaunchKernelGGL(k_merge_big<BigCfgM>, dim3(n), dim3(BigCfgM::THREADS), 0, s, arena, upd_off, doc_upd, fb_list, flags, out, out_off,
-                       out_len, status, (DocMeta*)meta, fb2_list, (BigBlk*)blk, blk_cap, (BigRec*)rec, rec_cap, slot_total, out_cap, S,
-                       fbx, up_list);
+  big_scan_layout(big->n_fb, big->fb_bytes, S, (uint8_t*)big->scan, total);
+  auto k = large ? k_merge_big<BigCfgL> : k_merge_big<BigCfgM>;
+  hipLaunchKernelGGL(k, dim3(n), dim3(large ? BigCfgL::THREADS : BigCfgM::THREADS), 0, s, in->arena, in->upd_off, in->doc_upd, big->fb_list,
+                     in->flags, r->out, r->out_off, r->out_len, r->status, (DocMeta*)in->meta, big->seq_list, (BigBlk*)big->blk, big->blk_cap,
+                     (BigRec*)big->rec, big->rec_cap, r->slot_total, r->out_cap, S, fbx, big->up_list);
   return ygm_launch_rc(__func__);
 }
 size_t ygm_k_meta_bytes() { return sizeof(DocMeta); }
@@ -3577,25 +3569,23 @@ size_t ygm_k_seq_reader_bytes() { return sizeof(Stream); }
 size_t ygm_k_drec_bytes() { return sizeof(DRec); }
 
 int ygm_k_launch_doc(int mode, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                     const uint32_t* docs, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                     uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap, hipStream_t s) {
+                     const uint32_t* docs, uint32_t n_docs, uint32_t flags, const ygm_results* r, unsigned long long* lb, void* meta,
+                     hipStream_t s) {
   const uint32_t tiles = (n_docs + DOC_NT - 1) / DOC_NT;
   if (tiles == 0) return 0;
-  if (mode == 0)
-    hipLaunchKernelGGL(k_doc<0>, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out, out_off, out_len, status, lb, (DocMeta*)meta, out_cap);
-  else
-    hipLaunchKernelGGL(k_doc<1>, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out, out_off, out_len, status, lb, (DocMeta*)meta, out_cap);
+  auto k = mode == 0 ? k_doc<0> : k_doc<1>;
+  hipLaunchKernelGGL(k, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, r->slot_total, n_docs, flags, r->out,
+                     r->out_off, r->out_len, r->status, lb, (DocMeta*)meta, r->out_cap);
   return ygm_launch_rc(__func__);
 }
 
 int ygm_k_launch_doc_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                            const uint32_t* docs, const uint32_t* ask_ix, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out,
-                            uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap,
-                            hipStream_t s) {
+                            const uint32_t* docs, const uint32_t* ask_ix, uint32_t n_docs, uint32_t flags, const ygm_results* r,
+                            unsigned long long* lb, void* meta, hipStream_t s) {
   const uint32_t tiles = (n_docs + DOC_NT - 1) / DOC_NT;
   if (tiles == 0) return 0;
-  hipLaunchKernelGGL(k_doc_gather, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, out_base, n_docs, flags, out,
-                     out_off, out_len, status, lb, (DocMeta*)meta, out_cap, ask_ix);
+  hipLaunchKernelGGL(k_doc_gather, dim3(tiles), dim3(DOC_NT), 0, s, arena, doc_off, sv_arena, sv_off, docs, r->slot_total, n_docs, flags,
+                     r->out, r->out_off, r->out_len, r->status, lb, (DocMeta*)meta, r->out_cap, ask_ix);
   return ygm_launch_rc(__func__);
 }
 
@@ -3702,23 +3692,25 @@ static uint32_t resident_blocks(K kernel, int threads, uint32_t fallback) {
 
 uint32_t ygm_k_lean_stage_bytes() { return (uint32_t)LN_IN; }   // input bytes the narrow lean kernel stages per document
 uint32_t ygm_k_lean_no_idlen_flag() { return LN_F_NO_IDLEN; }
-// doc_off / upd_len non-null: the compact input form (ygm_merge_v1_device_lens); upd_off is then unused
-int ygm_k_launch_merge_lean(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, uint32_t flags,
-                            uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, void* meta_next,
-                            uint32_t* defer_list, uint64_t out_cap, hipStream_t s, const uint64_t* doc_off, const uint16_t* upd_len) {
+// doc_off / upd_len non-null: the compact input form (ygm_merge_v1_device_lens); in->upd_off is then unused.
+// lean_flags: bits for this kernel alone, beside in->flags
+int ygm_k_launch_merge_lean(const ygm_merge_in* in, const ygm_results* r, uint32_t n_docs, uint32_t lean_flags, void* meta_next,
+                            uint32_t* defer_list, const uint64_t* doc_off, const uint16_t* upd_len, hipStream_t s) {
   if (n_docs == 0) return 0;
+  const uint32_t flags = in->flags | lean_flags;
   // persistent waves: enough for full occupancy, each looping over documents d, d + G, ...
   const int n_cu = (int)device_cus();
   const char* env = getenv("YGM_LEAN_WAVES_PER_CU");
   const uint32_t wpc = env ? (uint32_t)atoi(env) : 16u;
   const uint32_t grid = n_docs < (uint32_t)n_cu * wpc ? n_docs : (uint32_t)n_cu * wpc;
   if (doc_off)
-    hipLaunchKernelGGL((k_merge_lean<0, 1>), dim3(grid), dim3(WAVE), 0, s, arena, upd_off, doc_upd, n_docs, flags, out, out_off, out_len,
-                       status, (DocMeta*)meta, (DocMeta*)meta_next, defer_list, out_cap, (const uint32_t*)nullptr, 0u, doc_off, upd_len);
+    hipLaunchKernelGGL((k_merge_lean<0, 1>), dim3(grid), dim3(WAVE), 0, s, in->arena, in->upd_off, in->doc_upd, n_docs, flags, r->out,
+                       r->out_off, r->out_len, r->status, (DocMeta*)in->meta, (DocMeta*)meta_next, defer_list, r->out_cap,
+                       (const uint32_t*)nullptr, 0u, doc_off, upd_len);
   else
-    hipLaunchKernelGGL((k_merge_lean<0, 0>), dim3(grid), dim3(WAVE), 0, s, arena, upd_off, doc_upd, n_docs, flags, out, out_off, out_len,
-                       status, (DocMeta*)meta, (DocMeta*)meta_next, defer_list, out_cap, (const uint32_t*)nullptr, 0u,
-                       (const uint64_t*)nullptr, (const uint16_t*)nullptr);
+    hipLaunchKernelGGL((k_merge_lean<0, 0>), dim3(grid), dim3(WAVE), 0, s, in->arena, in->upd_off, in->doc_upd, n_docs, flags, r->out,
+                       r->out_off, r->out_len, r->status, (DocMeta*)in->meta, (DocMeta*)meta_next, defer_list, r->out_cap,
+                       (const uint32_t*)nullptr, 0u, (const uint64_t*)nullptr, (const uint16_t*)nullptr);
   return ygm_launch_rc(__func__);
 }
 // The update-offset table of the compact input form, for the documents of `list` (every document: list == nullptr):
@@ -3756,16 +3748,15 @@ int ygm_k_launch_build_off(const uint64_t* doc_off, const uint16_t* upd_len, con
 }
 // the wide lean kernel over the narrow one's deferred list (n_list entries); its own deferrals go to defer_list
 // (count: DocMeta::wide_defer)
-int ygm_k_launch_merge_lean_wide(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, const uint32_t* list,
-                                 uint32_t n_list, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status,
-                                 void* meta, void* meta_next, uint32_t* defer_list, uint64_t out_cap, const uint16_t* upd_len, hipStream_t s) {
+int ygm_k_launch_merge_lean_wide(const ygm_merge_in* in, const ygm_results* r, uint32_t n_docs, const uint32_t* list, uint32_t n_list,
+                                 void* meta_next, uint32_t* defer_list, const uint16_t* upd_len, hipStream_t s) {
   if (n_list == 0) return 0;
   static std::atomic<uint32_t> cache[YGM_MAX_DEVICES];
   const uint32_t resident = per_device(cache, [] { const char* g = getenv("YGM_WIDE_GRID"); return g ? (uint32_t)atoi(g) : resident_blocks(k_merge_lean<1, 0>, WAVE, 2048u); });
   const uint32_t grid = n_list < resident ? n_list : resident;
-  hipLaunchKernelGGL((k_merge_lean<1, 0>), dim3(grid), dim3(WAVE), 0, s, arena, upd_off, doc_upd, n_docs, flags, out, out_off, out_len,
-                     status, (DocMeta*)meta, (DocMeta*)meta_next, defer_list, out_cap, list, n_list, (const uint64_t*)nullptr,
-                     upd_len);
+  hipLaunchKernelGGL((k_merge_lean<1, 0>), dim3(grid), dim3(WAVE), 0, s, in->arena, in->upd_off, in->doc_upd, n_docs, in->flags, r->out,
+                     r->out_off, r->out_len, r->status, (DocMeta*)in->meta, (DocMeta*)meta_next, defer_list, r->out_cap, list, n_list,
+                     (const uint64_t*)nullptr, upd_len);
   return ygm_launch_rc(__func__);
 }
 
@@ -3777,9 +3768,8 @@ static uint32_t grid_knob(const char* name) {
   return 0;
 }
 
-int ygm_k_launch_merge_wave(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs,
-                            const unsigned int* n_dev, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
-                            int32_t* status, void* meta, uint32_t* defer_list, uint32_t* fb_list, uint64_t out_cap, hipStream_t s) {
+int ygm_k_launch_merge_wave(const ygm_merge_in* in, const ygm_results* r, const uint32_t* docs, const unsigned int* n_dev, uint32_t n_docs,
+                            uint32_t* defer_list, uint32_t* fb_list, hipStream_t s) {
   if (n_docs == 0) return 0;
   // persistent: exactly the waves that are resident at once (LDS / VGPR occupancy x CUs), so no wave starts
   // its grid-stride share after the others have finished theirs; n_docs is the upper bound of the device count
@@ -3787,42 +3777,38 @@ int ygm_k_launch_merge_wave(const uint8_t* arena, const uint64_t* upd_off, const
   const uint32_t env = grid_knob("YGM_WAVE_GRID");
   const uint32_t resident = env ? env : per_device(cache, [] { return resident_blocks(k_merge_wave, WAVE, 2048u); });
   const uint32_t grid = n_docs < resident ? n_docs : resident;
-  hipLaunchKernelGGL(k_merge_wave, dim3(grid), dim3(WAVE), 0, s, arena, upd_off, doc_upd, docs, n_dev, n_docs,
-                     flags, out, out_off, out_len, status, (DocMeta*)meta, defer_list, fb_list, out_cap);
+  hipLaunchKernelGGL(k_merge_wave, dim3(grid), dim3(WAVE), 0, s, in->arena, in->upd_off, in->doc_upd, docs, n_dev, n_docs, in->flags, r->out,
+                     r->out_off, r->out_len, r->status, (DocMeta*)in->meta, defer_list, fb_list, r->out_cap);
   return ygm_launch_rc(__func__);
 }
 
-int ygm_k_launch_route_big(const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs, const unsigned int* n_dev, uint32_t n_docs,
-                           uint32_t flags, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, uint32_t* fb_list, uint32_t* rest,
-                           hipStream_t s) {
+int ygm_k_launch_route_big(const ygm_merge_in* in, const ygm_results* r, const uint32_t* docs, const unsigned int* n_dev, uint32_t n_docs,
+                           uint32_t* fb_list, uint32_t* rest, hipStream_t s) {
   if (n_docs == 0) return 0;
   const uint32_t grid = (n_docs + 255u) / 256u < 2048u ? (n_docs + 255u) / 256u : 2048u;   // (n_docs: the bound of the device count)
-  hipLaunchKernelGGL(k_route_big, dim3(grid), dim3(256), 0, s, upd_off, doc_upd, docs, n_dev, n_docs, flags, out_off, out_len, status,
-                     (DocMeta*)meta, fb_list, rest);
+  hipLaunchKernelGGL(k_route_big, dim3(grid), dim3(256), 0, s, in->upd_off, in->doc_upd, docs, n_dev, n_docs, in->flags, r->out_off, r->out_len,
+                     r->status, (DocMeta*)in->meta, fb_list, rest);
   return ygm_launch_rc(__func__);
 }
 
-int ygm_k_launch_merge_fast(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs,
-                            const unsigned int* n_dev, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
-                            int32_t* status, uint64_t slot_total, void* meta, uint32_t* fb_list, uint64_t out_cap, hipStream_t s) {
+int ygm_k_launch_merge_fast(const ygm_merge_in* in, const ygm_results* r, const uint32_t* docs, const unsigned int* n_dev, uint32_t n_docs,
+                            uint32_t* fb_list, hipStream_t s) {
   if (n_docs == 0) return 0;
   static std::atomic<uint32_t> cache[YGM_MAX_DEVICES];   // persistent: the resident workgroups (see ygm_k_launch_merge_wave)
   const uint32_t env = grid_knob("YGM_FAST_GRID");
   const uint32_t resident = env ? env : per_device(cache, [] { return resident_blocks(k_merge_fast, M_NT, 512u); });
   const uint32_t grid = n_docs < resident ? n_docs : resident;
-  hipLaunchKernelGGL(k_merge_fast, dim3(grid), dim3(M_NT), 0, s, arena, upd_off, doc_upd, docs, n_dev, n_docs, flags, out, out_off, out_len,
-                     status, slot_total, (DocMeta*)meta, fb_list, out_cap);
+  hipLaunchKernelGGL(k_merge_fast, dim3(grid), dim3(M_NT), 0, s, in->arena, in->upd_off, in->doc_upd, docs, n_dev, n_docs, in->flags, r->out,
+                     r->out_off, r->out_len, r->status, r->slot_total, (DocMeta*)in->meta, fb_list, r->out_cap);
   return ygm_launch_rc(__func__);
 }
 
-int ygm_k_launch_merge_seq(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list, uint32_t n_fb,
-                           uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta,
-                           void* readers, int* order, int* tmp, const uint8_t** ubase, uint32_t* ulen, uint64_t upd_cap,
-                           uint32_t* cnt, void* drec, uint64_t byte_cap, uint64_t slot_total, uint64_t out_cap, hipStream_t s) {
+int ygm_k_launch_merge_seq(const ygm_merge_in* in, const ygm_results* r, const uint32_t* fb_list, uint32_t n_fb, const ygm_seq_scratch* h,
+                           hipStream_t s) {
   if (n_fb == 0) return 0;
-  SeqScratch scr{(Stream*)readers, order, tmp, ubase, ulen, cnt, (DRec*)drec, upd_cap, byte_cap};
-  hipLaunchKernelGGL(k_merge_seq, dim3((n_fb + 63) / 64), dim3(64), 0, s, arena, upd_off, doc_upd, fb_list, n_fb, flags, out, out_off,
-                     out_len, status, (DocMeta*)meta, scr, slot_total, out_cap);
+  SeqScratch scr{(Stream*)h->readers, h->order, h->tmp, h->ubase, h->ulen, h->cnt, (DRec*)h->drec, h->upd_cap, h->byte_cap};
+  hipLaunchKernelGGL(k_merge_seq, dim3((n_fb + 63) / 64), dim3(64), 0, s, in->arena, in->upd_off, in->doc_upd, fb_list, n_fb, in->flags, r->out,
+                     r->out_off, r->out_len, r->status, (DocMeta*)in->meta, scr, r->slot_total, r->out_cap);
   return ygm_launch_rc(__func__);
 }
 

@@ -1,7 +1,10 @@
 // ygm_launch.hpp -- the kernel launchers (ygm_k_*): defined in the .hip files, called by the host runtime
 // (ygm_engine.cpp).  Every definer and the caller include this header, so a definition that disagrees with its
-// declaration does not compile (C-linkage functions cannot be overloaded).  ygm_launch_rc is every launcher's return:
-// the launch's error, reported once.
+// declaration does not compile (C-linkage functions cannot be overloaded).  The merge tiers and the SV / diff walkers
+// take what they all share as two structs, each filled in one place per call: ygm_merge_in (what a tier reads) and
+// ygm_results (where results go).  A pointer cannot then land in its neighbour's place at a call site; a launcher
+// lists after them only what is its own (documents, device count, bound, lists, scratch, the stream last) and unpacks
+// them into its kernel's parameter list.  ygm_launch_rc is every launcher's return: the launch's error, reported once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -16,12 +19,27 @@ static inline int ygm_launch_rc(const char* fn) {
 }
 
 extern "C" {
+// what every merge tier reads: the packed updates, the context's flags, the call's counter slot (a DocMeta)
+struct ygm_merge_in { const uint8_t* arena; const uint64_t* upd_off; const uint32_t* doc_upd; uint32_t flags; void* meta; };
+// where results go: the output arena (per-document slots in [0, slot_total), the overflow region up to out_cap) and
+// each document's place, length and status
+struct ygm_results { uint8_t* out; uint64_t* out_off; uint64_t* out_len; int32_t* status; uint64_t slot_total, out_cap; };
+// the large-document tier's documents (n_fb entries of the routing pass's list, fb_bytes in all) and its scratch: the
+// scan (ygm_k_big_scan_bytes), block tables and struct records, the mid size's hand-ons, the documents left to replay
+struct ygm_big_tier {
+  const uint32_t* fb_list; uint32_t n_fb; uint64_t fb_bytes;
+  void *scan, *blk; uint64_t blk_cap; void* rec; uint64_t rec_cap;
+  uint32_t *up_list, *seq_list;
+};
+// the sequential replay's scratch: upd_cap entries of the per-update arrays, byte_cap of cnt, byte_cap / 2 + 1 of drec
+struct ygm_seq_scratch { void* readers; int *order, *tmp; const uint8_t** ubase; uint32_t *ulen, *cnt; void* drec; uint64_t upd_cap, byte_cap; };
 size_t ygm_k_meta_bytes();
 size_t ygm_k_seq_reader_bytes();
 size_t ygm_k_drec_bytes();
+// (the SV / diff launchers: r->slot_total is where the exact kernel's packed region starts)
 int ygm_k_launch_doc(int mode, const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                     const uint32_t* docs, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                     uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap, hipStream_t s);
+                     const uint32_t* docs, uint32_t n_docs, uint32_t flags, const ygm_results* r, unsigned long long* lb, void* meta,
+                     hipStream_t s);
 size_t ygm_k_sv_table_bytes(uint32_t n_docs);
 int ygm_k_launch_ask_plan(const uint64_t* doc_off, uint32_t n_docs, const uint32_t* ask_doc, uint32_t n_asks, uint32_t* ask_ix,
                           uint64_t* ask_base, uint64_t* bs, hipStream_t s);
@@ -29,13 +47,11 @@ int ygm_k_launch_ask_status(const uint32_t* ask_ix, uint32_t n_asks, const int32
 int ygm_k_launch_ask_pending(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, uint32_t* list, unsigned int* n_out,
                              hipStream_t s);
 int ygm_k_launch_doc_lean_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                                 const uint32_t* ask_ix, const uint64_t* ask_base, uint32_t n_asks, uint8_t* out, uint64_t* out_off,
-                                 uint64_t* out_len, int32_t* status, void* meta, uint32_t* defer_list, uint64_t out_cap, uint8_t* tbl,
-                                 uint32_t* tbl_n, hipStream_t s);
+                                 const uint32_t* ask_ix, const uint64_t* ask_base, uint32_t n_asks, const ygm_results* r, void* meta,
+                                 uint32_t* defer_list, uint8_t* tbl, uint32_t* tbl_n, hipStream_t s);
 int ygm_k_launch_doc_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                            const uint32_t* docs, const uint32_t* ask_ix, uint64_t out_base, uint32_t n_docs, uint32_t flags, uint8_t* out,
-                            uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* lb, void* meta, uint64_t out_cap,
-                            hipStream_t s);
+                            const uint32_t* docs, const uint32_t* ask_ix, uint32_t n_docs, uint32_t flags, const ygm_results* r,
+                            unsigned long long* lb, void* meta, hipStream_t s);
 int ygm_k_launch_pend_split_g(const uint32_t* list, uint32_t P, const uint32_t* ask_ix, const uint8_t* ws, const uint64_t* out_off,
                               const uint8_t* sv, const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc,
                               uint8_t* dsv, int pass, hipStream_t s);
@@ -90,34 +106,27 @@ int ygm_k_launch_ver_cut_gather(const uint8_t* S, const uint64_t* s_off, const i
 int ygm_k_launch_pack(const uint8_t* src, const uint64_t* off, const uint64_t* len, const int32_t* status, uint32_t n, uint64_t* bsum,
                       uint8_t* dst, uint64_t* poff, hipStream_t s);
 int ygm_k_launch_doc_lean(int mode, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* doc_off, const uint8_t* sv_arena,
-                          uint64_t sv_bytes, const uint64_t* sv_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                          uint64_t* out_len, int32_t* status, void* meta, uint32_t* defer_list, uint64_t out_cap, uint8_t* tbl,
-                          uint32_t* tbl_n, hipStream_t s);
+                          uint64_t sv_bytes, const uint64_t* sv_off, uint32_t n_docs, uint32_t flags, const ygm_results* r, void* meta,
+                          uint32_t* defer_list, uint8_t* tbl, uint32_t* tbl_n, hipStream_t s);
 uint32_t ygm_k_lean_stage_bytes();
-uint32_t ygm_k_lean_no_idlen_flag();   // the `flags` bit of ygm_k_launch_merge_lean that switches the id-length parse off
-int ygm_k_launch_merge_lean(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, uint32_t flags,
-                            uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, void* meta_next,
-                            uint32_t* defer_list, uint64_t out_cap, hipStream_t s, const uint64_t* doc_off, const uint16_t* upd_len);
+uint32_t ygm_k_lean_no_idlen_flag();   // the lean_flags bit of ygm_k_launch_merge_lean that switches the id-length parse off
+// The merge tiers.  Each takes the input and the results, then what is its own.  n_dev: the device-side count of the
+// list (nullptr: the bound is the count); bound: the host's upper bound of it, which sizes the grid.
+int ygm_k_launch_merge_lean(const ygm_merge_in* in, const ygm_results* r, uint32_t n_docs, uint32_t lean_flags, void* meta_next,
+                            uint32_t* defer_list, const uint64_t* doc_off, const uint16_t* upd_len, hipStream_t s);
 int ygm_k_launch_big_wait(void* meta, uint32_t n_large, hipStream_t s);
 int ygm_k_launch_build_off(const uint64_t* doc_off, const uint16_t* upd_len, const uint32_t* doc_upd, const uint32_t* list, uint32_t n,
                            uint64_t* upd_off, hipStream_t s);
-int ygm_k_launch_merge_lean_wide(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, uint32_t n_docs, const uint32_t* list,
-                                 uint32_t n_list, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status,
-                                 void* meta, void* meta_next, uint32_t* defer_list, uint64_t out_cap, const uint16_t* upd_len,
-                                 hipStream_t s);
-int ygm_k_launch_merge_wave(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs,
-                            const unsigned int* n_dev, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
-                            int32_t* status, void* meta, uint32_t* defer_list, uint32_t* fb_list, uint64_t out_cap, hipStream_t s);
-int ygm_k_launch_route_big(const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs, const unsigned int* n_dev, uint32_t n_docs,
-                           uint32_t flags, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, uint32_t* fb_list, uint32_t* rest,
+int ygm_k_launch_merge_lean_wide(const ygm_merge_in* in, const ygm_results* r, uint32_t n_docs, const uint32_t* list, uint32_t n_list,
+                                 void* meta_next, uint32_t* defer_list, const uint16_t* upd_len, hipStream_t s);
+int ygm_k_launch_route_big(const ygm_merge_in* in, const ygm_results* r, const uint32_t* docs, const unsigned int* n_dev, uint32_t bound,
+                           uint32_t* fb_list, uint32_t* rest, hipStream_t s);
+int ygm_k_launch_merge_wave(const ygm_merge_in* in, const ygm_results* r, const uint32_t* docs, const unsigned int* n_dev, uint32_t bound,
+                            uint32_t* defer_list, uint32_t* fb_list, hipStream_t s);
+int ygm_k_launch_merge_fast(const ygm_merge_in* in, const ygm_results* r, const uint32_t* docs, const unsigned int* n_dev, uint32_t bound,
+                            uint32_t* fb_list, hipStream_t s);
+int ygm_k_launch_merge_seq(const ygm_merge_in* in, const ygm_results* r, const uint32_t* list, uint32_t n, const ygm_seq_scratch* scr,
                            hipStream_t s);
-int ygm_k_launch_merge_fast(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* docs,
-                            const unsigned int* n_dev, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
-                            int32_t* status, uint64_t slot_total, void* meta, uint32_t* fb_list, uint64_t out_cap, hipStream_t s);
-int ygm_k_launch_merge_seq(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list, uint32_t n_fb,
-                           uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta,
-                           void* readers, int* order, int* tmp, const uint8_t** ubase, uint32_t* ulen, uint64_t upd_cap,
-                           uint32_t* cnt, void* drec, uint64_t byte_cap, uint64_t slot_total, uint64_t out_cap, hipStream_t s);
 int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s);
 size_t ygm_k_v2_cols();
 int ygm_k_launch_v21(int pass, const uint8_t* arena, const uint64_t* upd_off, uint32_t n_upd, const uint32_t* doc_upd, uint32_t n_docs,
@@ -137,13 +146,10 @@ int ygm_k_launch_v2_status(const int32_t* ust, uint32_t n, int32_t* status, uint
 int ygm_k_launch_v2_lens(const uint64_t* off, const int32_t* st, uint32_t n, uint64_t* len, hipStream_t s);
 size_t ygm_k_big_blk_bytes();
 size_t ygm_k_big_rec_bytes();
-int ygm_k_launch_big_scan(const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list,
-                          uint32_t n_fb, uint32_t flags, void* scan, uint64_t fb_bytes, hipStream_t s);
-int ygm_k_launch_merge_big(int large, const uint8_t* arena, const uint64_t* upd_off, const uint32_t* doc_upd, const uint32_t* fb_list,
-                           uint32_t n_fb, const uint32_t* fbx, uint32_t n, uint32_t* up_list, uint32_t flags, uint8_t* out,
-                           uint64_t* out_off, uint64_t* out_len, int32_t* status, void* meta, uint32_t* fb2_list, void* blk,
-                           uint64_t blk_cap, void* rec, uint64_t rec_cap, uint64_t slot_total, uint64_t out_cap, void* scan,
-                           uint64_t fb_bytes, hipStream_t s);
+int ygm_k_launch_big_scan(const ygm_merge_in* in, const ygm_big_tier* big, hipStream_t s);   // (writes no results)
+// large = 0: the mid size, large = 1: the 16-wave size, over the big->fb_list indices in fbx[0, n)
+int ygm_k_launch_merge_big(int large, const ygm_merge_in* in, const ygm_results* r, const ygm_big_tier* big, const uint32_t* fbx, uint32_t n,
+                           hipStream_t s);
 size_t ygm_k_big_scan_bytes(uint32_t n_fb, uint64_t fb_bytes);
 void ygm_k_big_lists(void* scan, uint32_t n_fb, uint64_t fb_bytes, unsigned long long** cnt, uint32_t** llist, uint32_t** mlist);
 }

@@ -910,23 +910,21 @@ int ygm_k_launch_ask_status(const uint32_t* ask_ix, uint32_t n_asks, const int32
 }
 // the gather walker over n_asks asks (state-vector tables per ask: k_sv_table needs no change)
 int ygm_k_launch_doc_lean_gather(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* sv_arena, const uint64_t* sv_off,
-                                 const uint32_t* ask_ix, const uint64_t* ask_base, uint32_t n_asks, uint8_t* out, uint64_t* out_off,
-                                 uint64_t* out_len, int32_t* status, void* meta, uint32_t* defer_list, uint64_t out_cap, uint8_t* tbl,
-                                 uint32_t* tbl_n, hipStream_t s) {
+                                 const uint32_t* ask_ix, const uint64_t* ask_base, uint32_t n_asks, const ygm_results* r, void* meta,
+                                 uint32_t* defer_list, uint8_t* tbl, uint32_t* tbl_n, hipStream_t s) {
   if (n_asks == 0) return 0;
   const uint32_t waves = (n_asks + WAVE - 1) / WAVE, cap = device_cus() * 4u * YGM_DW_WPE1;
   const uint32_t grid = waves < cap ? waves : cap;
   hipLaunchKernelGGL(k_sv_table, dim3(waves), dim3(WAVE), 0, s, sv_arena, sv_off, n_asks, tbl, tbl_n);
   hipLaunchKernelGGL(k_doc_walk_gather, dim3(grid), dim3(WAVE), 0, s, arena, doc_off, (const uint8_t*)tbl, (const uint32_t*)tbl_n, n_asks,
-                     out, out_off, out_len, status, (DocMeta*)meta, defer_list, out_cap, ask_ix, ask_base);
+                     r->out, r->out_off, r->out_len, r->status, (DocMeta*)meta, defer_list, r->out_cap, ask_ix, ask_base);
   return ygm_launch_rc(__func__);
 }
 
 size_t ygm_k_sv_table_bytes(uint32_t n_docs) { return 144ull * n_docs + 64; }
 int ygm_k_launch_doc_lean(int mode, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* doc_off, const uint8_t* sv_arena,
-                          uint64_t sv_bytes, const uint64_t* sv_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                          uint64_t* out_len, int32_t* status, void* meta, uint32_t* defer_list, uint64_t out_cap, uint8_t* tbl,
-                          uint32_t* tbl_n, hipStream_t s) {
+                          uint64_t sv_bytes, const uint64_t* sv_off, uint32_t n_docs, uint32_t flags, const ygm_results* r, void* meta,
+                          uint32_t* defer_list, uint8_t* tbl, uint32_t* tbl_n, hipStream_t s) {
   (void)arena_bytes; (void)sv_bytes; (void)flags;   // segments are read in 64-byte chunks: 64 bytes of tail padding (ygm.h)
   if (n_docs == 0) return 0;
   const int n_cu = (int)device_cus();
@@ -939,11 +937,11 @@ int ygm_k_launch_doc_lean(int mode, const uint8_t* arena, uint64_t arena_bytes, 
   if (genv && atoi(genv) > 0 && (uint32_t)atoi(genv) < grid) grid = (uint32_t)atoi(genv);
   if (mode == 0)
     hipLaunchKernelGGL(k_doc_walk<0>, dim3(grid), dim3(WAVE), 0, s, arena, doc_off, (const uint8_t*)nullptr, (const uint32_t*)nullptr,
-                       n_docs, out, out_off, out_len, status, (DocMeta*)meta, defer_list, out_cap);
+                       n_docs, r->out, r->out_off, r->out_len, r->status, (DocMeta*)meta, defer_list, r->out_cap);
   else {
     hipLaunchKernelGGL(k_sv_table, dim3(waves), dim3(WAVE), 0, s, sv_arena, sv_off, n_docs, tbl, tbl_n);
     hipLaunchKernelGGL(k_doc_walk<1>, dim3(grid), dim3(WAVE), 0, s, arena, doc_off, (const uint8_t*)tbl, (const uint32_t*)tbl_n, n_docs,
-                       out, out_off, out_len, status, (DocMeta*)meta, defer_list, out_cap);
+                       r->out, r->out_off, r->out_len, r->status, (DocMeta*)meta, defer_list, r->out_cap);
   }
   return ygm_launch_rc(__func__);
 }
