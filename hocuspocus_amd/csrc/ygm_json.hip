@@ -23,17 +23,19 @@
 namespace ygm {
 
 // the batch's walker (ygm_json_batch.hpp): the ProseMirror JSON of one field, or the object of several
-template <bool FIELDS>
+template <bool FIELDS, bool FLOATS>
 struct JsonWalk {
-  template <class... A> static YDEV int doc(A&&... a) { return json::json_doc<FIELDS>(a...); }
-  template <class... A> static YDEV int run(A&&... a) { return json::json_run<FIELDS>(a...); }
+  template <class... A> static YDEV int doc(A&&... a) { return json::json_doc<FIELDS, FLOATS>(a...); }
+  template <class... A> static YDEV int run(A&&... a) { return json::json_run<FIELDS, FLOATS>(a...); }
 };
 
 // The batch and its arguments: docstage::json_batch.
 // FIELDS (ygm_json_fields_v1): names / name_off hold a field list per document and the JSON is the object of its
 // fields; staging, workspaces and the overflow route are the same, so the single-field kernel is its own instantiation
 // and carries none of the fields code.
-template <bool FIELDS>
+// FLOATS (a context opened with YGM_F_FLOATS): the walk's FLOATS form (json::Walk) -- instantiations of their own again,
+// so the two kernels of a context without the flag carry none of the number conversion and stay what they were.
+template <bool FIELDS, bool FLOATS>
 __global__ __launch_bounds__(docstage::NT) void k_json(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
                                                const uint8_t* __restrict__ names, const uint64_t* __restrict__ name_off, uint32_t n_docs,
                                                uint32_t flags, uint32_t kind, const uint4* __restrict__ cnt, const uint64_t* __restrict__ ws_off,
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(docstage::NT) void k_json(const uint8_t* __restrict
                                                int32_t* __restrict__ status, DocMeta* __restrict__ meta, uint32_t dpw, uint64_t base,
                                                uint64_t ovf_base, uint32_t* __restrict__ list, uint32_t n_list, uint32_t again) {
   __shared__ __attribute__((aligned(16))) uint8_t stg[docstage::STAGE + 16];
-  docstage::json_batch<JsonWalk<FIELDS>>(stg, arena, doc_off, names, name_off, n_docs, flags, kind, cnt, ws_off, ws, out_off, out_len, status,
+  docstage::json_batch<JsonWalk<FIELDS, FLOATS>>(stg, arena, doc_off, names, name_off, n_docs, flags, kind, cnt, ws_off, ws, out_off, out_len, status,
                                          meta, dpw, base, ovf_base, list, n_list, again);
 }
 
@@ -61,7 +63,7 @@ int ygm_k_launch_json(const uint8_t* arena, const uint64_t* doc_off, const uint8
   if (n == 0) return 0;
   const uint32_t dpw = docstage::docs_per_wave(0);
   const uint32_t g = (n + dpw - 1) / dpw;
-  auto k = fields ? k_json<true> : k_json<false>;
+  auto k = flags & F_FLOATS ? (fields ? k_json<true, true> : k_json<false, true>) : (fields ? k_json<true, false> : k_json<false, false>);
   hipLaunchKernelGGL(k, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off, ws,
                      out_off, out_len, status, (DocMeta*)meta, dpw, base, ovf_base, list, n_list, again ? 1u : 0u);
   return ygm_launch_rc(__func__);

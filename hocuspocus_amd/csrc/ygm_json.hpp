@@ -80,6 +80,11 @@ YDEV bool hashed_mark(const uint8_t* k, uint32_t n) {
   return true;
 }
 
+// FLOATS (a context opened with YGM_F_FLOATS; a compile-time option, so the other instantiations compile to what they
+// were): attribute numbers go through any_json's FLOATS form, and mark and embed values are copied without the
+// json_has_float refusal -- the state's parse has proven their numbers canonical (at most 15 significant digits, no
+// exponent: what JSON.stringify writes), or the document carries ST_NONCANON from it already.
+template <bool FLOATS>
 struct Walk {
   snap::Doc& D;
   snap::OutCap& o;
@@ -109,7 +114,7 @@ struct Walk {
   YDEV void mark(uint32_t i, bool& first) {
     const snap::Rng m = D.tx[i];
     if (hashed_mark(D.in + m.client, m.clock)) { D.fail(snap::ST_UNSUP); return; }
-    if (json_has_float(D.in + m.len, m.pad)) { D.fail(ST_NONCANON); return; }
+    if (!FLOATS && json_has_float(D.in + m.len, m.pad)) { D.fail(ST_NONCANON); return; }
     if (!first) o.b(',');
     first = false;
     lit(o, "{\"type\":"); quoted(o, D.in + m.client, m.clock); lit(o, ",\"attrs\":"); o.copy(D.in + m.len, m.pad); o.b('}');
@@ -150,7 +155,7 @@ struct Walk {
     o.b(first ? '{' : ',');
     first = false;
     quoted(o, D.in + e.key_off, e.key_len); o.b(':');
-    const int r = v2::any_json(c, o);
+    const int r = v2::any_json<snap::OutCap, false, FLOATS>(c, o);
     if (r) D.fail(r);
   }
   // ,"attrs":{...} of element type t when it has a live entry.  The entries go onto the free stack above sp (newest
@@ -196,11 +201,12 @@ struct Walk {
 // is inside of; what it needs on the way back (element or text) is read from the item again.
 // {"type":"doc","content":[...]} of root type `root` (a ty[] index), -1: the empty document.  D.tx and D.st are the
 // walk's alone and start empty: roots can be written one after another.
+template <bool FLOATS = false>
 YDEV void emit_root(snap::Doc& D, int32_t root, snap::OutCap& o) {
   using namespace snap;
   lit(o, "{\"type\":\"doc\",\"content\":[");
   if (root < 0) { lit(o, "]}"); return; }   // doc.getXmlFragment(name) of a name the update has no root for: an empty fragment
-  Walk W{D, o, 0};
+  Walk<FLOATS> W{D, o, 0};
   const uint64_t limit = (uint64_t)D.n_it + D.n_ty + 1u;
   uint64_t steps = 0;
   uint32_t sp = 0;
@@ -251,7 +257,7 @@ YDEV void emit_root(snap::Doc& D, int32_t root, snap::OutCap& o) {
         Cur c{D.in, u.c_start, u.c_end, 0, 0};
         uint32_t vl; const uint32_t vo = c.buf(vl);
         if (c.err) { D.fail(ST_MALFORMED); return; }
-        if (json_has_float(D.in + vo, vl)) { D.fail(ST_NONCANON); return; }
+        if (!FLOATS && json_has_float(D.in + vo, vl)) { D.fail(ST_NONCANON); return; }
         if (has) o.b(',');
         has = true;
         lit(o, "{\"type\":\"text\",\"text\":"); o.copy(D.in + vo, vl); W.marks(); o.b('}');
@@ -283,9 +289,10 @@ YDEV void emit_root(snap::Doc& D, int32_t root, snap::OutCap& o) {
   }
   lit(o, "]}");
 }
+template <bool FLOATS = false>
 YDEV void emit_json(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32_t kind, snap::OutCap& o) {
   (void)kind;
-  emit_root(D, snap::find_root(D, name, name_len), o);
+  emit_root<FLOATS>(D, snap::find_root(D, name, name_len), o);
 }
 
 // ---- every asked field of a document as one object (ygm_json_fields_v1):
@@ -356,6 +363,7 @@ struct Fields {
   }
 };
 
+template <bool FLOATS = false>
 YDEV void emit_fields(snap::Doc& D, const uint8_t* fl, uint32_t fn, snap::OutCap& o) {
   Fields F{D, fl, fn, 0};
   bool first = true, index_pass = true, any_prev = false;
@@ -390,7 +398,7 @@ YDEV void emit_fields(snap::Doc& D, const uint8_t* fl, uint32_t fn, snap::OutCap
     first = false;
     quoted(o, s, n); o.b(':');
     if (o.n >= JSON_MAX) { D.fail(ST_NOMEM); return; }
-    emit_root(D, root == -2 ? snap::find_root(D, s, n) : root, o);
+    emit_root<FLOATS>(D, root == -2 ? snap::find_root(D, s, n) : root, o);
     if (D.err) return;
     if (o.n >= JSON_MAX) { D.fail(ST_NOMEM); return; }
   }
@@ -401,8 +409,8 @@ YDEV void emit_fields(snap::Doc& D, const uint8_t* fl, uint32_t fn, snap::OutCap
 // the JSON of root `name` of in[0, n) over a workspace carved from ws, at most out_cap bytes at out.  ST_JSON_MORE:
 // out_len is the length a second run needs.  Pending structs / a pending delete set: the integrated part (ST_OK).
 // FIELDS: name[0, name_len) is a field list and the JSON the object of its fields (emit_fields); the state's own
-// status comes before the list's.
-template <bool FIELDS = false>
+// status comes before the list's.  FLOATS: the walk's FLOATS form (Walk).
+template <bool FIELDS = false, bool FLOATS = false>
 YDEV_NI int json_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, const uint8_t* name,
                      uint32_t name_len, uint32_t kind, uint8_t* out, uint32_t out_cap, uint32_t& out_len) {
   snap::Doc D;
@@ -413,19 +421,19 @@ YDEV_NI int json_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws,
   snap::OutCap o{out, 0, out_cap};
   if (FIELDS) {
     if (fields_check(name, name_len)) return ST_INVAL;
-    emit_fields(D, name, name_len, o);
-  } else emit_json(D, name, name_len, kind, o);
+    emit_fields<FLOATS>(D, name, name_len, o);
+  } else emit_json<FLOATS>(D, name, name_len, kind, o);
   if (D.err) return D.err;
   if (o.n >= JSON_MAX) return ST_NOMEM;
   out_len = o.n;
   return o.n > o.cap ? ST_JSON_MORE : ST_OK;
 }
 // document d's workspace from caps_of, its output region at the end (as text::text_doc)
-template <bool FIELDS = false>
+template <bool FIELDS = false, bool FLOATS = false>
 YDEV int json_doc(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, const uint8_t* name, uint32_t name_len,
                   uint32_t kind, uint32_t& out_off, uint32_t& out_len) {
   out_off = (uint32_t)snap::ws_core_bytes(k);
-  return json_run<FIELDS>(in, n, flags, ws, k, name, name_len, kind, ws + out_off, k.out, out_len);
+  return json_run<FIELDS, FLOATS>(in, n, flags, ws, k, name, name_len, kind, ws + out_off, k.out, out_len);
 }
 
 }  // namespace json

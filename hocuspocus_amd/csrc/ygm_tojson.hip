@@ -23,12 +23,16 @@
 namespace ygm {
 
 // the batch's walker (ygm_json_batch.hpp): toJSON of a Map, Array or Text root
+template <bool FLOATS>
 struct ToJsonWalk {
-  template <class... A> static YDEV int doc(A&&... a) { return tojson::tojson_doc(a...); }
-  template <class... A> static YDEV int run(A&&... a) { return tojson::tojson_run(a...); }
+  template <class... A> static YDEV int doc(A&&... a) { return tojson::tojson_doc<FLOATS>(a...); }
+  template <class... A> static YDEV int run(A&&... a) { return tojson::tojson_run<FLOATS>(a...); }
 };
 
 // The batch and its arguments: docstage::json_batch.
+// FLOATS (a context opened with YGM_F_FLOATS): the walk's FLOATS form (tojson::emit_tojson) -- an instantiation of its
+// own, so the kernel of a context without the flag carries none of the number conversion and stays what it was.
+template <bool FLOATS>
 __global__ __launch_bounds__(docstage::NT) void k_tojson(const uint8_t* __restrict__ arena, const uint64_t* __restrict__ doc_off,
                                                  const uint8_t* __restrict__ names, const uint64_t* __restrict__ name_off, uint32_t n_docs,
                                                  uint32_t flags, uint32_t kind, const uint4* __restrict__ cnt, const uint64_t* __restrict__ ws_off,
@@ -36,7 +40,7 @@ __global__ __launch_bounds__(docstage::NT) void k_tojson(const uint8_t* __restri
                                                  int32_t* __restrict__ status, DocMeta* __restrict__ meta, uint32_t dpw, uint64_t base,
                                                  uint64_t ovf_base, uint32_t* __restrict__ list, uint32_t n_list, uint32_t again) {
   __shared__ __attribute__((aligned(16))) uint8_t stg[docstage::STAGE + 16];
-  docstage::json_batch<ToJsonWalk>(stg, arena, doc_off, names, name_off, n_docs, flags, kind, cnt, ws_off, ws, out_off, out_len, status, meta,
+  docstage::json_batch<ToJsonWalk<FLOATS>>(stg, arena, doc_off, names, name_off, n_docs, flags, kind, cnt, ws_off, ws, out_off, out_len, status, meta,
                                    dpw, base, ovf_base, list, n_list, again);
 }
 
@@ -56,7 +60,8 @@ int ygm_k_launch_tojson(const uint8_t* arena, const uint64_t* doc_off, const uin
   if (n == 0) return 0;
   const uint32_t dpw = docstage::docs_per_wave(0);
   const uint32_t g = (n + dpw - 1) / dpw;
-  hipLaunchKernelGGL(k_tojson, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off,
+  auto k = flags & F_FLOATS ? k_tojson<true> : k_tojson<false>;
+  hipLaunchKernelGGL(k, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off,
                      ws, out_off, out_len, status, (DocMeta*)meta, dpw, base, ovf_base, list, n_list, again ? 1u : 0u);
   return ygm_launch_rc(__func__);
 }

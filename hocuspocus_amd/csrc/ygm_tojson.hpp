@@ -64,13 +64,16 @@ YDEV void emit_string(snap::Doc& D, int32_t t, snap::OutCap& o, uint64_t& steps,
   o.b('"');
 }
 
-// one ContentJSON element (a varString of JSON text) at c; undef: the word `undefined` (nothing is written)
+// one ContentJSON element (a varString of JSON text) at c; undef: the word `undefined` (nothing is written).
+// FLOATS (a context opened with YGM_F_FLOATS; a compile-time option as json::Walk's): the text is copied without the
+// float refusal -- its numbers are canonical by the state's parse -- and Any values take any_json's FLOATS form.
+template <bool FLOATS = false>
 YDEV void json_elem(snap::Doc& D, Cur& c, snap::OutCap& o, bool& undef) {
   uint32_t vl; const uint32_t vo = c.buf(vl);
   undef = false;
   if (c.err) { D.fail(ST_MALFORMED); return; }
   if (is_word(D.in + vo, vl, "undefined")) { undef = true; return; }
-  if (json::json_has_float(D.in + vo, vl)) { D.fail(ST_NONCANON); return; }
+  if (!FLOATS && json::json_has_float(D.in + vo, vl)) { D.fail(ST_NONCANON); return; }
   o.copy(D.in + vo, vl);
 }
 
@@ -120,6 +123,7 @@ YDEV void map_frame(snap::Doc& D, int32_t t, uint32_t& sp) {
 
 // The walk.  Every loop is bounded as emit_root's: each list item is visited once, each map entry written once and
 // each type returned from once in a well-formed document; a list that cycles exhausts the bound and ends in ST_UNSUP.
+template <bool FLOATS = false>
 YDEV void emit_tojson(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint32_t kind, snap::OutCap& o) {
   using namespace snap;
   const int32_t root = find_root(D, name, name_len);
@@ -162,8 +166,8 @@ YDEV void emit_tojson(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint
           if (has) o.b(',');
           has = true;
           quoted(o, D.in + e.key_off, e.key_len); o.b(':');
-          if (u.ref == 8) { const int r = v2::any_json<OutCap, true>(c, o); if (r) { D.fail(r); return; } }
-          else json_elem(D, c, o, undef);
+          if (u.ref == 8) { const int r = v2::any_json<OutCap, true, FLOATS>(c, o); if (r) { D.fail(r); return; } }
+          else json_elem<FLOATS>(D, c, o, undef);
           continue;
         }
       }
@@ -185,8 +189,8 @@ YDEV void emit_tojson(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint
           for (uint32_t j = 0; j < q.cnt; j++) {
             if (has) o.b(',');
             has = true;
-            if (u.ref == 8) { const int r = v2::any_json<OutCap, true>(c, o); if (r) { D.fail(r); return; } }
-            else { bool undef; json_elem(D, c, o, undef); if (undef) lit(o, "null"); }
+            if (u.ref == 8) { const int r = v2::any_json<OutCap, true, FLOATS>(c, o); if (r) { D.fail(r); return; } }
+            else { bool undef; json_elem<FLOATS>(D, c, o, undef); if (undef) lit(o, "null"); }
             if (c.err) { D.fail(ST_MALFORMED); return; }
             if (D.err) return;
             if (o.n >= JSON_MAX) { D.fail(ST_NOMEM); return; }
@@ -221,6 +225,7 @@ YDEV void emit_tojson(snap::Doc& D, const uint8_t* name, uint32_t name_len, uint
 // the JSON of root `name` of in[0, n) read as `kind`, over a workspace carved from ws, at most out_cap bytes at out.
 // ST_JSON_MORE: out_len is the length a second run needs.  Pending structs / a pending delete set: the integrated
 // part (ST_OK).
+template <bool FLOATS = false>
 YDEV_NI int tojson_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, const uint8_t* name,
                        uint32_t name_len, uint32_t kind, uint8_t* out, uint32_t out_cap, uint32_t& out_len) {
   snap::Doc D;
@@ -229,17 +234,18 @@ YDEV_NI int tojson_run(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* w
   D.load();
   if (D.err) return D.err;
   snap::OutCap o{out, 0, out_cap};
-  emit_tojson(D, name, name_len, kind, o);
+  emit_tojson<FLOATS>(D, name, name_len, kind, o);
   if (D.err) return D.err;
   if (o.n >= JSON_MAX) return ST_NOMEM;
   out_len = o.n;
   return o.n > o.cap ? ST_JSON_MORE : ST_OK;
 }
 // document d's workspace from caps_of, its output region at the end (as json::json_doc)
+template <bool FLOATS = false>
 YDEV int tojson_doc(const uint8_t* in, uint32_t n, uint32_t flags, uint8_t* ws, const snap::Caps& k, const uint8_t* name, uint32_t name_len,
                     uint32_t kind, uint32_t& out_off, uint32_t& out_len) {
   out_off = (uint32_t)snap::ws_core_bytes(k);
-  return tojson_run(in, n, flags, ws, k, name, name_len, kind, ws + out_off, k.out, out_len);
+  return tojson_run<FLOATS>(in, n, flags, ws, k, name, name_len, kind, ws + out_off, k.out, out_len);
 }
 
 }  // namespace tojson

@@ -46,6 +46,9 @@ constexpr uint32_t F_COMPAT_135 = 1u;
 // diff: every struct keeps its input's parentSub bit 0x20 (Item.write of an integrated item, Y@80416): the bytes
 // Y.encodeStateAsUpdate(doc, sv) writes for a document loaded from a normalized state (ygm_sync_step2_v1)
 constexpr uint32_t F_KEEP_SUB = 4u;
+// YGM_F_FLOATS: the stored-document JSON kernels write non-integer numbers (the launchers pick the FLOATS instantiations;
+// no device code reads the bit)
+constexpr uint32_t F_FLOATS = 8u;
 
 struct Cur {
   const uint8_t* p;

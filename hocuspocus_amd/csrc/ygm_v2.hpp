@@ -22,6 +22,7 @@
 // JavaScript's `arr[pos++] === undefined` arithmetic.
 #pragma once
 #include "ygm_v1.hpp"
+#include "ygm_dtoa.hpp"
 #ifdef YGM_HOST_BUILD
 static inline uint32_t __float_as_uint(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 static inline long long __double_as_longlong(double x) { long long u; memcpy(&u, &x, 8); return u; }
@@ -179,8 +180,12 @@ YDEV void js_quote(O& o, const uint8_t* s, uint32_t n) {
 // and an undefined array element (or the value itself) is null; a float32 / float64 tag that is not finite is null,
 // an integer of magnitude <= 2^53 its decimal digits (negative zero: 0), anything else ST_NONCANON (its shortest
 // round-trip decimal is not built); a Uint8Array (stringify writes an index-keyed object) is YGM_EUNSUPPORTED.
+// FLOATS (a context opened with YGM_F_FLOATS; a compile-time option in the same way): a float32 / float64 tag holding a
+// finite value is written as Number::toString writes it (ygm_dtoa.hpp: the shortest decimal that reads back, so 2^60 is
+// 1152921504606847000), a float32 widened exactly first; this replaces TOJSON's integer-only branch and, in the other
+// form, the refusal of these tags.  A value that is not finite stays what it was: null for TOJSON, ST_NONCANON otherwise.
 constexpr int ST_ANY_UNSUP = 9;   // YGM_EUNSUPPORTED
-template <class O, bool TOJSON = false>
+template <class O, bool TOJSON = false, bool FLOATS = false>
 YDEV_NI int any_json(Cur& c, O& o) {
   uint32_t rem[MAX_DEPTH + 1]; uint8_t obj[MAX_DEPTH + 1]; uint8_t first[MAX_DEPTH + 1];
   int d = 0; rem[0] = 1; obj[0] = 2; first[0] = 1;
@@ -205,10 +210,26 @@ YDEV_NI int any_json(Cur& c, O& o) {
     }
     const uint8_t tag = c.u8();
     if (c.err) break;
+    if constexpr (FLOATS) {
+      if (tag == 124 || tag == 123) {
+        const uint32_t nb = tag == 124 ? 4u : 8u;
+        if (c.end - c.pos < nb) return ST_MALFORMED;
+        uint64_t bits = 0;
+        for (uint32_t i = 0; i < nb; i++) bits = (bits << 8) | c.p[c.pos + i];
+        if (tag == 124) bits = dtoa::widen_f32((uint32_t)bits);
+        c.pos += nb;
+        if (!dtoa::finite(bits)) {
+          if constexpr (TOJSON) { o.b('n'); o.b('u'); o.b('l'); o.b('l'); continue; }
+          return ST_NONCANON;
+        }
+        dtoa::write(o, bits);
+        continue;
+      }
+    }
     if constexpr (TOJSON) {
       if (tag == 127) { o.b('n'); o.b('u'); o.b('l'); o.b('l'); continue; }
       if (tag == 116) return ST_ANY_UNSUP;
-      if (tag == 124 || tag == 123) {
+      if (!FLOATS && (tag == 124 || tag == 123)) {
         const uint32_t nb = tag == 124 ? 4u : 8u;
         if (c.end - c.pos < nb) return ST_MALFORMED;
         const double x = tag == 124 ? (double)be_f32(c.p + c.pos) : be_f64(c.p + c.pos);

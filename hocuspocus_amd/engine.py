@@ -28,6 +28,7 @@ STATUS_NAMES = {0: "OK", 1: "EMALFORMED", 2: "ERANGE", 3: "ENONCANON", 4: "ESURR
                 6: "ENOMEM", 7: "EDEVICE", 8: "EINVAL", 9: "EUNSUPPORTED"}
 F_COMPAT_135 = 1
 F_FORCE_SEQ = 2
+F_FLOATS = 8      # YGM_F_FLOATS: the JSON calls write non-integer numbers (off by default: stored expectations do not move)
 DOC_NO_GC = 1   # YGM_DOC_NO_GC: a document's option byte, the document is a Y.Doc({gc: false})
 TEXT_FLAT, TEXT_DEEP = 0, 1   # YGM_TEXT_FLAT / YGM_TEXT_DEEP: the modes of ygm_text_v1
 JSON_PROSEMIRROR = 0          # YGM_JSON_PROSEMIRROR: the one kind of ygm_json_v1
@@ -295,8 +296,8 @@ class DeviceResult:
 class Engine:
     """One engine context on one GPU (not thread-safe; one batch in flight)."""
 
-    def __init__(self, device: int = 0, compat135: bool = False, force_seq: bool = False):
-        flags = (F_COMPAT_135 if compat135 else 0) | (F_FORCE_SEQ if force_seq else 0)
+    def __init__(self, device: int = 0, compat135: bool = False, force_seq: bool = False, floats: bool = False):
+        flags = (F_COMPAT_135 if compat135 else 0) | (F_FORCE_SEQ if force_seq else 0) | (F_FLOATS if floats else 0)
         ctx = ctypes.c_void_p()
         _check(lib().ygm_open(device, flags, ctypes.byref(ctx)))
         self._ctx = ctx

@@ -55,6 +55,18 @@ extern "C" {
 #define YGM_F_COMPAT_135 1u   /* delete-set clients in first-seen order; lone surrogate -> error */
 #define YGM_F_FORCE_SEQ 2u    /* route every merge through the exact sequential kernel (testing) */
 #define YGM_F_KEEP_SUB 4u     /* internal to ygm_sync_step2_v1: diffs keep each struct's parentSub bit (0x20) */
+#define YGM_F_FLOATS 8u       /* opt-in, given to ygm_open: ygm_json_v1, ygm_json_fields_v1, ygm_tojson_v1 (their _device
+                                 forms and the version forms built on them) write the numbers they refuse without it -- a
+                                 finite float32 / float64 of a ContentAny as Number.prototype.toString writes it (the
+                                 shortest decimal that reads back as the same double, JavaScript's layout: 103.5, 1e+21,
+                                 1.5e-7; an integer above 2^53 likewise, 2^60 is 1152921504606847000; a float32 widened
+                                 exactly first, 0.1f is 0.10000000149011612), and non-integer numbers inside ContentJSON,
+                                 format and embed values as the canonical text they already are.  Still refused with the
+                                 flag: JSON text holding a number of more than 15 significant digits or with an exponent
+                                 (the state's parse calls it not canonical: YGM_ENONCANON), BigInt, Uint8Array, the
+                                 undefined rules, __proto__, hashed mark names.  Without the flag every call returns what
+                                 it returned before the flag existed; every other entry point ignores it
+                                 (ygm_convert_v2_to_v1 keeps its refusal). */
 #define YGM_F_SNAP_STATE 16u  /* internal to ygm_contains_v1: such a state's snapshot is its integrated part alone
                                  (Y.snapshot(doc): the store's state vector and delete set) */
 #define YGM_F_SNAP_NOGC 32u   /* internal to ygm_version_restore_v1: every document of the batch is snapshotted as a
@@ -233,6 +245,11 @@ int ygm_text_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, 
  * states / state_off / names / name_off, tail padding, packing and the other statuses as ygm_text_v1.  A kind other
  * than YGM_JSON_PROSEMIRROR is YGM_EINVAL for the call (toJSON of Map and Array roots: ygm_tojson_v1).  No options form:
  * the JSON depends neither on YGM_F_COMPAT_135 nor on garbage collection.
+ * With YGM_F_FLOATS (ygm_open): the first YGM_ENONCANON row above does not apply -- an attribute's finite float32 /
+ * float64 is written as Number.prototype.toString writes it, and a mark or embed value holding a non-integer number of
+ * at most 15 significant digits and no exponent is copied as it stands; an attribute that is not finite (JSON.stringify
+ * writes null, the conversion refuses) and the second row (more than 15 significant digits, or an exponent) stay
+ * YGM_ENONCANON.
  * (Replaces packages/transformer/src/Prosemirror.ts:26: transformer.fromYdoc(document, fieldName) with one field
  * name, what a REST read of one field sends.  The body of a change webhook is ygm_json_fields_v1 below.) */
 #define YGM_JSON_PROSEMIRROR 0u
@@ -268,6 +285,7 @@ int ygm_json_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, 
  * The object is larger than any of its roots: the second run of ygm_json_v1 covers it in the same way.  states /
  * state_off, tail padding, packing and the other statuses as ygm_json_v1; a kind other than YGM_JSON_PROSEMIRROR is
  * YGM_EINVAL for the call.  No options form: neither YGM_F_COMPAT_135 nor garbage collection changes the result.
+ * With YGM_F_FLOATS (ygm_open) every field is written as ygm_json_v1 writes it with the flag.
  * (Replaces packages/extension-webhook/src/index.ts:119 -- the `document` of every change webhook,
  * transformer.fromYdoc(data.document) -- and packages/transformer/src/Prosemirror.ts:29-39.) */
 int ygm_json_fields_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *state_off, const uint8_t *fields,
@@ -319,6 +337,11 @@ int ygm_json_fields_v1(ygm_ctx *ctx, const uint8_t *states, const uint64_t *stat
  * changes the result.
  * Out of scope: the shortest-round-trip decimal of non-integer doubles; XML strings of nested Xml types; toDelta; a
  * multi-root object form.
+ * With YGM_F_FLOATS (ygm_open): the YGM_ENONCANON row above does not apply -- every finite float32 / float64 of an Any
+ * is written as Number.prototype.toString writes it (a non-integer, an integer above 2^53; a float32 widened exactly
+ * first), and a ContentJSON element holding a non-integer number of at most 15 significant digits and no exponent is
+ * copied as it stands; one with more digits or an exponent stays YGM_ENONCANON by the state's parse.  A number of up
+ * to 25 bytes stands where 9 stood in the state: the second run covers it.
  * (Replaces no single reference interface: the batched form of a custom webhook transformer's `fromYdoc`,
  * extension-webhook/src/index.ts:27-31,119.) */
 #define YGM_TOJSON_MAP 0u   /* JSON.stringify(doc.getMap(name).toJSON())   */

@@ -15,7 +15,14 @@ export type DocOptionList = ArrayLike<number | boolean | DocOptions> | Uint8Arra
 
 /** the fields of a document to serialize: null, undefined or [] for every key of doc.share, else their names */
 export type FieldList = (string | Uint8Array)[] | null | undefined
-export interface GpuEngineOptions { device?: number; compat135?: boolean; batchWindowMs?: number; maxBatchDocs?: number }
+export interface GpuEngineOptions {
+  device?: number; compat135?: boolean; batchWindowMs?: number; maxBatchDocs?: number
+  /** YGM_F_FLOATS (default false): jsonMany / jsonFieldsMany / toJsonMany, and jsonOf / versionJson / sharedJsonOf /
+   *  versionSharedJson of the extension, write non-integer numbers (103.5, 1.5e-7, integers above 2^53) as JSON.stringify
+   *  does instead of refusing the document with ENONCANON.  Still refused: JSON text with a number of more than 15
+   *  significant digits or an exponent, BigInt, Uint8Array, __proto__, hashed mark names. */
+  floats?: boolean
+}
 
 export declare class GpuEngine {
   constructor (opts?: GpuEngineOptions)

@@ -181,11 +181,13 @@ const OPS = {
 
 class GpuEngine {
   /**
-   * @param {{device?: number, compat135?: boolean, batchWindowMs?: number, maxBatchDocs?: number}} [opts]
+   * @param {{device?: number, compat135?: boolean, floats?: boolean, batchWindowMs?: number, maxBatchDocs?: number}} [opts]
+   *   floats (YGM_F_FLOATS, off by default): jsonMany / jsonFieldsMany / toJsonMany write non-integer numbers as
+   *   JSON.stringify does, where they refuse the document (ENONCANON) without it
    */
   constructor (opts = {}) {
     this.device = opts.device || 0
-    this.flags = opts.compat135 ? 1 : 0
+    this.flags = (opts.compat135 ? 1 : 0) | (opts.floats ? 8 : 0)
     this.batchWindowMs = opts.batchWindowMs === undefined ? 2 : opts.batchWindowMs
     this.maxBatchDocs = opts.maxBatchDocs || 65536
     this.handle = loadAddon().open(this.device, this.flags)

@@ -45,7 +45,7 @@ class DocumentStore {
 class GpuMerge {
   /**
    * @param {{store?: DocumentStore|Function, fetch?: Function, device?: number, Y?: any,
-   *          engine?: GpuEngine, batchWindowMs?: number, maxBatchDocs?: number, compat135?: boolean,
+   *          engine?: GpuEngine, batchWindowMs?: number, maxBatchDocs?: number, compat135?: boolean, floats?: boolean,
    *          onRefused?: 'reference'|'throw', normalize?: boolean, normalizeMaxBytes?: number,
    *          gc?: 'document'|boolean}} configuration
    *   gc ('document' by default): whether the normalized snapshot and the responder's / fan-out's replies are
@@ -105,7 +105,7 @@ class GpuMerge {
   _engine () {
     if (!this.engine) {
       const c = this.configuration
-      const opts = { device: c.device || 0, compat135: c.compat135, batchWindowMs: c.batchWindowMs, maxBatchDocs: c.maxBatchDocs }
+      const opts = { device: c.device || 0, compat135: c.compat135, floats: c.floats, batchWindowMs: c.batchWindowMs, maxBatchDocs: c.maxBatchDocs }
       // several GPUs of the node: documents sharded by fnv1a64(documentName) mod N (SURVEY.md §8e)
       this.engine = c.devices && c.devices.length > 1 ? new GpuEnginePool({ ...opts, devices: c.devices }) : new GpuEngine(opts)
     }

@@ -34,18 +34,22 @@ const ContentAny = (() => {   // the content constructor, from a document of the
 })()
 
 class Refuse extends Error { constructor (st) { super('refused ' + st); this.st = st } }
+// the refusal table of a context opened with YGM_F_FLOATS (tools/floats_corpus.js turns it on; this tool's own fixtures
+// are made with it off)
+let FLOATS = false
+const setFloats = on => { FLOATS = !!on }
 
 // a value that came from JSON text (a format or embed value): numbers JSON.stringify writes as plain integers of at
 // most 15 significant digits (more are not canonical to the engine's JSON check, as in the snapshot)
 const sigDigits = v => String(Math.abs(v)).replace(/^0\./, '').replace(/\./, '').replace(/^0+/, '').replace(/0+$/, '').length
 function checkJson (v) {
-  if (typeof v === 'number') { if (!Number.isInteger(v) || /e/.test(String(v)) || sigDigits(v) > 15) throw new Refuse(3) } else if (Array.isArray(v)) v.forEach(checkJson)
+  if (typeof v === 'number') { if ((!FLOATS && !Number.isInteger(v)) || /e/.test(String(v)) || sigDigits(v) > 15) throw new Refuse(3) } else if (Array.isArray(v)) v.forEach(checkJson)
   else if (v !== null && typeof v === 'object') Object.keys(v).forEach(k => checkJson(v[k]))
 }
 // a value that came from an Any (an attribute): what the engine's Any -> JSON conversion writes
 function checkAny (v) {
   if (typeof v === 'bigint') throw new Refuse(1)
-  if (typeof v === 'number') { if (!Number.isInteger(v) || Math.abs(v) > 2147483647) throw new Refuse(3) } else if (v === undefined || v instanceof Uint8Array) throw new Refuse(3)
+  if (typeof v === 'number') { if (FLOATS ? !Number.isFinite(v) : (!Number.isInteger(v) || Math.abs(v) > 2147483647)) throw new Refuse(3) } else if (v === undefined || v instanceof Uint8Array) throw new Refuse(3)
   else if (Array.isArray(v)) v.forEach(checkAny)
   else if (v !== null && typeof v === 'object') Object.keys(v).forEach(k => checkAny(v[k]))
 }
@@ -390,4 +394,4 @@ if (require.main === module && process.argv[2] === '--time') {
   console.log(JSON.stringify({ counts, edges: edge.length, overflow_state_bytes: ovf.state.length / 2, overflow_caps_out: capsOut, overflow_json_bytes: ovf.roots[0][2].length / 2 }))
 }
 
-module.exports = { serialize, jsonOf, rootsOf, Refuse }
+module.exports = { serialize, jsonOf, rootsOf, Refuse, setFloats, edges }

@@ -5,7 +5,8 @@
 // protocol is jsondev.cpp's: a first run into a region of exactly Caps::out bytes, a second over a fresh workspace
 // into a region of exactly the recorded length (reran = 1).  The state and the list are allocations of their exact
 // sizes (the state with the 64 readable bytes the arenas promise), so a read past a list is a sanitizer's finding.
-//     jsonfieldsdev in.bin out.bin [flags]       (flags: 1 = 13.5 compat; the JSON does not depend on it)
+//     jsonfieldsdev [--floats] in.bin out.bin [flags]   (flags: 1 = 13.5 compat; the JSON does not depend on it.
+//                                          --floats: the walk as a context opened with YGM_F_FLOATS runs it)
 // A sanitizer build of this program (g++ -fsanitize=address,undefined) over the whole fixture is where the field
 // decoder's and the walk's bounds are checked.
 #define YGM_HOST_BUILD 1
@@ -25,6 +26,9 @@ static bool rd(FILE* f, std::vector<uint8_t>& v, uint32_t pad) {
 }
 
 int main(int argc, char** argv) {
+  bool floats = false;   // --floats, anywhere: the FLOATS instantiation (a context opened with YGM_F_FLOATS)
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--floats")) { floats = true; for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1]; argc--; i--; }
   if (argc < 3) { fprintf(stderr, "usage: jsonfieldsdev in.bin out.bin [flags]\n"); return 2; }
   const uint32_t flags = argc > 3 ? (uint32_t)atoi(argv[3]) : 0u;
   FILE* f = fopen(argv[1], "rb"); FILE* g = fopen(argv[2], "wb");
@@ -42,14 +46,14 @@ int main(int argc, char** argv) {
       uint32_t S, Dn, C; ygm::snap::count_doc(st.data(), len, flags, S, Dn, C);
       const ygm::snap::Caps k = ygm::snap::caps_of(S, Dn, C, len);
       std::vector<uint8_t> ws((size_t)ygm::snap::ws_core_bytes(k), 0), first((size_t)k.out, 0), big;
-      gs = ygm::json::json_run<true>(st.data(), len, flags, ws.data(), k, list.data(), fl, 0u, first.data(), k.out, ol);
+      gs = (floats ? ygm::json::json_run<true, true> : ygm::json::json_run<true, false>)(st.data(), len, flags, ws.data(), k, list.data(), fl, 0u, first.data(), k.out, ol);
       if (gs == 0) res.assign(first.begin(), first.begin() + ol);
       if (gs == ygm::json::ST_JSON_MORE) {
         const uint32_t need = ol;
         reran = 1;
         big.assign((size_t)need, 0);   // (exactly the recorded length: a sanitizer sees one byte more)
         std::fill(ws.begin(), ws.end(), 0);
-        gs = ygm::json::json_run<true>(st.data(), len, flags, ws.data(), k, list.data(), fl, 0u, big.data(), need, ol);
+        gs = (floats ? ygm::json::json_run<true, true> : ygm::json::json_run<true, false>)(st.data(), len, flags, ws.data(), k, list.data(), fl, 0u, big.data(), need, ol);
         if (gs != 0 || ol != need) { fprintf(stderr, "ask %u: the rerun gave status %d, %u bytes for %u recorded\n", i, gs, ol, need); return 1; }
         res = big;
       }

@@ -5,8 +5,9 @@
 // output region of Caps::out bytes (an allocation of its own, of exactly that size), or of `cap` bytes when a cap is
 // forced; a document whose JSON does not fit (ST_JSON_MORE) runs again over a fresh workspace into a region of exactly
 // the recorded length (reran = 1), and must then give that length.
-//     tojsondev in.bin out.bin [flags [cap]]   (flags: 1 = 13.5 compat; the JSON does not depend on it.  cap > 0: the
-//                                               first run's region is min(cap, Caps::out) bytes)
+//     tojsondev [--floats] in.bin out.bin [flags [cap]]   (flags: 1 = 13.5 compat; the JSON does not depend on it.  cap > 0:
+//                                               the first run's region is min(cap, Caps::out) bytes.  --floats: the
+//                                               walk as a context opened with YGM_F_FLOATS runs it)
 // A sanitizer build of this program (g++ -fsanitize=address,undefined) over the whole fixture is where the walk's
 // bounds are checked.
 #define YGM_HOST_BUILD 1
@@ -26,6 +27,9 @@ static bool rd(FILE* f, std::vector<uint8_t>& v, uint32_t pad) {
 }
 
 int main(int argc, char** argv) {
+  bool floats = false;   // --floats, anywhere: the FLOATS instantiation (a context opened with YGM_F_FLOATS)
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--floats")) { floats = true; for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1]; argc--; i--; }
   if (argc < 3) { fprintf(stderr, "usage: tojsondev in.bin out.bin [flags [cap]]\n"); return 2; }
   const uint32_t flags = argc > 3 ? (uint32_t)atoi(argv[3]) : 0u;
   const uint32_t cap = argc > 4 ? (uint32_t)atoi(argv[4]) : 0u;
@@ -45,14 +49,14 @@ int main(int argc, char** argv) {
       const uint32_t oc = cap && cap < k.out ? cap : k.out;
       // (fresh allocations per ask, each of its exact size: no capacity left over from a larger document)
       std::vector<uint8_t> ws((size_t)ygm::snap::ws_core_bytes(k), 0), first((size_t)oc, 0), big;
-      gs = ygm::tojson::tojson_run(st.data(), len, flags, ws.data(), k, name.data(), nl, kind, first.data(), oc, ol);
+      gs = (floats ? ygm::tojson::tojson_run<true> : ygm::tojson::tojson_run<false>)(st.data(), len, flags, ws.data(), k, name.data(), nl, kind, first.data(), oc, ol);
       if (gs == 0) res.assign(first.begin(), first.begin() + ol);
       if (gs == ygm::json::ST_JSON_MORE) {
         const uint32_t need = ol;
         reran = 1;
         big.assign((size_t)need, 0);   // (exactly the recorded length: a sanitizer sees one byte more)
         std::fill(ws.begin(), ws.end(), 0);
-        gs = ygm::tojson::tojson_run(st.data(), len, flags, ws.data(), k, name.data(), nl, kind, big.data(), need, ol);
+        gs = (floats ? ygm::tojson::tojson_run<true> : ygm::tojson::tojson_run<false>)(st.data(), len, flags, ws.data(), k, name.data(), nl, kind, big.data(), need, ol);
         if (gs != 0 || ol != need) { fprintf(stderr, "ask %u: the rerun gave status %d, %u bytes for %u recorded\n", i, gs, ol, need); return 1; }
         res = big;
       }

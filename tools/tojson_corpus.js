@@ -32,11 +32,15 @@ const SESSIONS = 160
 const ESCAPES = 'q" b\\ \b\f\n\r\t \u0001\u001f \u007f \u2028 😀'   // (the string of json_v135's "values of every kind")
 
 class Refuse extends Error { constructor (st) { super('refused ' + st); this.st = st } }
+// the refusal table of a context opened with YGM_F_FLOATS (tools/floats_corpus.js turns it on; this tool's own fixture
+// is made with it off)
+let FLOATS = false
+const setFloats = on => { FLOATS = !!on }
 
 // ---- does the engine refuse the root?  (include/ygm.h's table, in the order of the engine's walk)
 function checkAny (v) {
   if (typeof v === 'bigint') throw new Refuse(1)
-  if (typeof v === 'number') { if (Number.isFinite(v) && (!Number.isInteger(v) || Math.abs(v) > 9007199254740992)) throw new Refuse(3) } else if (v instanceof Uint8Array) throw new Refuse(9)
+  if (typeof v === 'number') { if (!FLOATS && Number.isFinite(v) && (!Number.isInteger(v) || Math.abs(v) > 9007199254740992)) throw new Refuse(3) } else if (v instanceof Uint8Array) throw new Refuse(9)
   else if (Array.isArray(v)) v.forEach(checkAny)
   else if (v !== null && typeof v === 'object') Object.keys(v).forEach(k => checkAny(v[k]))
 }
@@ -211,11 +215,11 @@ function mulberry32 (a) {
 }
 const KEYS = ['title', 'id', 'x', 'y', 'color', 'done', 'tags', 'meta', '0', '7', '12', 'updatedAt', 'owner', 'k"q']
 const WORDS = ['alpha', 'beta', 'gamma "quoted"', 'delta\n', 'épsilon', 'zeta😀', 'eta\\', 'theta', 'a longer piece of text for a card body', '']
-function randomSession (seed) {
+function randomSession (seed, forceFloaty) {   // forceFloaty: every session holds non-integer numbers (tools/floats_corpus.js)
   const rnd = mulberry32(seed)
   const int = n => Math.floor(rnd() * n)
   const pick = a => a[int(a.length)]
-  const floaty = rnd() < 0.05   // (a session with a non-integer number: its roots are refused where it is reached)
+  const floaty = rnd() < 0.05 || !!forceFloaty   // (a session with a non-integer number: its roots are refused where it is reached)
   const scalar = () => {
     const r = int(10)
     if (r < 3) return pick(WORDS)
@@ -360,4 +364,4 @@ if (require.main === module && process.argv[2] === '--time') {
   console.log(JSON.stringify({ counts, edges: edge.length }))
 }
 
-module.exports = { ask, Refuse, edges, randomSession }
+module.exports = { ask, Refuse, edges, randomSession, setFloats, MAP, ARRAY, TEXT }
