@@ -99,10 +99,24 @@ struct ygm_ctx {
   DevBuf arena, offs, docs, sv_arena, sv_offs, opt;   // (opt: the chunk's per-document option bytes, *_opts_v1)
   // device outputs + state
   DevBuf out, out_off, out_len, status, lb, meta, fb_list, defer_list, defer2_list, defer_w_list, route_list;
-  // where a call's results go: the output buffers as prep_outputs left them, the slot region's and the arena's size
-  ygm_results results(uint64_t slot_total, uint64_t out_cap) const {
-    return {out.as<uint8_t>(), out_off.as<uint64_t>(), out_len.as<uint64_t>(), status.as<int32_t>(), slot_total, out_cap};
+  // where a call's results go: the per-document buffers as prep_outputs (or ws_begin) left them, over an output arena
+  // (`out` for the merge and the walkers), the slot region's and the arena's size
+  ygm_results results_in(const DevBuf& arena, uint64_t slot_total, uint64_t out_cap) const {
+    return {arena.as<uint8_t>(), out_off.as<uint64_t>(), out_len.as<uint64_t>(), status.as<int32_t>(), slot_total, out_cap};
   }
+  ygm_results results(uint64_t slot_total, uint64_t out_cap) const { return results_in(out, slot_total, out_cap); }
+  // ... of a workspace batch, whose bytes lie in sn_ws (the flat tier's slots first); the pending documents' launches
+  // read their PendHdr records back through it
+  ygm_results ws_results(uint64_t slot_total = 0) const { return results_in(sn_ws, slot_total, sn_ws.cap); }
+  // ... of a version cut: per-unit slots in the `total` bytes of vr_out
+  ygm_results vr_results(uint64_t total) const {
+    return {vr_out.as<uint8_t>(), vr_off.as<uint64_t>(), vr_len.as<uint64_t>(), vr_st.as<int32_t>(), total, total};
+  }
+  ygm_packed packed() const { return {s2_data.as<uint8_t>(), s2_off.as<uint64_t>(), s2_st.as<int32_t>()}; }   // (after pack_snapshots)
+  // step2 of pending documents: their parts as step2_pending_split placed them
+  ygm_pend_parts pend_parts() const { return {pq_off.as<uint64_t>(), pq_a.as<uint8_t>(), pq_b.as<uint8_t>(), pq_c.as<uint8_t>(), pq_s.as<uint8_t>()}; }
+  // the pending documents' three-update batch (arena: false in the planning pass, which sizes it)
+  ygm_pend_batch pend_batch(bool arena) const { return {pn_off.as<uint64_t>(), pn_du.as<uint32_t>(), arena ? pn_arena.as<uint8_t>() : nullptr}; }
   Meta* h_meta = nullptr;  // pinned read-back of the per-launch counters
   int mslot = 0;           // counter slot of the next merge launch
   void* meta_slot(int i) const { return (uint8_t*)meta.p + (size_t)i * sizeof(Meta); }
@@ -592,6 +606,7 @@ static int run_doc_kernel(ygm_ctx* c, int mode, const uint8_t* d_arena, uint64_t
   return YGM_OK;
 }
 
+static ygm_batch_out batch_out(const ygm_device_result& r) { return {r.data, r.off, r.len, r.status}; }   // (for a later launch)
 // The pending documents' three-update batch (c->pn_arena / pn_off / pn_du, `total` bytes) merged on the child context
 // c->pend_ctx; the merged bytes appended to `dst` at `used` and the documents' places, lengths and statuses written
 // (k_pend_fix; pst: statuses decided before the merge, nullable)
@@ -599,15 +614,16 @@ static int pend_merge_place(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t tota
                             uint64_t& data_bytes, unsigned long long& payload, const uint32_t* list = nullptr) {
   if (!list) list = c->sn_pend.as<uint32_t>();   // (the shared-state step2: its list of asks)
   if (!c->pend_ctx) { const int e = ygm_open(c->device, c->flags, &c->pend_ctx); if (e) return e; }
-  int e = ygm_merge_v1_device_async(c->pend_ctx, c->pn_arena.as<uint8_t>(), total, c->pn_off.as<uint64_t>(), c->pn_du.as<uint32_t>(), 3 * P, P, s);
+  const ygm_pend_batch b = c->pend_batch(true);
+  int e = ygm_merge_v1_device_async(c->pend_ctx, b.dst, total, b.upd_off, b.doc_upd, 3 * P, P, s);
   ygm_device_result r;
   if (!e) e = ygm_merge_v1_device_finish(c->pend_ctx, &r);
   if (e) return e;
   if (!dst.ensure(used + r.data_bytes + 64, used, s)) return YGM_ENOMEM;
   if (r.data_bytes) HIPCHK(hipMemcpyAsync(dst.as<uint8_t>() + used, r.data, r.data_bytes, hipMemcpyDeviceToDevice, s));
-  if (ygm_k_launch_pend_fix(list, P, r.off, r.len, r.status, pst, used, c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
-                            c->status.as<int32_t>(), s))
-    return YGM_EDEVICE;
+  const ygm_batch_out merged = batch_out(r);
+  const ygm_results res = c->results_in(dst, 0, dst.cap);
+  if (ygm_k_launch_pend_fix(list, P, &merged, pst, used, &res, s)) return YGM_EDEVICE;
   data_bytes = used + r.data_bytes;
   payload += r.payload_bytes;
   c->stats.docs_pending += P;
@@ -618,17 +634,16 @@ static int pend_merge_place(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t tota
 // k_pend_copy) and merged by pend_merge_place, which appends the merged bytes to the snapshot's output region at `used`.
 static int snap_resolve_pending(ygm_ctx* c, hipStream_t s, uint32_t P, uint64_t used, uint64_t& data_bytes, unsigned long long& payload) {
   if (!c->pn_off.ensure(8ull * (3ull * P + 1) + 16) || !c->pn_du.ensure(4ull * (P + 1) + 16)) return YGM_ENOMEM;
-  if (ygm_k_launch_pend_plan(c->sn_pend.as<uint32_t>(), P, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->pn_off.as<uint64_t>(),
-                             c->pn_du.as<uint32_t>(), s))
-    return YGM_EDEVICE;
+  ygm_pend_batch b = c->pend_batch(false);
+  const ygm_results rec = c->ws_results();   // (the documents' records)
+  if (ygm_k_launch_pend_plan(c->sn_pend.as<uint32_t>(), P, rec.out, rec.out_off, &b, s)) return YGM_EDEVICE;
   int e = 0;
-  const uint64_t total = read_u64(c, s, c->pn_off.as<uint64_t>() + 3ull * P, e);
+  const uint64_t total = read_u64(c, s, b.upd_off + 3ull * P, e);
   if (e) return e;
   if (!c->pn_arena.ensure(total + 64)) return YGM_ENOMEM;
   HIPCHK(hipMemsetAsync(c->pn_arena.as<uint8_t>() + total, 0, 64, s));   // (the merge kernels' tail padding)
-  if (ygm_k_launch_pend_copy(c->sn_pend.as<uint32_t>(), P, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->pn_off.as<uint64_t>(),
-                             c->pn_arena.as<uint8_t>(), s))
-    return YGM_EDEVICE;
+  b = c->pend_batch(true);
+  if (ygm_k_launch_pend_copy(c->sn_pend.as<uint32_t>(), P, rec.out, rec.out_off, &b, s)) return YGM_EDEVICE;
   return pend_merge_place(c, s, P, total, nullptr, c->sn_ws, used, data_bytes, payload);
 }
 
@@ -644,6 +659,11 @@ struct WsBatch {
   uint64_t total = 0;       // bytes of the workspaces after it (ws_plan)
   uint64_t flat_pay = 0, flat_docs = 0, flat_first = 0;   // flat tier: payload bytes, documents claimed, by launch 0
   const uint8_t* claim() const { return slot_total ? c->sn_claim.as<uint8_t>() : nullptr; }
+  // the launch arguments (ygm_launch.hpp): the batch's documents under the call's flags, the workspaces (after ws_plan,
+  // which grows the buffer), the results over c->sn_ws
+  ygm_docs docs(const uint8_t* arena, const uint64_t* off, uint32_t flags, const uint8_t* opt = nullptr) const { return {arena, off, n_docs, flags, opt}; }
+  ygm_ws ws() const { return {c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_ws.as<uint8_t>(), slot_total, claim()}; }
+  ygm_results results() const { return c->ws_results(slot_total); }
   unsigned long long* payload() const { return (unsigned long long*)((uint8_t*)meta + offsetof(Meta, payload)); }
   unsigned int* fb_count() const { return (unsigned int*)((uint8_t*)meta + offsetof(Meta, fb_count)); }
 };
@@ -658,7 +678,7 @@ static int ws_begin(ygm_ctx* c, hipStream_t s, uint32_t n_docs, WsBatch& B) {
   HIPCHK(hipEventRecord(c->e0, s));
   return YGM_OK;
 }
-// the flat tier: launch(again) writes flat documents (input + workspace in LDS) into per-document slots of c->sn_ws
+// the flat tier: launch(results, claims, counters, again) writes flat documents (input + workspace in LDS) into per-document slots of c->sn_ws
 // and claims them -- 6 KiB of LDS per document, then 24 KiB for what that left; one read of the tier's counters after
 // each.  The documents it leaves take the general path, whose workspaces follow the slot region.  YGM_SNAP_NOLDS
 // (testing knob) turns the tier off.
@@ -670,8 +690,9 @@ static int ws_flat(WsBatch& B, uint64_t in_bytes, L launch) {
   if (!c->sn_ws.ensure(B.slot_total + 64) || !c->sn_claim.ensure((size_t)B.n_docs + 16) || !c->sn_pay.ensure(16)) return YGM_ENOMEM;
   HIPCHK(hipMemsetAsync(c->sn_pay.p, 0, 16, B.s));
   uint64_t pay[2] = {0, 0};
+  const ygm_results r = B.results();   // (over the slot region)
   for (int again = 0; again < 2 && pay[1] < B.n_docs; again++) {
-    if (launch(again)) return YGM_EDEVICE;
+    if (launch(r, c->sn_claim.as<uint8_t>(), c->sn_pay.as<unsigned long long>(), again)) return YGM_EDEVICE;
     const int e = read_u64_pair(c, B.s, c->sn_pay.as<uint64_t>(), pay);
     if (e) return e;
     if (again == 0) B.flat_first = pay[1];
@@ -681,13 +702,12 @@ static int ws_flat(WsBatch& B, uint64_t in_bytes, L launch) {
 }
 // plan: the count and scan launches (cont: the containment's), one read of the scanned total, c->sn_ws grown to hold
 // the workspaces after the slot region, which is kept
-static int ws_plan(WsBatch& B, const uint8_t* d_arena, const uint64_t* d_off, uint32_t flags, bool cont = false) {
+static int ws_plan(WsBatch& B, const ygm_docs& d, bool cont = false) {
   ygm_ctx* c = B.c;
-  if (cont ? ygm_k_launch_cont_plan(d_arena, d_off, B.n_docs, flags, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), B.s)
-           : ygm_k_launch_snap_plan(d_arena, d_off, B.n_docs, flags, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_bs.as<uint64_t>(), B.claim(), B.s))
-    return YGM_EDEVICE;
+  const ygm_ws w = B.ws();   // (its buffer as it is now: the plan sizes it)
+  if ((cont ? ygm_k_launch_cont_plan : ygm_k_launch_snap_plan)(&d, &w, c->sn_bs.as<uint64_t>(), B.s)) return YGM_EDEVICE;
   int e = 0;
-  if (B.n_docs) B.total = read_u64(c, B.s, c->sn_off.as<uint64_t>() + B.n_docs, e);
+  if (B.n_docs) B.total = read_u64(c, B.s, w.ws_off + B.n_docs, e);
   if (e) return e;
   return c->sn_ws.ensure(B.slot_total + B.total + 64, B.slot_total, B.s) ? YGM_OK : YGM_ENOMEM;
 }
@@ -699,8 +719,8 @@ static int ws_finish(WsBatch& B, uint64_t in_bytes, uint8_t* data, uint64_t data
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->e0, c->e1) == hipSuccess) c->stats.kernel_ms += ms;
   c->stats.calls++; c->stats.docs += B.n_docs; c->stats.bytes_in += in_bytes; c->stats.bytes_out += payload;
-  out->data = data; out->off = c->out_off.as<uint64_t>(); out->len = c->out_len.as<uint64_t>();
-  out->status = c->status.as<int32_t>(); out->data_bytes = data_bytes; out->payload_bytes = payload;
+  const ygm_results r = B.results();
+  out->data = data; out->off = r.out_off; out->len = r.out_len; out->status = r.status; out->data_bytes = data_bytes; out->payload_bytes = payload;
   return YGM_OK;
 }
 
@@ -713,27 +733,24 @@ static int snapshot_dev(ygm_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes
                         hipStream_t s, ygm_device_result* out, uint32_t xf, uint32_t* leave = nullptr, uint32_t dpw = 0,
                         const uint8_t* d_opt = nullptr) {
   if (leave) *leave = 0;
-  const uint32_t fl = c->flags | xf;
   WsBatch B;
   int e = ws_begin(c, s, n_docs, B);
   if (e) return e;
+  const ygm_docs d = B.docs(d_arena, d_doc_off, c->flags | xf, d_opt);
   // tier 1: k_snap_text (the flat-text tier writes updates only: a take batch, YGM_F_SNAP_VERSION, goes to k_snap whole)
-  if (!(xf & YGM_F_SNAP_VERSION) && (e = ws_flat(B, arena_bytes, [&](int again) {
-        return ygm_k_launch_snap_text(d_arena, d_doc_off, n_docs, fl, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(),
-                                      c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(), c->sn_pay.as<unsigned long long>(), again,
-                                      B.slot_total, d_opt, s);
+  if (!(xf & YGM_F_SNAP_VERSION) && (e = ws_flat(B, arena_bytes, [&](const ygm_results& r, uint8_t* claim, unsigned long long* pay, int again) {
+        return ygm_k_launch_snap_text(&d, &r, claim, pay, again, s);
       })))
     return e;
   uint64_t total_out = 0;   // the output region's extent when pending documents' merged bytes follow the workspaces
   Meta m;
   memset(&m, 0, sizeof(m));
   if (!B.slot_total || B.flat_docs < n_docs) {   // the count / scan / k_snap path
-    if ((e = ws_plan(B, d_arena, d_doc_off, fl))) return e;
+    if ((e = ws_plan(B, d))) return e;
     if (!c->sn_pend.ensure(4ull * n_docs + 16)) return YGM_ENOMEM;
-    if (ygm_k_launch_snap_w(d_arena, d_doc_off, n_docs, fl, c->sn_cnt.p, c->sn_off.as<uint64_t>(), c->sn_ws.as<uint8_t>(),
-                            c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.payload(), B.claim(), B.slot_total,
-                            c->sn_pend.as<uint32_t>(), B.fb_count(), dpw, d_opt, s))
-      return YGM_EDEVICE;
+    const ygm_ws w = B.ws();
+    const ygm_results r = B.results();
+    if (ygm_k_launch_snap(&d, &w, &r, B.payload(), c->sn_pend.as<uint32_t>(), B.fb_count(), dpw, s)) return YGM_EDEVICE;
     if ((e = read_meta(c, s, m, B.meta))) return e;
     if (m.fb_count && leave) *leave = m.fb_count;
     else if (m.fb_count && (e = snap_resolve_pending(c, s, m.fb_count, B.slot_total + B.total, total_out, m.payload))) return e;
@@ -766,23 +783,22 @@ int ygm_text_v1_device(ygm_ctx* c, const uint8_t* d_states, uint64_t states_byte
   if (!c || !out || mode > YGM_TEXT_DEEP || (n_docs && (!d_state_off || !d_name_off))) return YGM_EINVAL;
   (void)hipSetDevice(c->device);
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  const uint32_t fl = c->flags;
   WsBatch B;
   int e = ws_begin(c, s, n_docs, B);
-  if (e || (e = ws_flat(B, states_bytes, [&](int again) {
-        return ygm_k_launch_text_flat(d_states, d_state_off, d_names, d_name_off, n_docs, fl, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(),
-                                      c->out_len.as<uint64_t>(), c->status.as<int32_t>(), c->sn_claim.as<uint8_t>(),
-                                      c->sn_pay.as<unsigned long long>(), again, B.slot_total, s);
+  if (e) return e;
+  const ygm_docs d = B.docs(d_states, d_state_off, c->flags);
+  const ygm_side names{d_names, d_name_off};
+  if ((e = ws_flat(B, states_bytes, [&](const ygm_results& r, uint8_t* claim, unsigned long long* pay, int again) {
+        return ygm_k_launch_text_flat(&d, &names, &r, claim, pay, again, s);
       })))
     return e;
   Meta m;
   memset(&m, 0, sizeof(m));
   if (n_docs && (!B.slot_total || B.flat_docs < n_docs)) {
-    if ((e = ws_plan(B, d_states, d_state_off, fl))) return e;
-    if (ygm_k_launch_text(d_states, d_state_off, d_names, d_name_off, n_docs, fl, mode, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
-                          c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.payload(),
-                          B.claim(), B.slot_total, s))
-      return YGM_EDEVICE;
+    if ((e = ws_plan(B, d))) return e;
+    const ygm_ws w = B.ws();
+    const ygm_results r = B.results();
+    if (ygm_k_launch_text(&d, &names, mode, &w, &r, B.payload(), s)) return YGM_EDEVICE;
     if ((e = read_meta(c, s, m, B.meta))) return e;
   }
   if (getenv("YGM_TIER_COUNTS"))   // (testing knob, as the snapshot's line: the tier that finished the call's documents)
@@ -805,25 +821,23 @@ static int json_dev(ygm_ctx* c, const uint8_t* d_states, uint64_t states_bytes, 
     return YGM_EINVAL;
   (void)hipSetDevice(c->device);
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  const uint32_t fl = c->flags;
   WsBatch B;
   int e = ws_begin(c, s, n_docs, B);
   if (e) return e;
   if (!c->sn_pend.ensure(4ull * n_docs + 16)) return YGM_ENOMEM;
+  const ygm_docs d = B.docs(d_states, d_state_off, c->flags);
+  const ygm_side names{d_names, d_name_off};
   uint64_t ovf = 0;
   uint32_t reran = 0;
   Meta m;
   memset(&m, 0, sizeof(m));
   if (n_docs) {
-    if ((e = ws_plan(B, d_states, d_state_off, fl))) return e;
-    auto launch = [&](uint32_t n_list, int again) {
-      if (tojson)
-        return ygm_k_launch_tojson(d_states, d_state_off, d_names, d_name_off, n_docs, fl, kind, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
-                                   c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.meta,
-                                   0, B.total, c->sn_pend.as<uint32_t>(), n_list, again, s);
-      return ygm_k_launch_json(d_states, d_state_off, d_names, d_name_off, n_docs, fl, kind, c->sn_cnt.p, c->sn_off.as<uint64_t>(),
-                               c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), B.meta, 0,
-                               B.total, c->sn_pend.as<uint32_t>(), n_list, again, fields, s);
+    if ((e = ws_plan(B, d))) return e;
+    auto launch = [&](uint32_t n_list, int again) {   // (the buffer may have grown between the two: built per launch)
+      const ygm_ws w = B.ws();
+      const ygm_results r = B.results();
+      const ygm_rerun rr{B.total, c->sn_pend.as<uint32_t>(), n_list, again};
+      return (tojson ? ygm_k_launch_tojson : ygm_k_launch_json)(&d, &names, kind, &w, &r, &rr, B.meta, fields, s);
     };
     if (launch(0, 0)) return YGM_EDEVICE;
     if ((e = read_meta(c, s, m, B.meta))) return e;
@@ -927,10 +941,11 @@ int ygm_version_restore_v1_device(ygm_ctx* c, const uint8_t* d_states, const uin
   const double k1 = c->stats.kernel_ms;
   const uint64_t total = r1.payload_bytes + sv[1] + 32ull * n_docs + 64;
   float ms = 0;
-  e = restore_tail(c, s, n_docs, total, [&] {
-    return ygm_k_launch_ver_cut(c->s2_data.as<uint8_t>(), c->s2_off.as<uint64_t>(), c->s2_st.as<int32_t>(), d_versions, d_version_off, n_docs,
-                                c->flags, c->vr_out.as<uint8_t>(), total, c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(),
-                                c->vr_st.as<int32_t>(), s);
+  const ygm_side versions{d_versions, d_version_off};
+  e = restore_tail(c, s, n_docs, total, [&] {   // (the cut's buffers are restore_tail's: built after it has them)
+    const ygm_packed S = c->packed();
+    const ygm_results r = c->vr_results(total);
+    return ygm_k_launch_ver_cut(&S, &versions, n_docs, c->flags, &r, s);
   }, d_restored_opt, out, ms);
   if (e) return e;
   HIPCHK(hipStreamSynchronize(s));
@@ -974,10 +989,11 @@ int ygm_version_restore_shared_v1_device(ygm_ctx* c, const uint8_t* d_states, ui
   if (n_asks && (e = read_u64s(c, s, {c->ask_base.as<uint64_t>() + n_asks, d_version_off + n_asks}, av))) return e;
   const uint64_t total = av[0] + av[1] + 32ull * n_asks + 64;
   float ms = 0;
+  const ygm_side versions{d_versions, d_version_off};
   e = restore_tail(c, s, n_asks, total, [&] {
-    return ygm_k_launch_ver_cut_gather(c->s2_data.as<uint8_t>(), c->s2_off.as<uint64_t>(), c->s2_st.as<int32_t>(), c->ask_ix.as<uint32_t>(),
-                                       c->ask_base.as<uint64_t>(), d_versions, d_version_off, n_asks, c->flags, c->vr_out.as<uint8_t>(), total,
-                                       c->vr_off.as<uint64_t>(), c->vr_len.as<uint64_t>(), c->vr_st.as<int32_t>(), s);
+    const ygm_packed S = c->packed();
+    const ygm_results r = c->vr_results(total);
+    return ygm_k_launch_ver_cut_gather(&S, c->ask_ix.as<uint32_t>(), c->ask_base.as<uint64_t>(), &versions, n_asks, c->flags, &r, s);
   }, d_restored_opt, out, ms);
   if (e) return e;
   // the carries: after the cut's status (restore_tail), as the other shared forms, id and state to ask
@@ -1003,18 +1019,18 @@ int ygm_contains_v1_device(ygm_ctx* c, const uint8_t* d_states_in, const uint64_
   ygm_device_result r1;
   e = snapshot_dev(c, d_states_in, states_bytes, d_state_off_in, n_docs, s, &r1, YGM_F_SNAP_STATE);
   if (e || (e = pack_snapshots(c, s, r1, n_docs))) return e;
-  const uint8_t* d_states = c->s2_data.as<uint8_t>();
-  const uint64_t* d_state_off = c->s2_off.as<uint64_t>();
+  const ygm_packed S = c->packed();
   // a workspace batch of its own: k_cont_count as the count launch, the answers (a byte per document) in c->out
   WsBatch B;
   if ((e = ws_begin(c, s, n_docs, B))) return e;
   if (!c->out.ensure((uint64_t)n_docs + 64)) return YGM_ENOMEM;
-  if ((e = ws_plan(B, d_states, d_state_off, c->flags, true))) return e;
-  if (ygm_k_launch_cont(d_states, d_state_off, d_updates, d_update_off, n_docs, c->flags, c->sn_off.as<uint64_t>(), c->sn_ws.as<uint8_t>(),
-                        c->out.as<uint8_t>(), c->out_off.as<uint64_t>(), c->out_len.as<uint64_t>(), c->status.as<int32_t>(), s))
-    return YGM_EDEVICE;
-  if (n_docs && ygm_k_launch_v2_status(c->s2_st.as<int32_t>(), n_docs, c->status.as<int32_t>(), c->out_len.as<uint64_t>(), s))
-    return YGM_EDEVICE;
+  const ygm_docs d = B.docs(S.data, S.off, c->flags);
+  const ygm_side updates{d_updates, d_update_off};
+  if ((e = ws_plan(B, d, true))) return e;
+  const ygm_ws w = B.ws();
+  const ygm_results r = c->results(0, n_docs);
+  if (ygm_k_launch_cont(&d, &updates, &w, &r, s)) return YGM_EDEVICE;
+  if (n_docs && ygm_k_launch_v2_status(S.st, n_docs, r.status, r.out_len, s)) return YGM_EDEVICE;
   if ((e = ws_finish(B, 0, c->out.as<uint8_t>(), n_docs, 0, out))) return e;   // (the call counts no bytes in or out)
   out->payload_bytes = n_docs;
   return YGM_OK;
@@ -1051,13 +1067,11 @@ static int step2_pending_split(ygm_ctx* c, hipStream_t s, uint32_t P, const uint
       !c->pn_du.ensure(4ull * np + 16))
     return YGM_ENOMEM;
   uint64_t* offs = c->pq_off.as<uint64_t>();
-  auto launch = [&](int pass, uint8_t* da, uint8_t* db, uint8_t* dc, uint8_t* dsv) {
-    return gather ? ygm_k_launch_pend_split_g(list, P, c->ask_ix.as<uint32_t>(), c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), d_sv_arena,
-                                              d_sv_off, offs, da, db, dc, dsv, pass, s)
-                  : ygm_k_launch_pend_split(list, P, c->sn_ws.as<uint8_t>(), c->out_off.as<uint64_t>(), d_sv_arena, d_sv_off, offs, da, db, dc,
-                                            dsv, pass, s);
-  };
-  if (launch(0, nullptr, nullptr, nullptr, nullptr)) return YGM_EDEVICE;
+  const ygm_results rec = c->ws_results();   // (the pending states' records)
+  const ygm_side sv{d_sv_arena, d_sv_off};
+  const uint32_t* ask_ix = gather ? c->ask_ix.as<uint32_t>() : nullptr;
+  ygm_pend_parts parts{offs, nullptr, nullptr, nullptr, nullptr};
+  if (ygm_k_launch_pend_split(list, P, ask_ix, rec.out, rec.out_off, &sv, &parts, 0, s)) return YGM_EDEVICE;
   const int e = read_u64s(c, s, {offs + P, offs + np + P, offs + 2 * np + P, offs + 3 * np + P}, tot);
   if (e) return e;
   DevBuf* part[4] = {&c->pq_a, &c->pq_b, &c->pq_c, &c->pq_s};
@@ -1065,30 +1079,28 @@ static int step2_pending_split(ygm_ctx* c, hipStream_t s, uint32_t P, const uint
     if (!part[k]->ensure(tot[k] + 64)) return YGM_ENOMEM;
     HIPCHK(hipMemsetAsync(part[k]->as<uint8_t>() + tot[k], 0, 64, s));   // (readable tail padding for the kernels)
   }
-  return launch(1, c->pq_a.as<uint8_t>(), c->pq_b.as<uint8_t>(), c->pq_c.as<uint8_t>(), c->pq_s.as<uint8_t>()) ? YGM_EDEVICE : YGM_OK;
+  parts = c->pend_parts();
+  return ygm_k_launch_pend_split(list, P, ask_ix, rec.out, rec.out_off, &sv, &parts, 1, s) ? YGM_EDEVICE : YGM_OK;
 }
 // finish (after the main diff): the two diffs, the join, the merge, the places in `out`
 static int step2_pending_finish(ygm_ctx* c, hipStream_t s, uint32_t P, const uint64_t (&tot)[4], ygm_device_result* out,
                                 const uint32_t* list = nullptr) {
   const uint64_t np = (uint64_t)P + 1;
-  uint64_t* offs = c->pq_off.as<uint64_t>();
+  const ygm_pend_parts parts = c->pend_parts();
   for (ygm_ctx*& k : c->pend_dx) if (!k) { const int e = ygm_open(c->device, c->flags, &k); if (e) return e; }
   ygm_device_result ra, rc;
-  int e = run_doc_kernel(c->pend_dx[0], 1, c->pq_a.as<uint8_t>(), tot[0], offs, c->pq_s.as<uint8_t>(), tot[3], offs + 3 * np, P, s, &ra,
-                         YGM_F_KEEP_SUB);
-  if (!e) e = run_doc_kernel(c->pend_dx[1], 1, c->pq_c.as<uint8_t>(), tot[2], offs + 2 * np, c->pq_s.as<uint8_t>(), tot[3], offs + 3 * np, P,
-                             s, &rc, 0);
+  int e = run_doc_kernel(c->pend_dx[0], 1, parts.da, tot[0], parts.offs, parts.dsv, tot[3], parts.offs + 3 * np, P, s, &ra, YGM_F_KEEP_SUB);
+  if (!e) e = run_doc_kernel(c->pend_dx[1], 1, parts.dc, tot[2], parts.offs + 2 * np, parts.dsv, tot[3], parts.offs + 3 * np, P, s, &rc, 0);
   if (e) return e;
-  if (ygm_k_launch_pend_join(P, ra.data, ra.off, ra.len, ra.status, c->pq_b.as<uint8_t>(), offs, rc.data, rc.off, rc.len, rc.status,
-                             c->pn_off.as<uint64_t>(), c->pn_du.as<uint32_t>(), c->pq_st.as<int32_t>(), nullptr, 0, s))
-    return YGM_EDEVICE;
-  const uint64_t total = read_u64(c, s, c->pn_off.as<uint64_t>() + 3ull * P, e);
+  const ygm_batch_out a = batch_out(ra), cc = batch_out(rc);
+  ygm_pend_batch b = c->pend_batch(false);
+  if (ygm_k_launch_pend_join(P, &a, &cc, &parts, &b, c->pq_st.as<int32_t>(), 0, s)) return YGM_EDEVICE;
+  const uint64_t total = read_u64(c, s, b.upd_off + 3ull * P, e);
   if (e) return e;
   if (!c->pn_arena.ensure(total + 64)) return YGM_ENOMEM;
   HIPCHK(hipMemsetAsync(c->pn_arena.as<uint8_t>() + total, 0, 64, s));
-  if (ygm_k_launch_pend_join(P, ra.data, ra.off, ra.len, ra.status, c->pq_b.as<uint8_t>(), offs, rc.data, rc.off, rc.len, rc.status,
-                             c->pn_off.as<uint64_t>(), c->pn_du.as<uint32_t>(), c->pq_st.as<int32_t>(), c->pn_arena.as<uint8_t>(), 1, s))
-    return YGM_EDEVICE;
+  b = c->pend_batch(true);
+  if (ygm_k_launch_pend_join(P, &a, &cc, &parts, &b, c->pq_st.as<int32_t>(), 1, s)) return YGM_EDEVICE;
   uint64_t db = 0;
   unsigned long long pay = out->payload_bytes;
   if ((e = pend_merge_place(c, s, P, total, c->pq_st.as<int32_t>(), c->out, out->data_bytes, db, pay, list))) return e;

@@ -428,92 +428,88 @@ __global__ __launch_bounds__(docstage::NT) void k_cont(const uint8_t* __restrict
 
 using namespace ygm;
 
-extern "C" {
-
-// phase 1: counts and the scanned workspace offsets (ws_off: n_docs + 1 entries, total at [n_docs];
-// bs: ceil(n / 256) + 1 scratch entries)
-int ygm_k_launch_snap_text(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t* out_off,
-                           uint64_t* out_len, int32_t* status, uint8_t* claim, unsigned long long* pay, int again, uint64_t slot_total,
-                           const uint8_t* opt, hipStream_t s) {
-  if (n_docs == 0) return 0;
-  // again == 0: 6 KiB of LDS per document (207 parts); again == 1: 24 KiB (865 parts) for the documents the first launch left.
-  // YGM_SNAP_TEXT="KiB" picks another measured size for the first launch.
-  if (again) {
-    hipLaunchKernelGGL((k_snap_text<24576>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
-                       claim, pay, 1u, slot_total, opt);
-    return ygm_launch_rc(__func__);
-  }
-  const char* env = getenv("YGM_SNAP_TEXT");
-  const int lb = env ? atoi(env) : 6;
-#define SNT(L) if (lb == L) { hipLaunchKernelGGL((k_snap_text<L * 1024>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, out, \
-                                                   out_off, out_len, status, claim, pay, 0u, slot_total, opt); return ygm_launch_rc(__func__); }
-  SNT(4) SNT(5) SNT(8)
-#undef SNT
-  if (lb == 53) { hipLaunchKernelGGL((k_snap_text<5376>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status,
-                                     claim, pay, 0u, slot_total, opt); return ygm_launch_rc(__func__); }
-  hipLaunchKernelGGL((k_snap_text<6144>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, out, out_off, out_len, status, claim,
-                     pay, 0u, slot_total, opt);
-  return ygm_launch_rc(__func__);
-}
-int ygm_k_launch_snap_plan(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, void* cnt, uint64_t* ws_off,
-                           uint64_t* bs, const uint8_t* claim, hipStream_t s) {
-  if (n_docs == 0) return 0;
-  const uint32_t g = (n_docs + docstage::DPW - 1) / docstage::DPW, nb = (n_docs + 1 + 255) / 256;
-  hipLaunchKernelGGL(k_snap_count, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, (uint4*)cnt, ws_off, claim);
-  hipLaunchKernelGGL(k_snap_scan_sum, dim3(nb), dim3(256), 0, s, (const uint64_t*)ws_off, n_docs, bs);
-  hipLaunchKernelGGL(k_snap_scan_top, dim3(1), dim3(1024), 0, s, bs, nb);
-  hipLaunchKernelGGL(k_snap_scan_apply, dim3(nb), dim3(256), 0, s, ws_off, n_docs, (const uint64_t*)bs);
-  return ygm_launch_rc(__func__);
+// k_snap_text<LB> over every document of the batch (again: 0 / 1, the kernel's own argument)
+template <uint32_t LB>
+static void snap_text_launch(const ygm_docs* d, const ygm_results* r, uint8_t* claim, unsigned long long* pay, uint32_t again, hipStream_t s) {
+  hipLaunchKernelGGL((k_snap_text<LB>), dim3(d->n_docs), dim3(docstage::NT), 0, s, d->arena, d->doc_off, d->n_docs, d->flags, r->out, r->out_off,
+                     r->out_len, r->status, claim, pay, again, r->slot_total, d->opt);
 }
 // exclusive scan of v[0..n) in place, total at v[n] (bs: ceil((n + 1) / 256) + 1 scratch entries)
-int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s) {
-  if (n == 0) return 0;
+static void scan_launch(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s) {
   const uint32_t nb = (n + 1 + 255) / 256;
   hipLaunchKernelGGL(k_snap_scan_sum, dim3(nb), dim3(256), 0, s, (const uint64_t*)v, n, bs);
   hipLaunchKernelGGL(k_snap_scan_top, dim3(1), dim3(1024), 0, s, bs, nb);
   hipLaunchKernelGGL(k_snap_scan_apply, dim3(nb), dim3(256), 0, s, v, n, (const uint64_t*)bs);
+}
+
+extern "C" {
+
+// the flat tier.  again == 0: 6 KiB of LDS per document (207 parts); again == 1: 24 KiB (865 parts) for the documents the
+// first launch left.  YGM_SNAP_TEXT="KiB" picks another measured size for the first launch (4, 5, 53: 5.25, 8).
+int ygm_k_launch_snap_text(const ygm_docs* d, const ygm_results* r, uint8_t* claim, unsigned long long* pay, int again, hipStream_t s) {
+  if (d->n_docs == 0) return 0;
+  const char* env = again ? nullptr : getenv("YGM_SNAP_TEXT");
+  if (again) snap_text_launch<24576>(d, r, claim, pay, 1u, s);
+  else switch (env ? atoi(env) : 6) {
+    case 4: snap_text_launch<4096>(d, r, claim, pay, 0u, s); break;
+    case 5: snap_text_launch<5120>(d, r, claim, pay, 0u, s); break;
+    case 8: snap_text_launch<8192>(d, r, claim, pay, 0u, s); break;
+    case 53: snap_text_launch<5376>(d, r, claim, pay, 0u, s); break;
+    default: snap_text_launch<6144>(d, r, claim, pay, 0u, s);
+  }
   return ygm_launch_rc(__func__);
 }
-// phase 2: the snapshots (ws sized from ws_off[n_docs])
+// phase 1: counts and the scanned workspace offsets (w->ws_off: n_docs + 1 entries, total at [n_docs];
+// bs: ceil(n / 256) + 1 scratch entries)
+int ygm_k_launch_snap_plan(const ygm_docs* d, const ygm_ws* w, uint64_t* bs, hipStream_t s) {
+  if (d->n_docs == 0) return 0;
+  const uint32_t g = (d->n_docs + docstage::DPW - 1) / docstage::DPW;
+  hipLaunchKernelGGL(k_snap_count, dim3(g), dim3(docstage::NT), 0, s, d->arena, d->doc_off, d->n_docs, d->flags, (uint4*)w->cnt, w->ws_off, w->claim);
+  scan_launch(w->ws_off, d->n_docs, bs, s);
+  return ygm_launch_rc(__func__);
+}
+int ygm_k_launch_scan(uint64_t* v, uint32_t n, uint64_t* bs, hipStream_t s) {
+  if (n == 0) return 0;
+  scan_launch(v, n, bs, s);
+  return ygm_launch_rc(__func__);
+}
+// phase 2: the snapshots (w->ws sized from ws_off[n_docs])
 // dpw_hint: documents per wave when YGM_SNAP_DPW is not set (0: the default 16)
-int ygm_k_launch_snap_w(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
-                        uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
-                        uint64_t base, uint32_t* pend_list, unsigned int* pend_n, uint32_t dpw_hint, const uint8_t* opt, hipStream_t s) {
-  if (n_docs == 0) return 0;
+int ygm_k_launch_snap(const ygm_docs* d, const ygm_ws* w, const ygm_results* r, unsigned long long* payload, uint32_t* pend_list,
+                      unsigned int* pend_n, uint32_t dpw_hint, hipStream_t s) {
+  if (d->n_docs == 0) return 0;
   const uint32_t dpw = docstage::docs_per_wave(dpw_hint);
-  const uint32_t g = (n_docs + dpw - 1) / dpw;
-  hipLaunchKernelGGL(k_snap, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, n_docs, flags, (const uint4*)cnt, ws_off, ws, out_off, out_len,
-                     status, payload, dpw, claim, base, pend_list, pend_n, opt);
+  const uint32_t g = (d->n_docs + dpw - 1) / dpw;
+  hipLaunchKernelGGL(k_snap, dim3(g), dim3(docstage::NT), 0, s, d->arena, d->doc_off, d->n_docs, d->flags, (const uint4*)w->cnt,
+                     (const uint64_t*)w->ws_off, w->ws, r->out_off, r->out_len, r->status, payload, dpw, w->claim, w->base, pend_list, pend_n, d->opt);
   return ygm_launch_rc(__func__);
 }
-int ygm_k_launch_snap(const uint8_t* arena, const uint64_t* doc_off, uint32_t n_docs, uint32_t flags, const void* cnt, const uint64_t* ws_off,
-                      uint8_t* ws, uint64_t* out_off, uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim,
-                      uint64_t base, uint32_t* pend_list, unsigned int* pend_n, hipStream_t s) {
-  return ygm_k_launch_snap_w(arena, doc_off, n_docs, flags, cnt, ws_off, ws, out_off, out_len, status, payload, claim, base, pend_list, pend_n, 0u, nullptr, s);
-}
-int ygm_k_launch_pend_plan(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, uint64_t* upd_off, uint32_t* doc_upd,
-                           hipStream_t s) {
-  hipLaunchKernelGGL(k_pend_plan, dim3(1), dim3(1024), 0, s, list, P, ws, out_off, upd_off, doc_upd);
+int ygm_k_launch_pend_plan(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const ygm_pend_batch* b, hipStream_t s) {
+  hipLaunchKernelGGL(k_pend_plan, dim3(1), dim3(1024), 0, s, list, P, ws, out_off, b->upd_off, b->doc_upd);
   return ygm_launch_rc(__func__);
 }
-int ygm_k_launch_pend_copy(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const uint64_t* upd_off, uint8_t* dst,
-                           hipStream_t s) {
+int ygm_k_launch_pend_copy(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const ygm_pend_batch* b, hipStream_t s) {
   if (P == 0) return 0;
-  hipLaunchKernelGGL(k_pend_copy, dim3(P), dim3(256), 0, s, list, ws, out_off, upd_off, dst);
+  hipLaunchKernelGGL(k_pend_copy, dim3(P), dim3(256), 0, s, list, ws, out_off, (const uint64_t*)b->upd_off, b->dst);
   return ygm_launch_rc(__func__);
 }
-int ygm_k_launch_pend_fix(const uint32_t* list, uint32_t P, const uint64_t* m_off, const uint64_t* m_len, const int32_t* m_st,
-                          const int32_t* pst, uint64_t tail, uint64_t* out_off, uint64_t* out_len, int32_t* status, hipStream_t s) {
+int ygm_k_launch_pend_fix(const uint32_t* list, uint32_t P, const ygm_batch_out* m, const int32_t* pst, uint64_t tail,
+                          const ygm_results* r, hipStream_t s) {
   if (P == 0) return 0;
-  hipLaunchKernelGGL(k_pend_fix, dim3((P + 255) / 256), dim3(256), 0, s, list, P, m_off, m_len, m_st, pst, tail, out_off, out_len, status);
+  hipLaunchKernelGGL(k_pend_fix, dim3((P + 255) / 256), dim3(256), 0, s, list, P, m->off, m->len, m->status, pst, tail, r->out_off, r->out_len,
+                     r->status);
   return ygm_launch_rc(__func__);
 }
-int ygm_k_launch_pend_split(const uint32_t* list, uint32_t P, const uint8_t* ws, const uint64_t* out_off, const uint8_t* sv,
-                            const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc, uint8_t* dsv, int pass,
-                            hipStream_t s) {
+int ygm_k_launch_pend_split(const uint32_t* list, uint32_t P, const uint32_t* ask_ix, const uint8_t* ws, const uint64_t* out_off,
+                            const ygm_side* sv, const ygm_pend_parts* p, int pass, hipStream_t s) {
   if (P == 0) return 0;
-  if (pass == 0) hipLaunchKernelGGL(k_pend_split_plan, dim3(1), dim3(1024), 0, s, list, P, ws, out_off, sv_off, offs);
-  else hipLaunchKernelGGL(k_pend_split_copy, dim3(P), dim3(256), 0, s, list, P, ws, out_off, sv, sv_off, (const uint64_t*)offs, da, db, dc, dsv);
+  const uint64_t* offs = p->offs;   // (as the copy kernels read it)
+  if (!ask_ix) {
+    if (pass == 0) hipLaunchKernelGGL(k_pend_split_plan, dim3(1), dim3(1024), 0, s, list, P, ws, out_off, sv->off, p->offs);
+    else hipLaunchKernelGGL(k_pend_split_copy, dim3(P), dim3(256), 0, s, list, P, ws, out_off, sv->arena, sv->off, offs, p->da, p->db, p->dc, p->dsv);
+  } else if (pass == 0) hipLaunchKernelGGL(k_pend_split_plan_g, dim3(1), dim3(1024), 0, s, list, P, ask_ix, ws, out_off, sv->off, p->offs);
+  else hipLaunchKernelGGL(k_pend_split_copy_g, dim3(P), dim3(256), 0, s, list, P, ask_ix, ws, out_off, sv->arena, sv->off, offs, p->da, p->db, p->dc,
+                          p->dsv);
   return ygm_launch_rc(__func__);
 }
 int ygm_k_launch_ask_pending(const uint32_t* ask_ix, uint32_t n_asks, const int32_t* st_state, uint32_t* list, unsigned int* n_out,
@@ -522,42 +518,29 @@ int ygm_k_launch_ask_pending(const uint32_t* ask_ix, uint32_t n_asks, const int3
   hipLaunchKernelGGL(k_ask_pending, dim3((n_asks + 255) / 256), dim3(256), 0, s, ask_ix, n_asks, st_state, list, n_out);
   return ygm_launch_rc(__func__);
 }
-int ygm_k_launch_pend_split_g(const uint32_t* list, uint32_t P, const uint32_t* ask_ix, const uint8_t* ws, const uint64_t* out_off,
-                              const uint8_t* sv, const uint64_t* sv_off, uint64_t* offs, uint8_t* da, uint8_t* db, uint8_t* dc,
-                              uint8_t* dsv, int pass, hipStream_t s) {
+int ygm_k_launch_pend_join(uint32_t P, const ygm_batch_out* a, const ygm_batch_out* c, const ygm_pend_parts* p, const ygm_pend_batch* b,
+                           int32_t* pst, int pass, hipStream_t s) {
   if (P == 0) return 0;
-  if (pass == 0) hipLaunchKernelGGL(k_pend_split_plan_g, dim3(1), dim3(1024), 0, s, list, P, ask_ix, ws, out_off, sv_off, offs);
-  else hipLaunchKernelGGL(k_pend_split_copy_g, dim3(P), dim3(256), 0, s, list, P, ask_ix, ws, out_off, sv, sv_off, (const uint64_t*)offs, da,
-                          db, dc, dsv);
-  return ygm_launch_rc(__func__);
-}
-int ygm_k_launch_pend_join(uint32_t P, const uint8_t* ad, const uint64_t* a_off, const uint64_t* a_len, const int32_t* a_st, const uint8_t* bd,
-                           const uint64_t* offs, const uint8_t* cd, const uint64_t* c_off, const uint64_t* c_len, const int32_t* c_st,
-                           uint64_t* upd_off, uint32_t* doc_upd, int32_t* pst, uint8_t* dst, int pass, hipStream_t s) {
-  if (P == 0) return 0;
-  if (pass == 0) hipLaunchKernelGGL(k_pend_join_plan, dim3(1), dim3(1024), 0, s, P, a_len, a_st, offs, c_len, c_st, upd_off, doc_upd, pst);
-  else hipLaunchKernelGGL(k_pend_join_copy, dim3(P), dim3(256), 0, s, P, ad, a_off, bd, offs, cd, c_off, (const uint64_t*)upd_off, dst);
+  const uint64_t* offs = p->offs;
+  if (pass == 0) hipLaunchKernelGGL(k_pend_join_plan, dim3(1), dim3(1024), 0, s, P, a->len, a->status, offs, c->len, c->status, b->upd_off, b->doc_upd, pst);
+  else hipLaunchKernelGGL(k_pend_join_copy, dim3(P), dim3(256), 0, s, P, a->data, a->off, (const uint8_t*)p->db, offs, c->data, c->off,
+                          (const uint64_t*)b->upd_off, b->dst);
   return ygm_launch_rc(__func__);
 }
 
 // read-only SyncStep2 containment: workspace plan (the snapshot scan), then one thread per document
-int ygm_k_launch_cont_plan(const uint8_t* st_arena, const uint64_t* st_off, uint32_t n_docs, uint32_t flags, uint64_t* ws_off, uint64_t* bs,
-                           hipStream_t s) {
-  if (n_docs == 0) return 0;
-  const uint32_t g = (n_docs + docstage::NT - 1) / docstage::NT, nb = (n_docs + 1 + 255) / 256;
-  hipLaunchKernelGGL(k_cont_count, dim3(g), dim3(docstage::NT), 0, s, st_arena, st_off, n_docs, flags, ws_off);
-  hipLaunchKernelGGL(k_snap_scan_sum, dim3(nb), dim3(256), 0, s, (const uint64_t*)ws_off, n_docs, bs);
-  hipLaunchKernelGGL(k_snap_scan_top, dim3(1), dim3(1024), 0, s, bs, nb);
-  hipLaunchKernelGGL(k_snap_scan_apply, dim3(nb), dim3(256), 0, s, ws_off, n_docs, (const uint64_t*)bs);
+int ygm_k_launch_cont_plan(const ygm_docs* st, const ygm_ws* w, uint64_t* bs, hipStream_t s) {
+  if (st->n_docs == 0) return 0;
+  const uint32_t g = (st->n_docs + docstage::NT - 1) / docstage::NT;
+  hipLaunchKernelGGL(k_cont_count, dim3(g), dim3(docstage::NT), 0, s, st->arena, st->doc_off, st->n_docs, st->flags, w->ws_off);
+  scan_launch(w->ws_off, st->n_docs, bs, s);
   return ygm_launch_rc(__func__);
 }
-int ygm_k_launch_cont(const uint8_t* st_arena, const uint64_t* st_off, const uint8_t* up_arena, const uint64_t* up_off, uint32_t n_docs,
-                      uint32_t flags, const uint64_t* ws_off, uint8_t* ws, uint8_t* out, uint64_t* out_off, uint64_t* out_len,
-                      int32_t* status, hipStream_t s) {
-  if (n_docs == 0) return 0;
-  const uint32_t g = (n_docs + docstage::NT - 1) / docstage::NT;
-  hipLaunchKernelGGL(k_cont, dim3(g), dim3(docstage::NT), 0, s, st_arena, st_off, up_arena, up_off, n_docs, flags, ws_off, ws, out, out_off, out_len,
-                     status);
+int ygm_k_launch_cont(const ygm_docs* st, const ygm_side* upd, const ygm_ws* w, const ygm_results* r, hipStream_t s) {
+  if (st->n_docs == 0) return 0;
+  const uint32_t g = (st->n_docs + docstage::NT - 1) / docstage::NT;
+  hipLaunchKernelGGL(k_cont, dim3(g), dim3(docstage::NT), 0, s, st->arena, st->doc_off, upd->arena, upd->off, st->n_docs, st->flags,
+                     (const uint64_t*)w->ws_off, w->ws, r->out, r->out_off, r->out_len, r->status);
   return ygm_launch_rc(__func__);
 }
 

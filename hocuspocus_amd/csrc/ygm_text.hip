@@ -116,25 +116,21 @@ extern "C" {
 
 // the flat tier at k_snap_text's two LDS sizes: again == 0: 6 KiB per document; again == 1: 24 KiB for the documents
 // the first launch left (claim[] written by every launch for the documents it looked at)
-int ygm_k_launch_text_flat(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
-                           uint32_t flags, uint8_t* out, uint64_t* out_off, uint64_t* out_len, int32_t* status, uint8_t* claim,
-                           unsigned long long* pay, int again, uint64_t slot_total, hipStream_t s) {
-  if (n_docs == 0) return 0;
-  if (again) hipLaunchKernelGGL((k_text_flat<24576>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, out,
-                                out_off, out_len, status, claim, pay, 1u, slot_total);
-  else hipLaunchKernelGGL((k_text_flat<6144>), dim3(n_docs), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, out, out_off,
-                          out_len, status, claim, pay, 0u, slot_total);
+int ygm_k_launch_text_flat(const ygm_docs* d, const ygm_side* names, const ygm_results* r, uint8_t* claim, unsigned long long* pay, int again, hipStream_t s) {
+  if (d->n_docs == 0) return 0;
+  auto k = again ? k_text_flat<24576> : k_text_flat<6144>;
+  hipLaunchKernelGGL(k, dim3(d->n_docs), dim3(docstage::NT), 0, s, d->arena, d->doc_off, names->arena, names->off, d->n_docs, d->flags, r->out,
+                     r->out_off, r->out_len, r->status, claim, pay, again ? 1u : 0u, r->slot_total);
   return ygm_launch_rc(__func__);
 }
-// the general path over the workspaces ygm_k_launch_snap_plan sized (cnt, ws_off); dpw as ygm_k_launch_snap_w
-int ygm_k_launch_text(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
-                      uint32_t flags, uint32_t mode, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
-                      uint64_t* out_len, int32_t* status, unsigned long long* payload, const uint8_t* claim, uint64_t base, hipStream_t s) {
-  if (n_docs == 0) return 0;
+// the general path over the workspaces ygm_k_launch_snap_plan sized (w->cnt, w->ws_off); dpw as ygm_k_launch_snap
+int ygm_k_launch_text(const ygm_docs* d, const ygm_side* names, uint32_t mode, const ygm_ws* w, const ygm_results* r,
+                      unsigned long long* payload, hipStream_t s) {
+  if (d->n_docs == 0) return 0;
   const uint32_t dpw = docstage::docs_per_wave(0);
-  const uint32_t g = (n_docs + dpw - 1) / dpw;
-  hipLaunchKernelGGL(k_text, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, mode, (const uint4*)cnt, ws_off, ws,
-                     out_off, out_len, status, payload, dpw, claim, base);
+  const uint32_t g = (d->n_docs + dpw - 1) / dpw;
+  hipLaunchKernelGGL(k_text, dim3(g), dim3(docstage::NT), 0, s, d->arena, d->doc_off, names->arena, names->off, d->n_docs, d->flags, mode,
+                     (const uint4*)w->cnt, (const uint64_t*)w->ws_off, w->ws, r->out_off, r->out_len, r->status, payload, dpw, w->claim, w->base);
   return ygm_launch_rc(__func__);
 }
 

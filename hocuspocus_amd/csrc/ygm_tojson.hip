@@ -50,19 +50,19 @@ using namespace ygm;
 
 extern "C" {
 
-// as ygm_k_launch_json: over the workspaces ygm_k_launch_snap_plan sized (cnt, ws_off); again: the listed documents'
-// second run (n_list of them).  kind: YGM_TOJSON_MAP / _ARRAY / _TEXT (checked by the engine)
-int ygm_k_launch_tojson(const uint8_t* arena, const uint64_t* doc_off, const uint8_t* names, const uint64_t* name_off, uint32_t n_docs,
-                        uint32_t flags, uint32_t kind, const void* cnt, const uint64_t* ws_off, uint8_t* ws, uint64_t* out_off,
-                        uint64_t* out_len, int32_t* status, void* meta, uint64_t base, uint64_t ovf_base, uint32_t* list, uint32_t n_list,
-                        int again, hipStream_t s) {
-  const uint32_t n = again ? n_list : n_docs;
+// as ygm_k_launch_json, and its signature: over the workspaces ygm_k_launch_snap_plan sized (w->cnt, w->ws_off); run->again:
+// the listed documents' second run (n_list of them).  kind: YGM_TOJSON_MAP / _ARRAY / _TEXT (checked by the engine).
+// A root has no field list: `fields` is not read
+int ygm_k_launch_tojson(const ygm_docs* d, const ygm_side* names, uint32_t kind, const ygm_ws* w, const ygm_results* r,
+                        const ygm_rerun* run, void* meta, int /*fields*/, hipStream_t s) {
+  const uint32_t n = run->again ? run->n_list : d->n_docs;
   if (n == 0) return 0;
   const uint32_t dpw = docstage::docs_per_wave(0);
   const uint32_t g = (n + dpw - 1) / dpw;
-  auto k = flags & F_FLOATS ? k_tojson<true> : k_tojson<false>;
-  hipLaunchKernelGGL(k, dim3(g), dim3(docstage::NT), 0, s, arena, doc_off, names, name_off, n_docs, flags, kind, (const uint4*)cnt, ws_off,
-                     ws, out_off, out_len, status, (DocMeta*)meta, dpw, base, ovf_base, list, n_list, again ? 1u : 0u);
+  auto k = d->flags & F_FLOATS ? k_tojson<true> : k_tojson<false>;
+  hipLaunchKernelGGL(k, dim3(g), dim3(docstage::NT), 0, s, d->arena, d->doc_off, names->arena, names->off, d->n_docs, d->flags, kind,
+                     (const uint4*)w->cnt, (const uint64_t*)w->ws_off, w->ws, r->out_off, r->out_len, r->status, (DocMeta*)meta, dpw, w->base,
+                     run->ovf_base, run->list, run->n_list, run->again ? 1u : 0u);
   return ygm_launch_rc(__func__);
 }
 

@@ -132,21 +132,19 @@ using namespace ygm;
 
 extern "C" {
 
-int ygm_k_launch_ver_cut(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint8_t* V, const uint64_t* v_off,
-                         uint32_t n_docs, uint32_t flags, uint8_t* out, uint64_t out_total, uint64_t* out_off, uint64_t* out_len,
-                         int32_t* status, hipStream_t s) {
+// (r->slot_total: the slots' extent, the kernels' out_total)
+int ygm_k_launch_ver_cut(const ygm_packed* S, const ygm_side* V, uint32_t n_docs, uint32_t flags, const ygm_results* r, hipStream_t s) {
   if (n_docs == 0) return 0;
-  hipLaunchKernelGGL(k_ver_cut, dim3(n_docs), dim3(VR_NT), 0, s, S, s_off, s_st, V, v_off, n_docs, flags, out, out_total, out_off, out_len,
-                     status);
+  hipLaunchKernelGGL(k_ver_cut, dim3(n_docs), dim3(VR_NT), 0, s, S->data, S->off, S->st, V->arena, V->off, n_docs, flags, r->out, r->slot_total,
+                     r->out_off, r->out_len, r->status);
   return ygm_launch_rc(__func__);
 }
 
-int ygm_k_launch_ver_cut_gather(const uint8_t* S, const uint64_t* s_off, const int32_t* s_st, const uint32_t* ix, const uint64_t* ask_base,
-                                const uint8_t* V, const uint64_t* v_off, uint32_t n_asks, uint32_t flags, uint8_t* out, uint64_t out_total,
-                                uint64_t* out_off, uint64_t* out_len, int32_t* status, hipStream_t s) {
+int ygm_k_launch_ver_cut_gather(const ygm_packed* S, const uint32_t* ix, const uint64_t* ask_base, const ygm_side* V, uint32_t n_asks,
+                                uint32_t flags, const ygm_results* r, hipStream_t s) {
   if (n_asks == 0) return 0;
-  hipLaunchKernelGGL(k_ver_cut_gather, dim3(n_asks), dim3(VR_NT), 0, s, S, s_off, s_st, ix, ask_base, V, v_off, n_asks, flags, out, out_total,
-                     out_off, out_len, status);
+  hipLaunchKernelGGL(k_ver_cut_gather, dim3(n_asks), dim3(VR_NT), 0, s, S->data, S->off, S->st, ix, ask_base, V->arena, V->off, n_asks, flags,
+                     r->out, r->slot_total, r->out_off, r->out_len, r->status);
   return ygm_launch_rc(__func__);
 }
 
