@@ -8,7 +8,7 @@ what the caps count, `expected_tier` restates the caps.  The corpus is plain dat
 {name: [batch, ...]}, a batch being a list of `Doc`s that go to the device together."""
 import random
 
-from test_lean_fast_parse import item, text, upd
+from lean_docs import item, text, upd
 from v1util import _skip_struct, encode_ds, rd_vu, read_ds, vu
 
 

@@ -29,7 +29,7 @@ Labels corrected against the kernel (the issue's first guess in brackets):
 Left out: overflow of the slow queue (vq_cap = npos_cap / 4 + 1024) and of npos_cap / ntask_cap.  All three are sized
 from the batch's own bytes with slack (big_scan_layout), so no input reaches them by construction."""
 from general_tier_docs import block, ch, chars, gc, padded, skip, struct_len, update
-from test_lean_fast_parse import item, text, upd
+from lean_docs import item, text, upd
 from v1util import _skip_struct, encode_ds, rd_vu, read_ds, vu
 
 # ---------------------------------------------------------------- the tier's constants

@@ -10,8 +10,12 @@ bytes and 16 order bytes, then 26 + 2 bytes a part), not read from the library. 
 (tests/golden/snapshot_tier_edges_v135.json.gz, written by tools/snap_fixture.py --tiers from `unique()`).
 
 `unique()` lists every distinct document once; the families D, E and F are batches of names over it."""
+import gzip
+import json
+import os
 import random
 
+from golden import ds_to_desc
 from v1util import encode_ds, vu
 
 TIERS = ("first", "second", "general", "pending", "throws")
@@ -459,3 +463,27 @@ def family_f(n, shift=0):
     """n documents: the seven tiny ones in turn."""
     f = families()["F"]
     return [f[(k + shift) % len(f)] for k in range(n)]
+
+
+# ---------------------------------------------------------------- the yjs fixture of the corpus
+FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "snapshot_tier_edges_v135.json.gz")
+_ROWS = None
+
+
+def rows():
+    """{name: (update, (yjs status, bytes), (status, bytes under gc: false))}, read once."""
+    global _ROWS
+    if _ROWS is None:
+        d = json.load(gzip.open(FIX, "rt"))
+        _ROWS = {n: (bytes.fromhex(u), (st, bytes.fromhex(e)), (st, bytes.fromhex(x) if x is not None else b"")) for n, u, st, e, x in d["rows"]}
+        assert len(_ROWS) == len(d["rows"])
+    return _ROWS
+
+
+def expected(d, compat135=True, nogc=False):
+    """What the engine answers: yjs's bytes (the delete set client-descending in the default mode), or the status of a
+    documented refusal."""
+    if d.name in UNSUPPORTED:
+        return (9, b"")
+    st, e = rows()[d.name][2 if nogc else 1]
+    return (st, e) if compat135 or st else (st, bytes.fromhex(ds_to_desc(e.hex())))

@@ -18,6 +18,7 @@ import re
 import numpy as np
 import pytest
 
+from devrun import engine_fixture, read_results
 from v1util import vu
 
 pytestmark = pytest.mark.gpu
@@ -40,12 +41,7 @@ def knobs(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng = engine_fixture(compat135=True)
 
 
 def letters(n, salt):
@@ -98,7 +94,6 @@ def run(eng, capfd, op, specs, lead):
     """One device call over documents specs = [(n characters | None for an empty document)], the first starting `lead`
     bytes into a 16-aligned arena -> [(status, bytes)], general count of the tier line."""
     import torch
-    import bench
     dev = torch.device("cuda", 0)
     mk = make(op)
     docs = [b"" if n is None else mk(n, k) for k, n in enumerate(specs)]
@@ -122,11 +117,7 @@ def run(eng, capfd, op, specs, lead):
     line = LINES[op.split("_")[0]].findall(capfd.readouterr().err)
     assert len(line) == 1, line
     general = int(line[0][3 if op != "json" else 1])
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])]) for d in range(n)], general
+    return read_results(r, n, sync=False, every=True), general
 
 
 def check(op, specs, res, general, what):

@@ -10,10 +10,10 @@ launch at the cost of exactly one more host wait; and a float document between a
 BigInt one."""
 import re
 
-import numpy as np
 import pytest
 
 import floats_fixture as ff
+from devrun import read_results, upload
 from hocuspocus_amd.engine import encode_fields
 
 pytestmark = pytest.mark.gpu
@@ -42,26 +42,14 @@ def engines():
 
 def device_call(eng, fn, states, seconds, kind=None):
     """One of the _device forms over arenas from torch -> [(status, bytes)]."""
-    import torch
-    import bench
-    dev = torch.device("cuda", 0)
-
-    def up(blobs):
-        a = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8).copy()
-        off = np.cumsum([0] + [len(b) for b in blobs]).astype(np.uint64)
-        return torch.from_numpy(a).to(dev), torch.from_numpy(off.view(np.int64).copy()).to(dev), int(off[-1])
-    ta, to, nbytes = up(states)
-    tn, tno, _ = up(seconds)
+    ta, to, nbytes = upload(states)
+    tn, tno, _ = upload(seconds)
     n = len(states)
     r = getattr(eng, fn)(ta, nbytes, to, tn, tno, n, *(() if kind is None else (kind,)))
-    torch.cuda.synchronize()
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
+    res, offs, lens = read_results(r, n, every=True, places=True)
     for d in range(n):
-        assert int(offs[d]) + int(lens[d]) <= int(r.data_bytes) and (sts[d] == 0 or lens[d] == 0)
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])]) for d in range(n)]
+        assert offs[d] + lens[d] <= int(r.data_bytes) and (res[d][0] == 0 or lens[d] == 0)
+    return res
 
 
 def plain(res):

@@ -5,7 +5,7 @@ import pytest
 
 import oracle
 import general_tier_docs as g
-from test_lean_fast_parse import upd
+from lean_docs import upd
 from v1util import encode_ds, rd_vu
 
 

@@ -11,7 +11,7 @@ import pytest
 
 import oracle
 import general_tier_docs as g
-from test_lean_fast_parse import run_device, same
+from devrun import engine_fixture, run_merge, same
 
 pytestmark = pytest.mark.gpu
 
@@ -27,31 +27,9 @@ def tier_counts(monkeypatch):
     monkeypatch.delenv("YGM_FAST_GRID", raising=False)
 
 
-def _engine(**kw):
-    from hocuspocus_amd import Engine
-    return Engine(0, **kw)
-
-
-@pytest.fixture(scope="module")
-def eng():
-    e = _engine()
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng135():
-    e = _engine(compat135=True)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng_seq():
-    e = _engine(force_seq=True)
-    yield e
-    e.close()
-
+eng = engine_fixture()
+eng135 = engine_fixture(compat135=True)
+eng_seq = engine_fixture(force_seq=True)
 
 _ORACLE = {}
 
@@ -69,7 +47,7 @@ def run_counted(eng, capfd, docs, form):
     capfd.readouterr()
     s = eng.stats()
     before = (s.docs_lean, s.docs_fast, s.docs_seq, s.host_syncs)
-    res, _ = run_device(eng, [d.us for d in docs], form)
+    res, _ = run_merge(eng, [d.us for d in docs], form)
     s = eng.stats()
     after = (s.docs_lean, s.docs_fast, s.docs_seq, s.host_syncs)
     lines = LINE.findall(capfd.readouterr().err)

@@ -6,46 +6,18 @@ import numpy as np
 import pytest
 
 import oracle
+from devrun import THROWS, engine_fixture, read_results, same
 from golden import case_inputs, check_result, load_yjs_vectors
 from hocuspocus_amd.engine import EMALFORMED
 
 pytestmark = pytest.mark.gpu
 
 HEADER, CASES = load_yjs_vectors()
-THROWS = {1, 2, 4, 5}
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng_seq():
-    from hocuspocus_amd import Engine
-    e = Engine(0, force_seq=True)
-    yield e
-    e.close()
-
-
-def same(oracle_res, gpu_res):
-    """statuses agree (any throw == any throw) and bytes agree when OK."""
-    so, bo = oracle_res
-    sg, bg = gpu_res
-    if so in THROWS:
-        return sg in THROWS
-    return so == sg and bo == bg
+eng = engine_fixture()
+eng135 = engine_fixture(compat135=True)
+eng_seq = engine_fixture(force_seq=True)
 
 
 def run_batch(e, op, cases):
@@ -424,16 +396,11 @@ def test_async_device_api_matches_host_api(eng):
     for _ in range(2):   # the second enqueue reuses the context's buffers
         eng.merge_device_async(ta.data_ptr(), len(a) - 64, to.data_ptr(), td.data_ptr(), len(blobs), len(docs))
     r = eng.merge_device_finish()
-    torch.cuda.synchronize()
-    import bench
     n = len(docs)
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
+    res = read_results(r, n)
     host = eng.merge_updates_batch(docs)
     for d in range(n):
-        got = (int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])] if sts[d] == 0 else None)
+        got = res[d]
         assert got[0] == host[d][0] and (got[0] != 0 or got[1] == host[d][1]), d
     assert r.payload_bytes == sum(len(h[1]) for h in host if h[0] == 0)
 
@@ -443,7 +410,6 @@ def _lens_check(eng, docs, bad_lens):
     # holding a changed update get YGM_EMALFORMED on every route (the single-update check, the lean kernels, the
     # empty updates k_build_off leaves to the general tiers), every other one the host API's result
     import torch
-    import bench
     blobs = [u for us in docs for u in us]
     assert max(len(b) for b in blobs) < 65536
     a = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)
@@ -459,13 +425,9 @@ def _lens_check(eng, docs, bad_lens):
     host = eng.merge_updates_batch(docs)
     for _ in range(2):   # the second call reuses the context's buffers
         r = eng.merge_device_lens(ta.data_ptr(), len(a) - 64, to.data_ptr(), tl.data_ptr(), td.data_ptr(), len(blobs), n)
-        torch.cuda.synchronize()
-        offs = bench._d2h(r.off, n * 8).view(np.uint64)
-        ln = bench._d2h(r.len, n * 8).view(np.uint64)
-        sts = bench._d2h(r.status, n * 4).view(np.int32)
-        data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
+        res = read_results(r, n)
         for d in range(n):
-            got = (int(sts[d]), data[int(offs[d]):int(offs[d]) + int(ln[d])] if sts[d] == 0 else None)
+            got = res[d]
             if d in bad:
                 assert got[0] == EMALFORMED, (d, got[0])
             else:
@@ -475,7 +437,6 @@ def _lens_check(eng, docs, bad_lens):
 def _device_merge(eng, docs):
     # docs through ygm_merge_v1_device: (status, bytes) per document, and the call's host waits (ygm_stats host_syncs)
     import torch
-    import bench
     blobs = [u for us in docs for u in us]
     a = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)
     off = np.cumsum([0] + [len(b) for b in blobs]).astype(np.uint64)
@@ -487,13 +448,7 @@ def _device_merge(eng, docs):
     s1 = eng.stats()
     syncs = {"syncs": s1.host_syncs - s0.host_syncs, "general": (s1.docs_fast - s0.docs_fast) + (s1.docs_big - s0.docs_big),
              "large_or_seq": (s1.docs_big - s0.docs_big) + (s1.docs_seq - s0.docs_seq)}
-    torch.cuda.synchronize()
-    n = len(docs)
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])] if sts[d] == 0 else None) for d in range(n)], syncs
+    return read_results(r, len(docs)), syncs
 
 
 def test_host_syncs_per_merge_call(eng):

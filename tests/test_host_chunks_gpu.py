@@ -13,6 +13,8 @@ import pytest
 
 import oracle
 import text_fixture as tf
+from devrun import engine_fixture
+from golden import contains_fixtures, history_docs
 from v1util import rd_vu, vu
 
 pytestmark = pytest.mark.gpu
@@ -21,12 +23,7 @@ MB = 1 << 20
 EMPTY = bytes.fromhex("0000")   # the update of a document with no structs and no deletions
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
+eng = engine_fixture()
 
 
 def _fill(rows, size):
@@ -124,7 +121,6 @@ def test_diff_v1_chunked(eng, monkeypatch, logs):
 
 
 def test_contains_chunked(eng, monkeypatch):
-    from test_snapshot import contains_fixtures
     rows = _fill(contains_fixtures(), lambda r: len(r[0]))
     ref = _pin(eng, monkeypatch, lambda: eng.contains_batch([r[0] for r in rows], [r[1] for r in rows]))
     assert ref == [(0, r[2]) for r in rows]
@@ -144,7 +140,6 @@ def _scaled_sv(sv, num, den):
 def test_diff_shared_chunked(eng, monkeypatch):
     """Three updates, the middle one about 300 KB with six asks: 2.1 MB of virtual bytes, so it is split over chunks
     that each stage it again; small ones before and after it."""
-    from test_version_shared import history_docs
     docs = history_docs()
     big = [d for d in docs if d["family"] == "large"][0]["state"]
     small = [d["state"] for d in docs if d["family"] == "clients"][:2]

@@ -16,6 +16,7 @@ import pytest
 
 import json_fields_fixture as ff
 import json_fixture as jf
+from devrun import engine_fixture, read_results, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -46,12 +47,7 @@ def knobs(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng = engine_fixture(compat135=True)
 
 
 def tier_lines(capfd):
@@ -78,25 +74,11 @@ def call(eng, capfd, states, lists, api, lead=0):
         assert all(s == 0 or not b for s, b in got)
         res = [(s, b if s == 0 else b"") for s, b in got]
     else:
-        import torch
-        import bench
-        dev = torch.device("cuda", 0)
-
-        def up(blobs, lead):
-            a = np.frombuffer(b"\xee" * lead + b"".join(blobs) + bytes(64), np.uint8).copy()
-            off = (lead + np.cumsum([0] + [len(b) for b in blobs])).astype(np.uint64)
-            return torch.from_numpy(a).to(dev), torch.from_numpy(off.view(np.int64).copy()).to(dev), int(off[-1])
-        ta, to, nbytes = up(states, 0)
-        tf, tfo, _ = up(lists, lead)
+        ta, to, nbytes = upload(states)
+        tf, tfo, _ = upload(lists, lead=lead)
         r = eng.json_fields_device(ta, nbytes, to, tf, tfo, n)
-        torch.cuda.synchronize()
-        offs = [int(x) for x in bench._d2h(r.off, n * 8).view(np.uint64)]
-        lens = [int(x) for x in bench._d2h(r.len, n * 8).view(np.uint64)]
-        sts = bench._d2h(r.status, n * 4).view(np.int32)
-        data_bytes = int(r.data_bytes)
-        assert all(offs[d] + lens[d] <= data_bytes for d in range(n))
-        data = bench._d2h(r.data, data_bytes).tobytes()
-        res = [(int(sts[d]), data[offs[d]:offs[d] + lens[d]]) for d in range(n)]
+        res, offs, lens = read_results(r, n, every=True, places=True)
+        assert all(offs[d] + lens[d] <= int(r.data_bytes) for d in range(n))
         assert int(r.payload_bytes) == sum(len(b) for st, b in res if st == 0)
     lines = tier_lines(capfd)
     assert jf.ST_MORE not in {st for st, _ in res}

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import json_fixture as jf
+from devrun import engine_fixture, read_results, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +29,7 @@ def knobs(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng = engine_fixture(compat135=True)
 
 
 def host_json(eng, states, names):
@@ -42,27 +38,15 @@ def host_json(eng, states, names):
 
 def device_json(eng, states, names):
     """ygm_json_v1_device over arenas from torch -> (status, bytes) pairs."""
-    import torch
-    import bench
-    dev = torch.device("cuda", 0)
-
-    def up(blobs):
-        a = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)
-        off = np.cumsum([0] + [len(b) for b in blobs]).astype(np.uint64)
-        return torch.from_numpy(a.copy()).to(dev), torch.from_numpy(off.view(np.int64).copy()).to(dev), len(a) - 64
-    ta, to, nbytes = up(states)
-    tn, tno, _ = up(names)
+    ta, to, nbytes = upload(states)
+    tn, tno, _ = upload(names)
     n = len(states)
     r = eng.json_device(ta, nbytes, to, tn, tno, n)
-    torch.cuda.synchronize()
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    assert int(r.payload_bytes) == int(sum(int(lens[d]) for d in range(n) if sts[d] == 0))
+    res, offs, lens = read_results(r, n, every=True, places=True)
+    assert int(r.payload_bytes) == sum(lens[d] for d in range(n) if res[d][0] == 0)
     for d in range(n):
-        assert int(offs[d]) + int(lens[d]) <= int(r.data_bytes) and (sts[d] == 0 or lens[d] == 0)
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])]) for d in range(n)]
+        assert offs[d] + lens[d] <= int(r.data_bytes) and (res[d][0] == 0 or lens[d] == 0)
+    return res
 
 
 def run(eng, capfd, states, names, api="batch"):

@@ -11,11 +11,11 @@ root names of 1, 7 and 130 bytes; the yjs-made boundary sessions.  Every compari
 import collections
 import re
 
-import numpy as np
 import pytest
 
 import json_fixture as jf
 import json_overflow_docs as g
+from devrun import engine_fixture, read_results, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -35,12 +35,7 @@ def knobs(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng = engine_fixture(compat135=True)
 
 
 def call(eng, capfd, states, names, api, lead=0):
@@ -54,26 +49,13 @@ def call(eng, capfd, states, names, api, lead=0):
         res = [(0, r) if isinstance(r, bytes) else (r.code, b"") for r in eng.json_batch(states, names)]
         offs = lens = data_bytes = None
     else:
-        import torch
-        import bench
-        dev = torch.device("cuda", 0)
-
-        def up(blobs, lead):
-            a = np.frombuffer(b"\xee" * lead + b"".join(blobs) + bytes(64), np.uint8).copy()
-            off = (lead + np.cumsum([0] + [len(b) for b in blobs])).astype(np.uint64)
-            return torch.from_numpy(a).to(dev), torch.from_numpy(off.view(np.int64).copy()).to(dev), int(off[-1])
-        ta, to, nbytes = up(states, lead)
-        tn, tno, _ = up(names, 0)
+        ta, to, nbytes = upload(states, lead=lead)
+        tn, tno, _ = upload(names)
         assert ta.data_ptr() % 16 == 0
         r = eng.json_device(ta, nbytes, to, tn, tno, n)
-        torch.cuda.synchronize()
-        offs = [int(x) for x in bench._d2h(r.off, n * 8).view(np.uint64)]
-        lens = [int(x) for x in bench._d2h(r.len, n * 8).view(np.uint64)]
-        sts = bench._d2h(r.status, n * 4).view(np.int32)
+        res, offs, lens = read_results(r, n, every=True, places=True)
         data_bytes = int(r.data_bytes)
         assert all(offs[d] + lens[d] <= data_bytes for d in range(n))
-        data = bench._d2h(r.data, data_bytes).tobytes()
-        res = [(int(sts[d]), data[offs[d]:offs[d] + lens[d]]) for d in range(n)]
         assert lens == [len(b) for _, b in res]
         assert int(r.payload_bytes) == sum(len(b) for st, b in res if st == 0)
     lines = [dict(zip(("docs", "general", "overflow", "overflow_bytes"), map(int, ln))) for ln in JSON_LINE.findall(capfd.readouterr().err)]

@@ -9,12 +9,11 @@ order, batch sequences on one fresh context (the tier's scratch, bitmap and seco
 call), and the sequential replay."""
 import re
 
-import numpy as np
 import pytest
 
 import oracle
 import large_tier_docs as g
-from test_lean_fast_parse import _unpack, same
+from devrun import engine_fixture, run_merge, same
 
 pytestmark = pytest.mark.gpu
 
@@ -44,44 +43,14 @@ def _engine(**kw):
     return Engine(0, **kw)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    e = _engine()
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng135():
-    e = _engine(compat135=True)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng_seq():
-    e = _engine(force_seq=True)
-    yield e
-    e.close()
+eng = engine_fixture()
+eng135 = engine_fixture(compat135=True)
+eng_seq = engine_fixture(force_seq=True)
 
 
 def run_device(eng, docs, form):
     """docs through the u64-offset device API ('off') or the compact one ('lens': 16-bit update lengths)."""
-    import torch
-    blobs = [u for us in docs for u in us]
-    a = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)
-    off = np.cumsum([0] + [len(b) for b in blobs]).astype(np.uint64)
-    du = np.cumsum([0] + [len(us) for us in docs]).astype(np.uint32)
-    dev = torch.device("cuda", 0)
-    ta, td = torch.from_numpy(a.copy()).to(dev), torch.from_numpy(du.view(np.int32).copy()).to(dev)
-    if form == "off":
-        to = torch.from_numpy(off.view(np.int64).copy()).to(dev)
-        r = eng.merge_device(ta.data_ptr(), len(a) - 64, to.data_ptr(), td.data_ptr(), len(blobs), len(docs))
-    else:
-        lens = np.array([len(b) for b in blobs], np.uint16)
-        tl, tdo = torch.from_numpy(lens.view(np.int16).copy()).to(dev), torch.from_numpy(off[du].view(np.int64).copy()).to(dev)
-        r = eng.merge_device_lens(ta.data_ptr(), len(a) - 64, tdo.data_ptr(), tl.data_ptr(), td.data_ptr(), len(blobs), len(docs))
-    return _unpack(r, len(docs))
+    return run_merge(eng, docs, form)[0]
 
 
 def forms_of(docs):

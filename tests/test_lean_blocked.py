@@ -5,7 +5,8 @@ oracle, and every test asserts how many documents the lean kernels finished, so 
 import pytest
 
 import oracle
-from test_lean_fast_parse import CLIENTS, Log, fast_doc, item, run_device, same, text, upd
+from devrun import Memo, engine_fixture, run_merge, same
+from lean_docs import CLIENTS, Log, _ds, fast_doc, item, text, upd
 from v1util import vu
 
 pytestmark = pytest.mark.gpu
@@ -13,35 +14,15 @@ pytestmark = pytest.mark.gpu
 FORMS = ["off", "lens"]
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
-
-
-_ORACLE = {}
-
-
-def expect(key, docs, compat135=False):
-    """The oracle's results of a corpus, computed once and shared."""
-    if key not in _ORACLE:
-        _ORACLE[key] = [oracle.merge_updates(us, compat135=True) if compat135 else oracle.merge_updates(us) for us in docs]
-    return _ORACLE[key]
+eng = engine_fixture()
+eng135 = engine_fixture(compat135=True)
+MEMO = Memo()
+expect = MEMO.expect
 
 
 def check(e, exp, docs, form, lean, wide=None):
     w0 = e.stats().docs_lean_wide
-    res, took = run_device(e, docs, form)
+    res, took = run_merge(e, docs, form)
     bad = [d for d in range(len(docs)) if not same(exp[d], res[d])]
     assert not bad, (form, len(bad), bad[:5], [u.hex() for u in docs[bad[0]]][:8])
     assert took == lean, (form, took, lean)
@@ -133,14 +114,6 @@ def test_long_update_at_the_boundaries_takes_the_wide_kernel(eng):
 
 
 # ---- 3. delete-set order under yjs 13.5 semantics: clients in first-seen order, by (update, position in its delete set)
-def _ds(entries):
-    """A delete set: entries = [(client, [(clock, len), ...]), ...]."""
-    b = vu(len(entries))
-    for cl, rs in entries:
-        b += vu(cl) + vu(len(rs)) + b"".join(vu(ck) + vu(ln) for ck, ln in rs)
-    return b
-
-
 def _ds_doc(k, at, seed):
     """k updates of clients A / B; the updates at the positions `at` carry delete sets.  Delete-set clients are first
     seen in ascending order of their ids (the sorted order is descending), two new ones per update, the second update
@@ -216,9 +189,7 @@ def _seq_doc(d):
 
 
 def _seq_corpus():
-    if "seq_docs" not in _ORACLE:
-        _ORACLE["seq_docs"] = [_seq_doc(d) for d in range(N_SEQ)]
-    docs = _ORACLE["seq_docs"]
+    docs = MEMO.get("seq_docs", lambda: [_seq_doc(d) for d in range(N_SEQ)])
     return docs, expect("seq", docs)
 
 

@@ -12,8 +12,8 @@ import itertools
 import pytest
 
 import oracle
-from test_lean_fast_parse import Log, fast_doc, item, run_device, same, upd
-from test_lean_logorder import _deletion_docs, _ds, _longest
+from devrun import Memo, engine_fixture, run_merge, same
+from lean_docs import Log, _deletion_docs, _ds, _longest, fast_doc, item, overlong, upd
 from v1util import vu
 
 pytestmark = pytest.mark.gpu
@@ -23,37 +23,17 @@ SMALL = [5, 9, 70, 200]
 BIG = [3000000001, 77, 2 ** 31 + 5, 12345]
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
-
-
-_ORACLE = {}
-
-
-def expect(key, docs, compat135=False):
-    """The oracle's results of a corpus, computed once and shared."""
-    if key not in _ORACLE:
-        _ORACLE[key] = [oracle.merge_updates(us, compat135=True) if compat135 else oracle.merge_updates(us) for us in docs]
-    return _ORACLE[key]
+eng = engine_fixture()
+eng135 = engine_fixture(compat135=True)
+MEMO = Memo()
+expect = MEMO.expect
 
 
 def check(e, exp, docs, lean=None, wide=None):
     """Both input forms: exact against exp; `lean` documents finished by the lean kernels, `wide` of them by the wide one."""
     for form in FORMS:
         w0 = e.stats().docs_lean_wide
-        res, took = run_device(e, docs, form)
+        res, took = run_merge(e, docs, form)
         bad = [d for d in range(len(docs)) if not same(exp[d], res[d])]
         assert not bad, (form, len(bad), bad[:5], [u.hex() for u in docs[bad[0]]][:8])
         if lean is not None:
@@ -292,10 +272,6 @@ def fields(shape, c, ck, o=(B, 2), r=(B, 1), key=b"t", s=b"\x01q", ds=b"\x00"):
     return f, vus
 
 
-def overlong(b):
-    return b[:-1] + bytes([b[-1] | 0x80, 0])
-
-
 def wrap(c, ck, u, clen=1):
     """A document around the update u (client c, clock ck + 1): a first insert before it, two plain ones after."""
     first = upd(c, ck, [item(4, b"\x01a")])
@@ -382,14 +358,13 @@ def _kind_doc(kind, j):
 def _loop_corpus(n):
     """Document d of wave w = d % GRID, round r = d // GRID is of kind (w + (0, 1, 0)[r]) % 3: over three rounds every wave
     steps one kind up and one kind down, and the waves between them start at every kind."""
-    if "pool" not in _ORACLE:
-        _ORACLE["pool"] = [[_kind_doc(kind, j) for j in range(POOL)] for kind in range(3)]
-        _ORACLE["pool_exp"] = [[oracle.merge_updates(us) for us in row] for row in _ORACLE["pool"]]
+    pool = MEMO.get("pool", lambda: [[_kind_doc(kind, j) for j in range(POOL)] for kind in range(3)])
+    pool_exp = MEMO.get("pool_exp", lambda: [[oracle.merge_updates(us) for us in row] for row in pool])
     docs, exp, lean = [], [], 0
     for d in range(n):
         kind = (d % GRID + (0, 1, 0)[(d // GRID) % 3]) % 3
-        docs.append(_ORACLE["pool"][kind][d % POOL])
-        exp.append(_ORACLE["pool_exp"][kind][d % POOL])
+        docs.append(pool[kind][d % POOL])
+        exp.append(pool_exp[kind][d % POOL])
         lean += kind != 2
     return docs, exp, lean
 

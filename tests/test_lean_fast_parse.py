@@ -5,155 +5,22 @@ with the CPU oracle; the tests describe behaviour (what is finished by the lean 
 the kernel parses."""
 import random
 
-import numpy as np
 import pytest
 
-import oracle
+from devrun import Memo, engine_fixture, run_merge, same
+from lean_docs import CLIENTS, Log, fast_doc, item, text, upd
 from v1util import vu
 
 pytestmark = pytest.mark.gpu
 
-THROWS = {1, 2, 4, 5}
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-# ---- a sequential log generator: every client's clocks stay contiguous unless a test shifts them
-def item(info_ref, content, origin=None, right=None, parent=None, sub=None, flag20=False):
-    """One struct: info byte, origins / parent, content bytes."""
-    info = info_ref | (0x80 if origin else 0) | (0x40 if right else 0) | (0x20 if (sub is not None or flag20) else 0)
-    b = bytes([info])
-    for o in (origin, right):
-        if o:
-            b += o if isinstance(o, bytes) else vu(o[0]) + vu(o[1])
-    if not origin and not right:
-        b += parent if parent is not None else b"\x01\x01t"
-        if sub is not None:
-            b += vu(len(sub)) + sub
-    return b + content
-
-
-def text(s):
-    raw = s.encode()
-    return vu(len(raw)) + raw
-
-
-def upd(client, clock, structs, ds=b"\x00", nst=None):
-    cl = client if isinstance(client, bytes) else vu(client)
-    ck = clock if isinstance(clock, bytes) else vu(clock)
-    return vu(1) + vu(len(structs) if nst is None else nst) + cl + ck + b"".join(structs) + ds
-
-
-class Log:
-    """A document's log in the C2 shape: the first update inserts under the parent key 't', every later one is one
-    character with an origin (and, every third, a right origin too) pointing at earlier characters."""
-
-    def __init__(self, clients, clocks=None, seed=0):
-        self.clients = list(clients)
-        self.clock = dict(zip(self.clients, clocks or [0] * len(self.clients)))
-        self.rng = random.Random(seed)
-        self.ups = []
-        self.last = None     # (client, clock) of the latest character
-
-    def plain(self, c):
-        """The fast shape: one ASCII character."""
-        ch = self.rng.choice("abcdefghijklmnopqrstuvwxyz")
-        if self.last is None:
-            s = item(4, text(ch))
-        elif len(self.ups) % 3 == 2:
-            s = item(4, text(ch), origin=self.last, right=(self.clients[0], self.clock[self.clients[0]] // 2))
-        elif len(self.ups) % 7 == 5:
-            s = item(4, text(ch), right=self.last)
-        else:
-            s = item(4, text(ch), origin=self.last)
-        self.put(c, [s], 1)
-
-    def put(self, c, structs, clen, ds=b"\x00", shift=0, tail=b"", client_bytes=None, clock_bytes=None):
-        ck = self.clock[c] + shift
-        self.ups.append(upd(client_bytes or c, clock_bytes or ck, structs, ds) + tail)
-        if clen:
-            self.last = (c, ck + clen - 1)
-        self.clock[c] = ck + clen
-
-    def raw(self, u):
-        self.ups.append(u)
-
-
-def fast_doc(k, clients, clocks=None, seed=0, order=None):
-    """k plain updates; order(i) -> client index of update i (default: round robin)."""
-    g = Log(clients, clocks, seed)
-    for i in range(k):
-        g.plain(clients[order(i) if order else i % len(clients)])
-    return g.ups
-
-
-CLIENTS = [3000000001, 77, 2 ** 31 + 5, 12345, 999, 4000000000, 2, 65536]
-
-
-def same(o, g):
-    so, bo = o
-    sg, bg = g
-    if so in THROWS:
-        return sg in THROWS
-    return so == sg and bo == bg
-
-
-def _pack(docs):
-    blobs = [u for us in docs for u in us]
-    a = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)
-    lens = np.array([len(b) for b in blobs], np.uint16)
-    off = np.cumsum([0] + [len(b) for b in blobs]).astype(np.uint64)
-    du = np.cumsum([0] + [len(us) for us in docs]).astype(np.uint32)
-    doff = off[du]
-    return blobs, a, lens, off, du, doff
-
-
-def _unpack(r, n):
-    import torch
-    import bench
-    torch.cuda.synchronize()
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    ln = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(ln[d])] if sts[d] == 0 else None) for d in range(n)]
-
-
-def run_device(eng, docs, form):
-    """docs through the u64-offset device API ('off') or the compact one ('lens'): results, documents finished lean."""
-    import torch
-    blobs, a, lens, off, du, doff = _pack(docs)
-    dev = torch.device("cuda", 0)
-    ta, to, tl, td, tdo = (torch.from_numpy(x.copy()).to(dev) for x in
-                           (a, off.view(np.int64), lens.view(np.int16), du.view(np.int32), doff.view(np.int64)))
-    lean0 = eng.stats().docs_lean
-    if form == "off":
-        r = eng.merge_device(ta.data_ptr(), len(a) - 64, to.data_ptr(), td.data_ptr(), len(blobs), len(docs))
-    else:
-        r = eng.merge_device_lens(ta.data_ptr(), len(a) - 64, tdo.data_ptr(), tl.data_ptr(), td.data_ptr(), len(blobs), len(docs))
-    res = _unpack(r, len(docs))
-    return res, eng.stats().docs_lean - lean0
-
-
-_ORACLE = {}
-
-
-def expect(key, docs):
-    """The oracle's results of a corpus, computed once."""
-    if key not in _ORACLE:
-        _ORACLE[key] = [oracle.merge_updates(us) for us in docs]
-    return _ORACLE[key]
+eng = engine_fixture()
+MEMO = Memo()
+expect = MEMO.expect
 
 
 def check(eng, key, docs, form, lean=None):
     exp = expect(key, docs)
-    res, took = run_device(eng, docs, form)
+    res, took = run_merge(eng, docs, form)
     bad = [d for d in range(len(docs)) if not same(exp[d], res[d])]
     assert not bad, (key, form, len(bad), bad[:5], [u.hex() for u in docs[bad[0]]][:8])
     if lean is not None:

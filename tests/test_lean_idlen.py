@@ -22,8 +22,8 @@ import subprocess
 
 import pytest
 
-import oracle
-from test_lean_fast_parse import Log, item, run_device, same, text, upd
+from devrun import Memo, run_merge, same
+from lean_docs import Log, _ds_only, item, text
 from v1util import vu
 
 gpu = pytest.mark.gpu
@@ -49,18 +49,13 @@ def engs():
     e.close()
 
 
-_ORACLE = {}
-
-
-def expect(key, docs):
-    if key not in _ORACLE:
-        _ORACLE[key] = [oracle.merge_updates(us) for us in docs]
-    return _ORACLE[key]
+MEMO = Memo()
+expect = MEMO.expect
 
 
 def run(e, docs, form):
     wide0 = e.stats().docs_lean_wide
-    res, lean = run_device(e, docs, form)
+    res, lean = run_merge(e, docs, form)
     return res, lean, e.stats().docs_lean_wide - wide0
 
 
@@ -224,10 +219,6 @@ def test_info_bytes_and_origins_of_another_id_length(engs):
 
 
 # ======================================================================= shapes
-def _ds(client, clock, n=1):
-    return b"\x00\x01" + vu(client) + b"\x01" + vu(clock) + vu(n)
-
-
 def _ds_docs():
     docs = []
     for c, dc in ((F5[0], F5[0]), (F5[1], F4[0]), (F5[2], 77)):       # the delete set names a client of any id length
@@ -237,7 +228,7 @@ def _ds_docs():
             for i in range(k):
                 dso = {"first": i == 0, "last": i == k - 1, "between": i in (2, 3, 5), "most": i != 4}[where]
                 if dso:
-                    g.raw(_ds(dc, i))
+                    g.raw(_ds_only(dc, i))
                 else:
                     g.put(c, [item(4, text("d"), origin=g.last)], 1)
             docs.append(g.ups)

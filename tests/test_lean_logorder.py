@@ -9,7 +9,8 @@ forms, and the documents inside the envelope must be finished by the lean kernel
 import pytest
 
 import oracle
-from test_lean_fast_parse import Log, fast_doc, item, run_device, same, upd
+from devrun import Memo, engine_fixture, run_merge, same
+from lean_docs import A, B, C, Log, _deletion_doc, _deletion_docs, _longest, fast_doc, item, text1
 from v1util import vu
 
 pytestmark = pytest.mark.gpu
@@ -20,37 +21,17 @@ BIG = [3000000001, 77, 2 ** 31 + 5, 12345, 999, 4000000000, 2, 65536, 424242]
 LN_IN, LN_OUT = 5120, 4096                       # the narrow kernel's staged input / output bytes
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
-
-
-_ORACLE = {}
-
-
-def expect(key, docs, compat135=False):
-    """The oracle's results of a corpus, computed once and shared."""
-    if key not in _ORACLE:
-        _ORACLE[key] = [oracle.merge_updates(us, compat135=True) if compat135 else oracle.merge_updates(us) for us in docs]
-    return _ORACLE[key]
+eng = engine_fixture()
+eng135 = engine_fixture(compat135=True)
+MEMO = Memo()
+expect = MEMO.expect
 
 
 def check(e, exp, docs, lean=None, wide=None):
     """Both input forms: exact against exp; `lean` documents finished by the lean kernels, `wide` of them by the wide one."""
     for form in FORMS:
         w0 = e.stats().docs_lean_wide
-        res, took = run_device(e, docs, form)
+        res, took = run_merge(e, docs, form)
         bad = [d for d in range(len(docs)) if not same(exp[d], res[d])]
         assert not bad, (form, len(bad), bad[:5], [u.hex() for u in docs[bad[0]]][:8])
         if lean is not None:
@@ -62,10 +43,6 @@ def check(e, exp, docs, lean=None, wide=None):
 def narrow(us):
     """The document is staged whole by the narrow kernel wherever the batch puts it."""
     return 2 <= len(us) <= 255 and all(len(u) <= 32 for u in us) and sum(len(u) for u in us) + 15 <= LN_IN
-
-
-def text1(ch="q"):
-    return b"\x01" + ch.encode()
 
 
 # ---- client count: 1 - 4 (log order; one byte scan up to two clients, two above), 5 and 8 (sorted domain), 9 (deferred)
@@ -189,9 +166,6 @@ def test_clock_past_the_largest_defers_and_is_exact(eng):
 
 
 # ---- rows and lanes: one slow row among fast ones; deletions between inserts; lanes holding only deletions
-A, B, C = 5, 9, 70
-
-
 def _slow_row_doc(ncl, at, shape, seed):
     ids = [A, B, C][:ncl]
     g = Log(ids, [5] * ncl, seed)
@@ -222,40 +196,6 @@ def test_one_slow_row_takes_the_sorted_domain(eng, shape):
     check(eng, exp, docs, lean=len(docs), wide=0)
 
 
-def _ds(entries):
-    b = vu(len(entries))
-    for cl, rs in entries:
-        b += vu(cl) + vu(len(rs)) + b"".join(vu(ck) + vu(ln) for ck, ln in rs)
-    return b
-
-
-def _deletion_doc(ncl, k, dels, empty, seed):
-    """k updates; the ones at the positions `dels` are deletions (no structs).  empty: their delete sets hold nothing
-    (the union is empty); else one range each, of client ids in ascending order of first sight."""
-    ids = [A, B, C, 200][:ncl]
-    g = Log(ids, [5] * ncl, seed)
-    n = 0
-    for j in range(k):
-        if j in dels:
-            g.raw(b"\x00\x00" if empty else b"\x00" + _ds([(ids[n % ncl] if n % 3 else 300 + n, [(5 + 2 * n, 1)])]))
-            n += 1
-        else:
-            g.plain(ids[(j * 7 // 3) % ncl])
-    return g.ups
-
-
-def _deletion_docs():
-    docs = []
-    for ncl in (1, 2, 3, 4):
-        for empty in (False, True):
-            docs.append(_deletion_doc(ncl, 90, {1, 2, 30, 63, 64, 89}, empty, 1))                       # between inserts
-            docs.append(_deletion_doc(ncl, 90, set(range(8, 12)) | set(range(40, 48)), empty, 2))      # lanes 2, 10, 11: only deletions
-            docs.append(_deletion_doc(ncl, 90, set(range(0, 8)) | set(range(84, 90)), empty, 3))       # the first two lanes, the last lanes
-            docs.append(_deletion_doc(ncl, 61, set(range(6, 61)) - {33}, empty, 4))                    # nearly all deletions
-            docs.append(_deletion_doc(ncl, 40, set(range(40)), empty, 5))                              # no structs at all
-    return docs
-
-
 def test_deletions_between_inserts(eng):
     docs = _deletion_docs()
     assert all(narrow(us) for us in docs)
@@ -274,14 +214,6 @@ def test_deletions_first_seen_order_under_compat135(eng135):
 
 
 # ---- block byte totals: the longest fast shape (a 32-byte update: parent key, one character)
-def _longest(c, ck):
-    pre = len(vu(1) + vu(1) + vu(c) + vu(ck))
-    key = b"k" * (32 - pre - 1 - 5)      # info, parentInfo, key length, key, string length, character; the delete set's 0
-    u = upd(c, ck, [item(4, text1("x"), parent=b"\x01" + vu(len(key)) + key)])
-    assert len(u) == 32
-    return u
-
-
 def _longest_doc(per_client, ncl):
     return [_longest([A, B][j % ncl], 3 + j // ncl) for j in range(per_client * ncl)]
 
@@ -334,9 +266,7 @@ def _mix_doc(d):
 
 
 def _mix_corpus():
-    if "mix_docs" not in _ORACLE:
-        _ORACLE["mix_docs"] = [_mix_doc(d) for d in range(N_MIX)]
-    docs = _ORACLE["mix_docs"]
+    docs = MEMO.get("mix_docs", lambda: [_mix_doc(d) for d in range(N_MIX)])
     return docs, expect("mix", docs)
 
 

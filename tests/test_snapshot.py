@@ -13,55 +13,15 @@ in 13.5 compat mode (the bundle's behaviour).  The 13.6 default writes the delet
 order instead of store order (the only difference in a snapshot's bytes): the default mode is
 pinned against the same yjs vectors with their delete sets rewritten client-descending (golden.ds_to_desc) --
 a derived expectation, as no 13.6 yjs is in the image."""
-import gzip
-import json
 import os
 import shutil
-import struct
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIX = os.path.join(ROOT, "tests", "golden", "snapshot_v135.json.gz")
-NODE = shutil.which("node")
-BUNDLE = os.path.exists("/opt/conda/share/jupyter/lab/static/3502.fbe0c610be82ba1360db.js")
-
-
-def fixtures():
-    d = json.load(gzip.open(FIX, "rt"))
-    return [(bytes.fromhex(u), bytes.fromhex(e)) for u, e in d["rows"]]
-
-
-def write_in(path, us):
-    with open(path, "wb") as f:
-        f.write(struct.pack("<I", len(us)))
-        for u in us:
-            f.write(struct.pack("<I", len(u)))
-            f.write(u)
-
-
-def read_res(path):
-    b = open(path, "rb").read()
-    i, out = 0, []
-    while i < len(b):
-        st, ln = struct.unpack_from("<iI", b, i)
-        i += 8
-        out.append((st, b[i:i + ln]))
-        i += ln
-    return out
-
-
-def read_in(path):
-    b = open(path, "rb").read()
-    n = struct.unpack_from("<I", b, 0)[0]
-    i, out = 4, []
-    for _ in range(n):
-        ln = struct.unpack_from("<I", b, i)[0]
-        i += 4
-        out.append(b[i:i + ln])
-        i += ln
-    return out
+from devrun import engine_fixture
+from golden import contains_fixtures, contains_pending_fixtures, fixtures, pending_fixtures, subdoc_fixtures, text_fixtures
+from twins import BUNDLE, NODE, ROOT, _resolve_pending, read_in, read_res, write_in
 
 
 def test_fixtures_present():
@@ -187,14 +147,6 @@ def test_gpu_snapshot_at_baseline_sizes(eng135, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------- flat text (k_snap_text)
-TFIX = os.path.join(ROOT, "tests", "golden", "snapshot_text_v135.json.gz")
-
-
-def text_fixtures():
-    d = json.load(gzip.open(TFIX, "rt"))
-    return [(bytes.fromhex(u), bytes.fromhex(e)) for u, e in d["rows"]]
-
-
 def test_text_fixtures_present():
     rows = text_fixtures()
     assert len(rows) == 320 and all(u and e for u, e in rows)
@@ -235,12 +187,7 @@ def test_text_kernel_code_on_host(tmp_path, mode):
 
 
 # ---------------------------------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
 
 
 @pytest.mark.gpu
@@ -350,14 +297,6 @@ def test_gpu_snapshot_envelope():
 # tests/golden/snapshot_pending_v135.json.gz: the generator's sessions with 1-3 of the log's updates lost
 # (tools/snap_fixture.py 200:31:120:pending 120:32:200:textpending): applyUpdate leaves pending structs and / or a
 # pending delete set, and encodeStateAsUpdate merges [state, pendingDs, pending structs] (Y@23300).
-PFIX = os.path.join(ROOT, "tests", "golden", "snapshot_pending_v135.json.gz")
-
-
-def pending_fixtures():
-    d = json.load(gzip.open(PFIX, "rt"))
-    return [(bytes.fromhex(u), bytes.fromhex(e)) for u, e in d["rows"]]
-
-
 def test_pending_fixtures_present():
     rows = pending_fixtures()
     assert len(rows) == 320 and all(u and e for u, e in rows)
@@ -371,21 +310,6 @@ def test_pending_fixtures_regenerate(tmp_path):
     rows = pending_fixtures()[:30]
     assert read_in(a) == [u for u, _ in rows]
     assert [e for _, e in read_res(b)] == [e for _, e in rows]
-
-
-def _resolve_pending(st, body, compat135):
-    """A host-compiled kernel result: status 64 (snap::ST_PEND) carries PendHdr + [state, pendingDs, pending structs],
-    which the engine merges with the merge kernels -- here the oracle's mergeUpdates does that step."""
-    import oracle
-    if st != 64:
-        return st, body
-    ln = struct.unpack_from("<IIII", body, 0)
-    assert ln[3] == 0x444E4550
-    parts, p = [], 16
-    for k in range(3):
-        parts.append(body[p:p + ln[k]])
-        p += ln[k]
-    return oracle.merge_updates(parts, compat135=compat135)
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
@@ -411,14 +335,6 @@ def test_pending_kernel_code_on_host(tmp_path, mode):
 
 # sub-documents (ContentDoc: Y.Doc values in a map and an array, overwritten and deleted ones among them), complete and
 # with lost updates (tools/snap_fixture.py 160:61:120:subdoc 100:62:120:subpending)
-SFIX = os.path.join(ROOT, "tests", "golden", "snapshot_subdoc_v135.json.gz")
-
-
-def subdoc_fixtures():
-    d = json.load(gzip.open(SFIX, "rt"))
-    return [(bytes.fromhex(u), bytes.fromhex(e)) for u, e in d["rows"]]
-
-
 def test_subdoc_fixtures_present():
     rows = subdoc_fixtures()
     assert len(rows) == 260 and all(u and e for u, e in rows)
@@ -499,15 +415,6 @@ def test_gpu_snapshot_pending_live_yjs(eng135, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------- read-only SyncStep2
-CFIX = os.path.join(ROOT, "tests", "golden", "contains_v135.json.gz")
-
-
-def contains_fixtures():
-    d = json.load(gzip.open(CFIX, "rt"))
-    states = [bytes.fromhex(s) for s in d["states"]]
-    return [(states[i], bytes.fromhex(u), bool(e)) for i, u, e in d["rows"]]
-
-
 def test_contains_fixtures_present():
     rows = contains_fixtures()
     assert len(rows) > 300 and 0 < sum(e for _, _, e in rows) < len(rows)
@@ -541,15 +448,6 @@ def test_gpu_contains_vs_live_yjs(tmp_path):
 
 # pending states (tools/snap_fixture.py --contains 120 51 pending): the stored state is the merge of a history with
 # lost updates -- its document keeps pending structs / a pending delete set, and Y.snapshot(doc) sees the store alone
-PCFIX = os.path.join(ROOT, "tests", "golden", "contains_pending_v135.json.gz")
-
-
-def contains_pending_fixtures():
-    d = json.load(gzip.open(PCFIX, "rt"))
-    states = [bytes.fromhex(s) for s in d["states"]]
-    return [(states[i], bytes.fromhex(u), bool(e)) for i, u, e in d["rows"]]
-
-
 def test_contains_pending_fixtures_present():
     rows = contains_pending_fixtures()
     assert len(rows) > 300 and 0 < sum(e for _, _, e in rows) < len(rows)

@@ -21,39 +21,12 @@ import subprocess
 
 import pytest
 
-from test_snapshot import BUNDLE, NODE, ROOT, _resolve_pending, fixtures, read_in, read_res, text_fixtures, write_in
+from golden import S2FIX, fixtures, nogc_fixtures, step2_nogc_rows, text_fixtures
+from twins import BUNDLE, NODE, NOGC, ROOT, _kernel_outputs, _parts_reply, _resolve_pending, build_twin, read_in, read_res, run_snaptext, write_in
 
-NFIX = os.path.join(ROOT, "tests", "golden", "snapshot_nogc_v135.json.gz")
-S2FIX = os.path.join(ROOT, "tests", "golden", "step2_nogc_v135.json.gz")
 # the fixture's parts: (first row, rows, seed, maxOps, mode)
 PARTS = ((0, 160, 61, 60, "nogc"), (160, 120, 62, 80, "textnogc"), (280, 40, 63, 60, "subnogc"), (320, 80, 64, 120, "pendingnogc"),
          (400, 24, 11, 80, "nogc"), (424, 24, 21, 150, "textnogc"))
-NOGC = 32   # snap::F_SNAP_NOGC, the host twins' mode bit
-
-
-def nogc_fixtures():
-    d = json.load(gzip.open(NFIX, "rt"))
-    return [(bytes.fromhex(u), bytes.fromhex(e)) for u, e in d["rows"]]
-
-
-def step2_nogc_rows():
-    d = json.load(gzip.open(S2FIX, "rt"))
-    return [(bytes.fromhex(u), bytes.fromhex(sv), None if e is None else bytes.fromhex(e), eq) for u, sv, e, eq in d["rows"]]
-
-
-def build_twin(tmp_path, name):
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "snapdev", name + ".cpp")], check=True, timeout=300)
-    return exe
-
-
-def run_snaptext(exe, tmp_path, updates, flags, budget):
-    """-> (taken indices, 'equals the general code' per document, the text path's results)"""
-    a, b = str(tmp_path / "tin.bin"), str(tmp_path / "tout.bin")
-    write_in(a, updates)
-    r = subprocess.run([exe, a, str(flags), str(budget), b], check=True, timeout=120, capture_output=True, text=True)
-    lines = [tuple(map(int, x.split())) for x in r.stdout.split("\n") if x]
-    return [k for k, (t, _, _) in enumerate(lines) if t], [eq for _, _, eq in lines], read_res(b)
 
 
 def test_nogc_fixtures_present():
@@ -167,7 +140,6 @@ def test_step2_nogc_decomposition_on_host(tmp_path, mode):
     no-GC snapshot diffed keeping the parentSub bit -- a pending state's three parts diffed and merged -- is yjs's reply
     on every row (13.5), and the client-descending rewrite of it in the default mode."""
     from golden import ds_to_desc
-    from test_step2 import _kernel_outputs, _parts_reply
     r = step2_nogc_rows()
     uniq = list(dict.fromkeys(u for u, *_ in r))
     outs = dict(zip(uniq, _kernel_outputs(tmp_path, uniq, mode | NOGC)))

@@ -7,18 +7,14 @@ import shutil
 import numpy as np
 import pytest
 
-from test_snapshot import fixtures, text_fixtures
-from test_snapshot_nogc import NOGC, build_twin, nogc_fixtures, run_snaptext
+from devrun import engine_fixture, read_results, to_device, upload
+from golden import fixtures, nogc_fixtures, text_fixtures
+from twins import NOGC, build_twin, run_snaptext
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
 
 
 @pytest.fixture(scope="module")
@@ -91,22 +87,11 @@ def test_gpu_mixed_lanes(eng135, nrows, monkeypatch, env):
 
 def _device_snapshot(eng, us, opts):
     """ygm_snapshot_opts_v1_device -> ((status, bytes | None) per document, their offsets, the arena's bytes)"""
-    import torch
-    import bench
-    a = np.frombuffer(b"".join(us) + bytes(64), np.uint8)
-    off = np.cumsum([0] + [len(u) for u in us]).astype(np.uint64)
-    dev = torch.device("cuda", 0)
-    ta, to = (torch.from_numpy(x.copy()).to(dev) for x in (a, off.view(np.int64)))
-    topt = torch.from_numpy(np.asarray(opts, np.uint8)).to(dev) if opts is not None else 0
-    r = eng.snapshot_device(ta, len(a) - 64, to, len(us), d_doc_opt=topt)
-    torch.cuda.synchronize()
-    n = len(us)
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    out = [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])] if sts[d] == 0 else None) for d in range(n)]
-    return out, [int(x) for x in offs], len(a) - 64
+    ta, to, nbytes = upload(us)
+    topt = to_device(np.asarray(opts, np.uint8))[0] if opts is not None else 0
+    r = eng.snapshot_device(ta, nbytes, to, len(us), d_doc_opt=topt)
+    out, offs, _ = read_results(r, len(us), places=True)
+    return out, offs, nbytes
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")

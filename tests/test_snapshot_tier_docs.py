@@ -12,43 +12,12 @@ import subprocess
 import pytest
 
 import snapshot_tier_docs as g
-from golden import ds_to_desc
-from test_snapshot import BUNDLE, NODE, ROOT, _resolve_pending, write_in, read_res
-from test_snapshot_nogc import NOGC, build_twin, run_snaptext
+from devrun import same
+from snapshot_tier_docs import FIX, expected, rows
+from twins import BUNDLE, NODE, NOGC, _resolve_pending, build_twin, read_res, run_snaptext, write_in
 
-FIX = os.path.join(ROOT, "tests", "golden", "snapshot_tier_edges_v135.json.gz")
-THROWS = {1, 2, 4, 5}
 GXX = pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")
 CENSUS = {"first": 242, "second": 15, "general": 41, "pending": 11, "throws": 27}
-
-
-def same(exp, got):
-    """statuses agree (a yjs throw == any engine throw status) and bytes agree when OK (test_gpu_parity.same)."""
-    if exp[0] in THROWS:
-        return got[0] in THROWS
-    return exp[0] == got[0] and exp[1] == got[1]
-
-
-_ROWS = None
-
-
-def rows():
-    """{name: (update, (yjs status, bytes), (status, bytes under gc: false))}, read once."""
-    global _ROWS
-    if _ROWS is None:
-        d = json.load(gzip.open(FIX, "rt"))
-        _ROWS = {n: (bytes.fromhex(u), (st, bytes.fromhex(e)), (st, bytes.fromhex(x) if x is not None else b"")) for n, u, st, e, x in d["rows"]}
-        assert len(_ROWS) == len(d["rows"])
-    return _ROWS
-
-
-def expected(d, compat135=True, nogc=False):
-    """What the engine answers: yjs's bytes (the delete set client-descending in the default mode), or the status of a
-    documented refusal."""
-    if d.name in g.UNSUPPORTED:
-        return (9, b"")
-    st, e = rows()[d.name][2 if nogc else 1]
-    return (st, e) if compat135 or st else (st, bytes.fromhex(ds_to_desc(e.hex())))
 
 
 def test_caps_restate_the_layout():

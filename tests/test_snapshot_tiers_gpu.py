@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 import snapshot_tier_docs as g
-from test_snapshot_tier_docs import expected, same
+from devrun import engine_fixture, read_results, same, to_device, upload
+from snapshot_tier_docs import expected
 
 pytestmark = pytest.mark.gpu
 
@@ -38,39 +39,18 @@ def _engine(compat135):
     return Engine(0, compat135=compat135)
 
 
-@pytest.fixture(scope="module")
-def eng135():
-    e = _engine(True)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng136():
-    e = _engine(False)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
+eng136 = engine_fixture(compat135=False)
 
 
 def device_snapshot(eng, us, opts=None, tail=0x00):
     """ygm_snapshot_(opts_)v1_device over an arena from torch (its base 16-aligned), the 64 bytes after it set to `tail`
     -> (status, bytes | None) per document."""
-    import torch
-    import bench
-    a = np.frombuffer(b"".join(us) + bytes([tail]) * 64, np.uint8)
-    off = np.cumsum([0] + [len(u) for u in us]).astype(np.uint64)
-    dev = torch.device("cuda", 0)
-    ta, to = (torch.from_numpy(x.copy()).to(dev) for x in (a, off.view(np.int64)))
+    ta, to, nbytes = upload(us, tail=tail)
     assert ta.data_ptr() % 16 == 0
-    topt = torch.from_numpy(np.asarray(opts, np.uint8)).to(dev) if opts is not None else 0
-    r = eng.snapshot_device(ta, len(a) - 64, to, len(us), d_doc_opt=topt)
-    torch.cuda.synchronize()
-    n = len(us)
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])] if sts[d] == 0 else None) for d in range(n)]
+    topt = to_device(np.asarray(opts, np.uint8))[0] if opts is not None else 0
+    r = eng.snapshot_device(ta, nbytes, to, len(us), d_doc_opt=topt)
+    return read_results(r, len(us))
 
 
 def run_counted(eng, capfd, docs, api="batch", opts=None, tail=0x00):
@@ -247,7 +227,6 @@ def test_scan_past_1024_blocks(eng135, capfd, monkeypatch):
     """262 400 documents: nb = 1 026 scan blocks, the second round of k_snap_scan_top's loop.  Built with numpy,
     compared per kind of document with gathers."""
     import torch
-    import bench
     monkeypatch.setenv("YGM_SNAP_NOLDS", "1")
     n = 262400
     f = g.families()["F"]
@@ -270,10 +249,7 @@ def test_scan_past_1024_blocks(eng135, capfd, monkeypatch):
     pend = int((kinds == 1).sum())
     assert lines == [(str(n), "0", "0", str(n), str(pend))], lines
     assert s1.docs_pending - s0.docs_pending == pend and s1.docs_snapshot - s0.docs_snapshot == n
-    offs = bench._d2h(r.off, n * 8).view(np.uint64).astype(np.int64)
-    ln = bench._d2h(r.len, n * 8).view(np.uint64).astype(np.int64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes))
+    sts, offs, ln, data = read_results(r, n, sync=False, raw=True)      # (the wait is above, inside the timed part)
     for k, d in enumerate(f):
         st, e = expected(d, True)
         sel = kinds == k

@@ -19,12 +19,11 @@ import subprocess
 import pytest
 
 import oracle
+from devrun import engine_fixture
+from twins import BUNDLE, NODE, ROOT, _kernel_outputs, _parts_reply
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = os.path.join(ROOT, "tests", "golden", "step2_v135.json.gz")
 SNAPS = [os.path.join(ROOT, "tests", "golden", f) for f in ("snapshot_v135.json.gz", "snapshot_text_v135.json.gz")]
-NODE = shutil.which("node")
-BUNDLE = os.path.exists("/opt/conda/share/jupyter/lab/static/3502.fbe0c610be82ba1360db.js")
 
 
 def rows():
@@ -81,12 +80,7 @@ def test_oracle_plain_diff_differs_only_by_the_bit():
             assert len(got) == len(exp) and all((a ^ b) in (0, 0x20) for a, b in zip(got, exp))
 
 
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
 
 
 @pytest.mark.gpu
@@ -144,32 +138,6 @@ def test_step2_pending_fixtures_regenerate(tmp_path):
     out = str(tmp_path / "s2p.json.gz")
     subprocess.run([NODE, os.path.join(ROOT, "tools", "step2_corpus.js"), out, "pending"], check=True, timeout=600, capture_output=True)
     assert json.load(gzip.open(out, "rt"))["rows"] == json.load(gzip.open(PFIX, "rt"))["rows"]
-
-
-def _parts_reply(body, st, sv, compat135):
-    """The reply from the kernel code's output: a complete state's snapshot diffed keeping the bit; a pending one's
-    three parts (PendHdr) diffed (state: keeping the bit, pending structs: plain) and merged -- the engine's steps."""
-    import struct
-    if st == 0:
-        return oracle.diff_update(body, sv, compat135=compat135, keep_sub=True)
-    assert st == 64
-    ln = struct.unpack_from("<IIII", body, 0)
-    a, b, c = body[16:16 + ln[0]], body[16 + ln[0]:16 + ln[0] + ln[1]], body[16 + ln[0] + ln[1]:16 + ln[0] + ln[1] + ln[2]]
-    sa, da = oracle.diff_update(a, sv, compat135=compat135, keep_sub=True)
-    sc, dc = oracle.diff_update(c, sv, compat135=compat135)
-    if sa or sc:
-        return (sa or sc), None
-    return oracle.merge_updates([da, b, dc], compat135=compat135)
-
-
-def _kernel_outputs(tmp_path, states, mode):
-    from test_snapshot import write_in, read_res
-    exe = str(tmp_path / "snapdev")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "snapdev", "snapdev.cpp")], check=True, timeout=300)
-    a, b = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-    write_in(a, states)
-    subprocess.run([exe, a, b, str(mode)], check=True, timeout=120)
-    return read_res(b)
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")

@@ -6,7 +6,7 @@ snapshot corpus, pending states kept; rows where 13.5's writeString throws on a 
 import pytest
 
 import oracle
-from test_snapshot_nogc import nogc_fixtures, step2_nogc_rows
+from golden import nogc_fixtures, step2_nogc_rows
 
 pytestmark = pytest.mark.gpu
 

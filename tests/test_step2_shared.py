@@ -11,6 +11,7 @@ import os
 import pytest
 
 import oracle
+from devrun import engine_fixture
 from v1util import rd_vu, vu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,12 +57,7 @@ def differing(res, exp):
     return [k for k, (g, e) in enumerate(zip(res, exp)) if (g[0] != 4 if e is None else g != (0, e))]
 
 
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
 
 
 # ---------------------------------------------------------------------------------------- 1: the fixture, grouped

@@ -15,6 +15,7 @@ import pytest
 
 import snapshot_tier_docs as g
 import text_fixture as tf
+from devrun import engine_fixture, read_results, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -36,18 +37,8 @@ def _engine(compat135):
     return Engine(0, compat135=compat135)
 
 
-@pytest.fixture(scope="module")
-def eng135():
-    e = _engine(True)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng136():
-    e = _engine(False)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
+eng136 = engine_fixture(compat135=False)
 
 
 def host_text(eng, states, names, deep):
@@ -57,28 +48,16 @@ def host_text(eng, states, names, deep):
 
 def device_text(eng, states, names, deep, tail=0x00):
     """ygm_text_v1_device over arenas from torch, the 64 bytes after each set to `tail` -> (status, bytes | None)."""
-    import torch
-    import bench
-    dev = torch.device("cuda", 0)
-
-    def up(blobs):
-        a = np.frombuffer(b"".join(blobs) + bytes([tail]) * 64, np.uint8)
-        off = np.cumsum([0] + [len(b) for b in blobs]).astype(np.uint64)
-        return torch.from_numpy(a.copy()).to(dev), torch.from_numpy(off.view(np.int64).copy()).to(dev), len(a) - 64
-    ta, to, nbytes = up(states)
-    tn, tno, _ = up(names)
+    ta, to, nbytes = upload(states, tail=tail)
+    tn, tno, _ = upload(names, tail=tail)
     assert ta.data_ptr() % 16 == 0
     n = len(states)
     r = eng.text_device(ta, nbytes, to, tn, tno, n, deep=deep)
-    torch.cuda.synchronize()
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    assert int(r.payload_bytes) == int(sum(int(lens[d]) for d in range(n) if sts[d] == 0))
+    res, offs, lens = read_results(r, n, places=True)
+    assert int(r.payload_bytes) == sum(lens[d] for d in range(n) if res[d][0] == 0)
     for d in range(n):
-        assert sts[d] != 0 or int(offs[d]) + int(lens[d]) <= int(r.data_bytes)
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])] if sts[d] == 0 else None) for d in range(n)]
+        assert res[d][0] != 0 or offs[d] + lens[d] <= int(r.data_bytes)
+    return res
 
 
 def run(eng, capfd, states, names, deep=False, api="batch", tail=0x00):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import tojson_fixture as tf
+from devrun import engine_fixture, read_results, upload
 from v1util import vu
 
 pytestmark = pytest.mark.gpu
@@ -32,38 +33,21 @@ def knobs(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng = engine_fixture(compat135=True)
 
 
 def device_tojson(eng, states, names, kind, lead=0):
     """ygm_tojson_v1_device over arenas from torch (the first state `lead` bytes into its arena) -> (status, bytes)."""
-    import torch
-    import bench
-    dev = torch.device("cuda", 0)
-
-    def up(blobs, lead):
-        a = np.frombuffer(b"\xee" * lead + b"".join(blobs) + bytes(64), np.uint8).copy()
-        off = (lead + np.cumsum([0] + [len(b) for b in blobs])).astype(np.uint64)
-        return torch.from_numpy(a).to(dev), torch.from_numpy(off.view(np.int64).copy()).to(dev), int(off[-1])
-    ta, to, nbytes = up(states, lead)
-    tn, tno, _ = up(names, 0)
+    ta, to, nbytes = upload(states, lead=lead)
+    tn, tno, _ = upload(names)
     assert ta.data_ptr() % 16 == 0
     n = len(states)
     r = eng.tojson_device(ta, nbytes, to, tn, tno, n, kind)
-    torch.cuda.synchronize()
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    assert int(r.payload_bytes) == int(sum(int(lens[d]) for d in range(n) if sts[d] == 0))
+    res, offs, lens = read_results(r, n, every=True, places=True)
+    assert int(r.payload_bytes) == sum(lens[d] for d in range(n) if res[d][0] == 0)
     for d in range(n):
-        assert int(offs[d]) + int(lens[d]) <= int(r.data_bytes) and (sts[d] == 0 or lens[d] == 0)
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])]) for d in range(n)]
+        assert offs[d] + lens[d] <= int(r.data_bytes) and (res[d][0] == 0 or lens[d] == 0)
+    return res
 
 
 def run(eng, capfd, states, names, kind, api="batch", lead=0):

@@ -13,6 +13,7 @@ import os
 import pytest
 
 import oracle
+from devrun import engine_fixture
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 THROW = {1, 2, 4, 5}
@@ -99,20 +100,8 @@ def test_v2_empty_merge_is_the_empty_v2_update():
 
 
 # ------------------------------------------------------------------ GPU (through the C ABI)
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
+eng = engine_fixture()
 
 
 def gpu_batch(e, op, cases):

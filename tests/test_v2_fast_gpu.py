@@ -19,23 +19,15 @@ import numpy as np
 import pytest
 
 import oracle
-from test_lean_fast_parse import CLIENTS, Log, item, text, upd
+from devrun import THROWS, engine_fixture, read_results, same, to_device
+from lean_docs import CLIENTS, Log, item, text, upd
 from v1util import vu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-THROWS = {1, 2, 4, 5}
 gpu = pytest.mark.gpu
 SV0 = b"\x00"            # the empty state vector: the diff is the whole state
 F_IN = 7168              # v2f::F_IN, the large tier's cap; 3328: the small tier's
 EXACT_L = [3327, 3328, 3329, 7167, 7168, 7169, 8000]
-
-
-def same(o, g):
-    so, bo = o
-    sg, bg = g
-    if so in THROWS:
-        return sg in THROWS
-    return so == sg and bo == bg
 
 
 def v2(u):
@@ -301,30 +293,12 @@ def test_corpus_flags_match_the_host_twin(twin):
 
 
 # ---------------------------------------------------------------- device runs
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
-
-
-def _dev(*arrs):
-    import torch
-    dev = torch.device("cuda", 0)
-    return [torch.from_numpy(a.copy()).to(dev) for a in arrs]
+eng = engine_fixture()
 
 
 def _fetch(r, n):
-    import torch
-    import bench
-    torch.cuda.synchronize()
-    off = bench._d2h(r.off, n * 8).view(np.uint64)
-    ln = bench._d2h(r.len, n * 8).view(np.uint64)
-    st = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    res = [(int(st[d]), data[int(off[d]):int(off[d]) + int(ln[d])] if st[d] == 0 else None) for d in range(n)]
-    return res, [int(x) for x in off], [int(x) for x in ln], int(r.payload_bytes)
+    res, off, ln = read_results(r, n, places=True)
+    return res, off, ln, int(r.payload_bytes)
 
 
 def _arena(blobs):
@@ -339,7 +313,7 @@ def run_merge(eng, docs):
     blobs = [u for us in docs for u in us]
     a, off = _arena(blobs)
     du = np.cumsum([0] + [len(us) for us in docs]).astype(np.uint32)
-    ta, to, td = _dev(a, off.view(np.int64), du.view(np.int32))
+    ta, to, td = to_device(a, off.view(np.int64), du.view(np.int32))
     r = eng.merge_v2_device(ta, len(a) - 64, to, td, len(blobs), len(docs))
     return _fetch(r, len(docs)) + ([int(x) for x in off[du[:-1]]], len(a) - 64)
 
@@ -347,10 +321,10 @@ def run_merge(eng, docs):
 def run_doc(eng, op, updates, svs=None):
     """updates through Engine.doc_v2_device ('diff' with svs, 'sv')."""
     a, off = _arena(updates)
-    ta, to = _dev(a, off.view(np.int64))
+    ta, to = to_device(a, off.view(np.int64))
     if op == "diff":
         s, soff = _arena(svs)
-        ts, tso = _dev(s, soff.view(np.int64))
+        ts, tso = to_device(s, soff.view(np.int64))
         r = eng.doc_v2_device("diff", ta, len(a) - 64, to, len(updates), ts, tso)
     else:
         r = eng.doc_v2_device(op, ta, len(a) - 64, to, len(updates))

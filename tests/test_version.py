@@ -10,77 +10,14 @@ import gzip
 import json
 import os
 import shutil
-import struct
 import subprocess
 
 import pytest
 
-from test_snapshot import BUNDLE, NODE, ROOT, _resolve_pending, read_res
-from v1util import encode_ds, rd_vu, read_ds, vu
+from golden import REFUSALS, VFIX, _sv, expected, version_rows, version_to_desc
+from twins import BUNDLE, NODE, ROOT, _resolve_pending, run_twin
 
-VFIX = os.path.join(ROOT, "tests", "golden", "version_v135.json.gz")
 FAMILIES = ("general", "text", "pending", "subdoc", "crafted", "edge", "align")
-
-
-def version_rows():
-    """-> dicts: family, state, version, take (bytes), restored / restored_nogc (bytes, or None where yjs throws)"""
-    d = json.load(gzip.open(VFIX, "rt"))
-    out = []
-    for r in d["rows"]:
-        o = {"family": r["family"], "note": r.get("note", "")}
-        for k in ("state", "version", "take"):
-            o[k] = bytes.fromhex(r[k])
-        for k in ("restored", "restored_nogc"):
-            o[k] = None if r[k] == "throws" else bytes.fromhex(r[k])
-        out.append(o)
-    return out
-
-
-def version_to_desc(v):
-    """An encoded Snapshot V1 as yjs 13.6 writes it: delete-set clients and state-vector clients descending."""
-    ds, p = read_ds(v, 0)
-    n, p = rd_vu(v, p)
-    sv = []
-    for _ in range(n):
-        c, p = rd_vu(v, p)
-        k, p = rd_vu(v, p)
-        sv.append((c, k))
-    o = bytearray(encode_ds(sorted(ds, key=lambda e: -e[0]))) + vu(len(sv))
-    for c, k in sorted(sv, key=lambda e: -e[0]):
-        o += vu(c) + vu(k)
-    return bytes(o)
-
-
-def update_to_desc(u):
-    from golden import ds_to_desc
-    return bytes.fromhex(ds_to_desc(u.hex()))
-
-
-def expected(row, key, compat135):
-    e = row[key]
-    if e is None or compat135:
-        return e
-    return version_to_desc(e) if key == "take" else update_to_desc(e)
-
-
-def write_pairs(path, pairs):
-    with open(path, "wb") as f:
-        f.write(struct.pack("<I", len(pairs)))
-        for s, v in pairs:
-            f.write(struct.pack("<I", len(s)) + s + struct.pack("<I", len(v)) + v)
-
-
-def run_twin(tmp_path, pairs, mode):
-    """-> per pair (take, cut, restored, restored_nogc), each (status, bytes)"""
-    exe = str(tmp_path / "versiondev")
-    if not os.path.exists(exe):
-        subprocess.run(["g++", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "snapdev", "versiondev.cpp")], check=True, timeout=300)
-    a, b = str(tmp_path / "vin.bin"), str(tmp_path / "vout.bin")
-    write_pairs(a, pairs)
-    subprocess.run([exe, a, b, str(mode)], check=True, timeout=300)
-    r = read_res(b)
-    assert len(r) == 4 * len(pairs)
-    return [tuple(r[4 * k:4 * k + 4]) for k in range(len(pairs))]
 
 
 def test_version_fixtures_present():
@@ -147,30 +84,9 @@ def test_version_throwing_rows_are_einval(tmp_path):
     assert rows and all(cut[0] == 8 and res[0] == 8 and resn[0] == 8 for _t, cut, res, resn in got)
 
 
-def _sv(pairs, ds=b"\x00"):
-    o = bytearray(ds) + vu(len(pairs))
-    for c, k in pairs:
-        o += vu(c) + vu(k)
-    return bytes(o)
-
-
 def _state7():
     rows = [r for r in version_rows() if r["note"] == "cut at a struct boundary"]
     return rows[0]["state"]
-
-
-REFUSALS = (
-    ("truncated state vector", lambda: _sv([(7, 3)])[:-1], 1),
-    ("truncated delete set", lambda: bytes([1, 7, 1, 0]), 1),
-    ("empty version", lambda: b"", 1),
-    ("varuint above 2^53", lambda: b"\x00\x01\x07" + b"\xff" * 8 + b"\x7f", 2),
-    ("non-minimal varuint", lambda: b"\x00\x01\x87\x00\x03", 3),
-    ("client repeated in the state vector", lambda: _sv([(7, 3), (7, 2)]), 3),
-    ("client repeated in the delete set", lambda: _sv([(7, 3)], ds=bytes([2, 7, 1, 0, 1, 7, 1, 2, 1])), 3),
-    ("clock above the state's", lambda: _sv([(7, 6)]), 8),
-    ("client the state does not have", lambda: _sv([(7, 3), (8, 1)]), 8),
-    ("4097 state-vector entries", lambda: _sv([(7, 3)] + [(1000 + i, 0) for i in range(4096)]), 9),
-)
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host compiler")

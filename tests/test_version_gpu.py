@@ -5,19 +5,12 @@ of test_version.py (tests/golden/version_v135.json.gz)."""
 import numpy as np
 import pytest
 
-from test_version import REFUSALS, _sv, expected, version_rows
+from devrun import engine_fixture, read_results, upload
+from golden import REFUSALS, UNSUP_STATE, _sv, expected, fixtures, version_rows
 
 pytestmark = pytest.mark.gpu
 
-UNSUP_STATE = bytes([2, 1, 5, 0, 0, 1, 1, 5, 1, 0, 1, 0])   # client 5's block twice: outside the snapshot envelope
-
-
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
 
 
 @pytest.fixture(scope="module")
@@ -71,39 +64,20 @@ def test_gpu_version_fixture_parity(rows, mode):
             assert e.stats().docs_pending > p0, fam
 
 
-def _to_dev(blobs):
-    import torch
-    a = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)
-    off = np.cumsum([0] + [len(u) for u in blobs]).astype(np.uint64)
-    dev = torch.device("cuda", 0)
-    return torch.from_numpy(a.copy()).to(dev), torch.from_numpy(off.view(np.int64).copy()).to(dev), len(a) - 64
-
-
-def _from_dev(r, n):
-    import torch
-    import bench
-    torch.cuda.synchronize()
-    offs = bench._d2h(r.off, n * 8).view(np.uint64)
-    lens = bench._d2h(r.len, n * 8).view(np.uint64)
-    sts = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    return [(int(sts[d]), data[int(offs[d]):int(offs[d]) + int(lens[d])] if sts[d] == 0 else None) for d in range(n)]
-
-
 @pytest.mark.parametrize("mode", [1, 0])
 def test_gpu_version_device_forms(rows, mode):
     """The same parity through ygm_version_take_v1_device / ygm_version_restore_v1_device, options alternating."""
     import torch
     from hocuspocus_amd import Engine
     n = len(rows)
-    ts, tso, sb = _to_dev([r["state"] for r in rows])
-    tv, tvo, _ = _to_dev([r["version"] for r in rows])
+    ts, tso, sb = upload([r["state"] for r in rows])
+    tv, tvo, _ = upload([r["version"] for r in rows])
     opts = [k % 2 for k in range(n)]
     topt = torch.from_numpy(np.asarray(opts, np.uint8)).to(ts.device)
     with Engine(0, compat135=bool(mode)) as e:
-        take = _from_dev(e.version_take_device(ts, sb, tso, n), n)
-        got = _from_dev(e.version_restore_device(ts, tso, tv, tvo, n, d_restored_opt=topt), n)
-        got0 = _from_dev(e.version_restore_device(ts, tso, tv, tvo, n), n)
+        take = read_results(e.version_take_device(ts, sb, tso, n), n)
+        got = read_results(e.version_restore_device(ts, tso, tv, tvo, n, d_restored_opt=topt), n)
+        got0 = read_results(e.version_restore_device(ts, tso, tv, tvo, n), n)
     res = [got0[k] for k in range(n)]
     resn = [got[k] if opts[k] else (0, expected(rows[k], "restored_nogc", mode)) if rows[k]["restored"] is not None else (8, None) for k in range(n)]
     bad = _check(rows, take, res, resn, mode)
@@ -194,7 +168,6 @@ def test_gpu_version_chunked_host_api(good, monkeypatch):
 
 def test_gpu_old_entry_points_unchanged(eng135, good):
     """snapshot_batch on the same context returns the same bytes before and after a restore call."""
-    from test_snapshot import fixtures
     rows = fixtures()[:80]
     us = [u for u, _ in rows]
     before = eng135.snapshot_batch(us)

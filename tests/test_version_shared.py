@@ -5,7 +5,6 @@ them, a null context is refused before any device work -- and the fixture tests/
 "throws" per version), checked pair by pair on the host twin of the device code (tools/snapdev/versiondev.cpp).  No
 compute calls: runs without a GPU.  The GPU tests are in test_version_shared_gpu.py."""
 import ctypes
-import functools
 import gzip
 import json
 import os
@@ -15,31 +14,13 @@ import subprocess
 
 import pytest
 
-from test_snapshot import BUNDLE, NODE, ROOT, _resolve_pending
-from test_version import expected, run_twin
+from golden import HFIX, expected, history_docs
+from twins import BUNDLE, NODE, ROOT, _resolve_pending, run_twin
 
 import hocuspocus_amd.engine as eng
 
-HFIX = os.path.join(ROOT, "tests", "golden", "version_history_v135.json.gz")
 FAMILIES = ("text", "clients", "many", "pending", "crafted", "empty", "large")
 NEW = ("ygm_version_restore_shared_v1", "ygm_version_restore_shared_v1_device")
-
-
-@functools.lru_cache(maxsize=None)
-def history_docs():
-    """-> dicts: family, state (bytes), versions: dicts of note, version (bytes), restored / restored_nogc (bytes, or
-    None where yjs throws)"""
-    d = json.load(gzip.open(HFIX, "rt"))
-    out = []
-    for doc in d["docs"]:
-        vs = []
-        for v in doc["versions"]:
-            o = {"note": v.get("note", ""), "version": bytes.fromhex(v["version"])}
-            for k in ("restored", "restored_nogc"):
-                o[k] = None if v[k] == "throws" else bytes.fromhex(v[k])
-            vs.append(o)
-        out.append({"family": doc["family"], "state": bytes.fromhex(doc["state"]), "versions": vs})
-    return tuple(out)
 
 
 def header():

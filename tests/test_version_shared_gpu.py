@@ -8,21 +8,15 @@ pair form run here."""
 import numpy as np
 import pytest
 
-from test_version import REFUSALS, _sv, expected, version_rows
-from test_version_gpu import UNSUP_STATE, _from_dev, _to_dev
-from test_version_shared import history_docs
+from devrun import engine_fixture, read_results, upload
+from golden import REFUSALS, UNSUP_STATE, _sv, expected, fixtures, history_docs, version_rows
 
 pytestmark = pytest.mark.gpu
 
 EINVAL = 8
 
 
-@pytest.fixture(scope="module")
-def eng135():
-    from hocuspocus_amd import Engine
-    e = Engine(0, compat135=True)
-    yield e
-    e.close()
+eng135 = engine_fixture(compat135=True)
 
 
 @pytest.fixture(scope="module")
@@ -52,13 +46,13 @@ def _want(row, opt, mode=1):
 
 def _device_call(e, states, ask_state, versions, opts=None):
     import torch
-    ts, tso, sb = _to_dev(states)
-    tv, tvo, _ = _to_dev(versions)
+    ts, tso, sb = upload(states)
+    tv, tvo, _ = upload(versions)
     dev = ts.device
     ta = torch.from_numpy(np.asarray(ask_state, np.int64).astype(np.uint32).view(np.int32).copy()).to(dev) if len(ask_state) else torch.zeros(1, dtype=torch.int32, device=dev)
     topt = 0 if opts is None else torch.from_numpy(np.asarray(list(opts) + [0], np.uint8)).to(dev)
     r = e.version_restore_shared_device(ts, sb, tso, len(states), tv, tvo, ta, len(ask_state), d_restored_opt=topt)
-    return _from_dev(r, len(ask_state))
+    return read_results(r, len(ask_state))
 
 
 # ---------------------------------------------------------------------------------------- fixture parity
@@ -230,7 +224,6 @@ def test_gpu_shared_chunked_host_api(monkeypatch):
 def test_gpu_shared_leaves_old_entry_points_unchanged(eng135):
     """restore_version_batch and snapshot_batch on the same context return the same bytes before and after a shared
     call."""
-    from test_snapshot import fixtures
     rows = fixtures()[:80]
     us = [u for u, _ in rows]
     good = [r for r in version_rows() if r["restored"] is not None][:40]

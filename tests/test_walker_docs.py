@@ -3,24 +3,8 @@ its construction says, every item that is meant to be valid is one yjs answers, 
 the residues they name, and the label predicate agrees with labels written by hand."""
 import collections
 
-import oracle
-
 import walker_docs as g
-
-_EXP = {}
-
-
-def expected(it, mode, compat135=False):
-    """yjs's answer for an item, (status, bytes | None), computed once per distinct (update, sv)."""
-    key = (it[1], it[2] if mode == "diff" else None, compat135)
-    if key not in _EXP:
-        r = oracle.diff_update(it[1], it[2], compat135=compat135) if mode == "diff" else oracle.encode_state_vector_from_update(it[1], compat135=compat135)
-        _EXP[key] = (r[0], r[1] if r[0] == 0 else None)
-    return _EXP[key]
-
-
-def flat(batches):
-    return [it for b in batches for it in b]
+from walker_docs import expected, flat
 
 
 def counts(batches):

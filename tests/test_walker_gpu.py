@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import walker_docs as g
-from test_walker_docs import expected, flat
+from devrun import engine_fixture, read_results, upload
+from walker_docs import expected, flat
 
 pytestmark = pytest.mark.gpu
 
@@ -32,12 +33,7 @@ def tier_counts(monkeypatch):
     print("\n".join(NOTES))
 
 
-@pytest.fixture(scope="module")
-def eng():
-    from hocuspocus_amd import Engine
-    e = Engine(0)
-    yield e
-    e.close()
+eng = engine_fixture()
 
 
 @pytest.fixture(scope="module")
@@ -47,26 +43,14 @@ def fam():
 
 def _dev(blobs, tail):
     """The blobs back to back in a torch allocation, 64 bytes of `tail` after them -> (arena, offsets, bytes)."""
-    import torch
-    raw = b"".join(blobs)
-    a = np.frombuffer(raw + bytes([tail]) * 64, np.uint8).copy()
-    off = np.cumsum([0] + [len(b) for b in blobs]).astype(np.int64)
-    dev = torch.device("cuda", 0)
-    ta, to = torch.from_numpy(a).to(dev), torch.from_numpy(off).to(dev)
+    ta, to, nbytes = upload(blobs, tail=tail)
     assert ta.data_ptr() % 256 == 0
-    return ta, to, len(raw)
+    return ta, to, nbytes
 
 
 def _read(r, n):
-    import bench
-    import torch
-    torch.cuda.synchronize()
-    off = bench._d2h(r.off, n * 8).view(np.uint64)
-    ln = bench._d2h(r.len, n * 8).view(np.uint64)
-    st = bench._d2h(r.status, n * 4).view(np.int32)
-    data = bench._d2h(r.data, int(r.data_bytes)).tobytes()
-    res = [(int(st[d]), data[int(off[d]):int(off[d]) + int(ln[d])] if st[d] == 0 else None) for d in range(n)]
-    return res, [int(x) for x in off]
+    res, off, _ = read_results(r, n, places=True)
+    return res, off
 
 
 def call(eng, batch, mode, form="host", tail=0x00):

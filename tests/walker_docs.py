@@ -9,7 +9,7 @@ Python of the envelope documented in the header of ygm_doc_walk.hpp and above k_
 library.  `valid` says that yjs answers both operations (the tests ask the oracle for the bytes either way).
 
 `families()` maps a family letter to a list of batches, a batch being a list of items packed one after the other the
-way Engine._pack does (`offsets`).  Pure Python, deterministic: no library, no torch."""
+way Engine._pack does (`offsets`).  Pure Python, deterministic: no library, no torch (`expected` alone asks the oracle)."""
 import random
 
 from v1util import encode_ds, vu
@@ -641,3 +641,20 @@ def family_i():
 def families():
     return {"A": family_a(), "B": family_b(), "C": family_c(), "D": family_d(), "E": family_e(), "F": family_f(),
             "G": family_g(), "H": family_h()}
+
+
+def flat(batches):
+    return [it for b in batches for it in b]
+
+
+_EXP = {}
+
+
+def expected(it, mode, compat135=False):
+    """yjs's answer for an item, (status, bytes | None), computed once per distinct (update, sv)."""
+    import oracle
+    key = (it[1], it[2] if mode == "diff" else None, compat135)
+    if key not in _EXP:
+        r = oracle.diff_update(it[1], it[2], compat135=compat135) if mode == "diff" else oracle.encode_state_vector_from_update(it[1], compat135=compat135)
+        _EXP[key] = (r[0], r[1] if r[0] == 0 else None)
+    return _EXP[key]

@@ -39,7 +39,7 @@ def corpora(n_docs):
 
 
 def main():
-    from test_lean_fast_parse import run_device
+    from devrun import run_merge
     n_docs = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
     L = eng.lib()
     L.ygm_diag_id5_read.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -54,7 +54,7 @@ def main():
         got = []
         for ctx in (e, g):
             L.ygm_diag_id5_read(buf.ctypes.data, 1)
-            run_device(ctx, docs, "lens")
+            run_merge(ctx, docs, "lens")
             L.ygm_diag_id5_read(buf.ctypes.data, 0)
             got.append((int(buf[0]), int(buf[1])))
         ok = got[0] == (len(docs), want) and got[1] == (len(docs), 0)
